@@ -12,7 +12,19 @@ RCCL all-gather of the per-tensor compressed sizes (N > 1) -> floatDecompress.
 value = (uncompressed bytes of the whole batch) / max over ranks of the step
 time  (GB/s = 1e9 B/s, reference convention benchmark.py:158-159).
 
+A plain run does only what the headline needs: set-up, warm-up, settle, the K
+timed steps, the output dump if asked for, and the result line.  Everything
+else (round-trip check, per-kernel times and roofline, isolated cold / warm
+decode, the CPU oracle baseline and the secondary configs) runs with --full.
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers (compressed sizes, archives, decoded tensors, status) as
+DIR/<name>.npy, float32 / float64; large buffers as a fixed seeded sample
+plus exact per-tensor integer checksums.  The inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
+
 Run:  python bench.py [--gpus N --steps K --warmup W] [--workload c2|c5]
+                      [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -45,6 +57,12 @@ def parse():
     p.add_argument("--c5-batch", type=int, default=8192, help="c5 tensors in the whole job")
     p.add_argument("--words", type=int, default=524288)
     p.add_argument("--prob-bits", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: round-trip check, per-kernel times "
+                        "and roofline, cold / warm decode, CPU baseline, secondary configs (extras); "
+                        "the --no-* options below select among these")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample", type=int, default=256,
                    help="tensors of the batch timed on the CPU oracle (rank 0, N=1)")
@@ -129,7 +147,8 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    if args.verify:
+    full = args.full
+    if full and args.verify:
         assert bool((ok == 1).all()), "decode reported failure"
         assert torch.equal(out.view(torch.int16), x.view(torch.int16)), "roundtrip mismatch"
     comp_bytes = int(sizes.to(torch.int64).sum().item())
@@ -147,14 +166,16 @@ def main():
     # the dominant kernel family, from one profiled step (event pair around
     # every launch); the full per-kernel breakdown is taken after the timed
     # region so that the timed steps follow the settle phase directly
-    C.profile_reset()
-    C.profile_filter(None)
-    C.profile(True)
-    step()
-    torch.cuda.synchronize()
-    C.profile(False)
-    probe = query_families()
-    dominant = max(probe, key=lambda k: probe[k]["avg_ms"]) if probe else None
+    dominant = None
+    if full:
+        C.profile_reset()
+        C.profile_filter(None)
+        C.profile(True)
+        step()
+        torch.cuda.synchronize()
+        C.profile(False)
+        probe = query_families()
+        dominant = max(probe, key=lambda k: probe[k]["avg_ms"]) if probe else None
 
     # settle: untimed steps for a fixed wall time (clock ramp; no work of the
     # timed region is skipped or cached by it).  The step count is fixed up
@@ -175,12 +196,14 @@ def main():
     settle_steps += 8
     settle_ms = (time.perf_counter() - t_s) * 1e3
 
-    # timed region: barrier + sync on both sides, K steps, max over ranks; the
-    # dominant kernel is timed live with hipEvents on its launch stream (only
-    # that family is recorded, so the other launches run back to back)
-    C.profile_reset()
-    C.profile_filter(dominant)
-    C.profile(not args.no_kernel_events and dominant is not None)
+    # timed region: barrier + sync on both sides, K steps, max over ranks; with
+    # --full the dominant kernel is timed live with hipEvents on its launch
+    # stream (only that family is recorded, so the other launches run back to
+    # back)
+    if full:
+        C.profile_reset()
+        C.profile_filter(dominant)
+        C.profile(not args.no_kernel_events and dominant is not None)
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
@@ -191,32 +214,37 @@ def main():
     if distributed:
         dist.barrier()
     t1 = time.perf_counter()
-    C.profile(False)
-    C.profile_filter(None)
-    live = query_families()
-    # per-kernel breakdown of the other families: a profiled pass after the
-    # timed region
-    C.profile_reset()
-    C.profile(True)
-    for _ in range(max(args.warmup, 3)):
-        step()
-    torch.cuda.synchronize()
-    C.profile(False)
-    breakdown = query_families()
-    # decode from HBM-sourced archives: the step above
-    # decodes archives the compressor has just written, most of which are
-    # still in the 256 MiB Infinity Cache (MALL).  Here, after each compress,
-    # a 512 MiB fill evicts them before the decode is timed alone; the same
-    # isolated timing without the fill is the warm figure.  Untimed for the
-    # headline, which stays the reference's compress -> decompress loop.
-    decode_cold = None if world > 1 else _decode_cold_warm(step_parts=(
-        lambda: N.check(L.dietgpu_float_compress(ws.h, ft, pb, 0, nb, in_ptrs, in_size, comp_ptrs,
-                                                 sizes.data_ptr(), stream)),
-        lambda: N.check(L.dietgpu_float_decompress(ws.h, ft, pb, 0, nb, comp_ptrs, out_ptrs, caps,
-                                                   ok.data_ptr(), osz.data_ptr(), stream))), dev=dev)
-    if args.verify:
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, rank, world, comp, sizes, out, ok, osz)
+    live = breakdown = {}
+    decode_cold = None
+    if full:
+        C.profile(False)
+        C.profile_filter(None)
+        live = query_families()
+        # per-kernel breakdown of the other families: a profiled pass after the
+        # timed region
+        C.profile_reset()
+        C.profile(True)
+        for _ in range(max(args.warmup, 3)):
+            step()
         torch.cuda.synchronize()
-        assert torch.equal(out.view(torch.int16), x.view(torch.int16)), "roundtrip mismatch (cold decode)"
+        C.profile(False)
+        breakdown = query_families()
+        # decode from HBM-sourced archives: the step above
+        # decodes archives the compressor has just written, most of which are
+        # still in the 256 MiB Infinity Cache (MALL).  Here, after each compress,
+        # a 512 MiB fill evicts them before the decode is timed alone; the same
+        # isolated timing without the fill is the warm figure.  Untimed for the
+        # headline, which stays the reference's compress -> decompress loop.
+        decode_cold = None if world > 1 else _decode_cold_warm(step_parts=(
+            lambda: N.check(L.dietgpu_float_compress(ws.h, ft, pb, 0, nb, in_ptrs, in_size, comp_ptrs,
+                                                     sizes.data_ptr(), stream)),
+            lambda: N.check(L.dietgpu_float_decompress(ws.h, ft, pb, 0, nb, comp_ptrs, out_ptrs, caps,
+                                                       ok.data_ptr(), osz.data_ptr(), stream))), dev=dev)
+        if args.verify:
+            torch.cuda.synchronize()
+            assert torch.equal(out.view(torch.int16), x.view(torch.int16)), "roundtrip mismatch (cold decode)"
     elapsed = t1 - t0
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -229,6 +257,29 @@ def main():
         comp_total = comp_bytes
     ms_per_step = elapsed / args.steps * 1e3
     value = total * n * 2 * args.steps / elapsed / 1e9
+    line = {
+        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "settle_ms": round(settle_ms, 1), "settle_steps": settle_steps,
+        "higher_is_better": True,
+        "scaling": "strong" if workload == "c5" else "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic",
+        "distributed": distributed,
+        "config": {"workload": (f"c5: batch={total} x {n * 2 // 1048576} MiB bf16 N(0,1) in total, "
+                                f"{nb} per GPU" if workload == "c5" else
+                                f"c2: batch={nb} x {n * 2 // 1048576} MiB bf16 N(0,1) per GPU"),
+                   "batch_per_gpu": nb, "words_per_tensor": n, "prob_bits": pb,
+                   "api": "floatCompress + floatDecompress (pointer API, C ABI)",
+                   "parallelism": f"dp{world} (independent shards + RCCL size all-gather)"},
+        "ratio": round(comp_total / (total * n * 2), 5),
+    }
+    if not full:  # the plain run ends here: the headline alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
+
     fam = dict(breakdown)
     if dominant in live:
         fam[dominant] = live[dominant]  # the timed region's own measurement
@@ -249,21 +300,7 @@ def main():
                     "algorithmic_bytes_per_launch": algo[dominant]}
     t_enc = sum(fam[k]["avg_ms"] for k in ("compress", "hist", "normalize", "encode", "coalesce") if k in fam)
     t_dec = fam.get("decode", {}).get("avg_ms", 0.0)
-    line = {
-        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "settle_ms": round(settle_ms, 1), "settle_steps": settle_steps,
-        "higher_is_better": True,
-        "scaling": "strong" if workload == "c5" else "weak", "vs_baseline": None, "dtype": "u32",
-        "data": "synthetic",
-        "distributed": distributed,
-        "config": {"workload": (f"c5: batch={total} x {n * 2 // 1048576} MiB bf16 N(0,1) in total, "
-                                f"{nb} per GPU" if workload == "c5" else
-                                f"c2: batch={nb} x {n * 2 // 1048576} MiB bf16 N(0,1) per GPU"),
-                   "batch_per_gpu": nb, "words_per_tensor": n, "prob_bits": pb,
-                   "api": "floatCompress + floatDecompress (pointer API, C ABI)",
-                   "parallelism": f"dp{world} (independent shards + RCCL size all-gather)"},
-        "ratio": round(comp_total / (total * n * 2), 5),
+    line.update({
         "encode_plus_decode_algorithmic_GBps": (round(2 * (U + comp_bytes) / ((t_enc + t_dec) * 1e-3) / 1e9, 1)
                                                 if t_enc and t_dec else None),
         "compress_GBps_kernels": round(U / (t_enc * 1e-3) / 1e9, 1) if t_enc else None,
@@ -273,7 +310,7 @@ def main():
                         "others from a profiled pass outside it",
         "roofline": roofline,
         "cpu_baseline": None,
-    }
+    })
     if decode_cold:
         # the step with the decode reading its archives from HBM: the timed
         # step's own decode replaced by the isolated cold one
@@ -314,6 +351,57 @@ def _bf16_rows(first, last, n, dev, chunk=512):
         x[a - first:b - first] = rows.view(torch.bfloat16)
         del x32
     return x
+
+
+def _dump_outputs(dirname, rank, world, comp, sizes, out, ok, osz, sample=1 << 22, seed=1234):
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    as <dirname>/<name>.npy (float32, or float64 where a value can exceed
+    2^24), about 38 MB in all for the c2 batch:
+      compressed_sizes, decoded_sizes, decode_status   whole, one per tensor
+      archive_checksums, decoded_checksums   exact integer sums per tensor (of
+                        the archive's bytes / of the decoded words as int16)
+      archive_head      the first bytes of every archive (header, tables)
+      archive_sample, decoded_sample   `sample` elements of the archive matrix /
+                        of the decoded batch at fixed positions (CPU generator,
+                        `seed`), in ascending position order
+    Only the first compressed_sizes[i] bytes of archive row i are the
+    compressor's output; bytes past them count as 0 everywhere here.  Ranks
+    of a multi-GPU run write <name>.rank<r>.npy, each its own shard."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+    dev = comp.device
+    nb, cols = comp.shape
+    sz = sizes.to(torch.int64)
+    words = out.view(torch.int16)
+    g = torch.Generator().manual_seed(seed)
+
+    def save(name, t, dt):
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), t.cpu().numpy().astype(dt))
+
+    save("compressed_sizes", sz, np.float64)
+    save("decoded_sizes", osz, np.float64)
+    save("decode_status", ok, np.float32)
+    col = torch.arange(cols, device=dev)
+    asum = torch.empty([nb], dtype=torch.int64, device=dev)
+    wsum = torch.empty([nb], dtype=torch.int64, device=dev)
+    for a in range(0, nb, 32):  # row chunks: the masks stay small
+        b = min(nb, a + 32)
+        valid = col[None, :] < sz[a:b, None]
+        asum[a:b] = torch.where(valid, comp[a:b], 0).sum(dim=1, dtype=torch.int64)
+        wsum[a:b] = words[a:b].sum(dim=1, dtype=torch.int64)
+    save("archive_checksums", asum, np.float64)
+    save("decoded_checksums", wsum, np.float64)
+    h = min(cols, max(1, (1 << 20) // nb))
+    save("archive_head", comp[:, :h].to(torch.float32) * (col[None, :h] < sz[:, None]), np.float32)
+    idx = torch.randint(0, nb * cols, (min(sample, nb * cols),), generator=g).sort().values.to(dev)
+    v = comp.view(-1)[idx].to(torch.float32)
+    v[idx % cols >= sz[idx // cols]] = 0
+    save("archive_sample", v, np.float32)
+    idx = torch.randint(0, out.numel(), (min(sample, out.numel()),), generator=g).sort().values.to(dev)
+    save("decoded_sample", out.view(-1)[idx].to(torch.float32), np.float32)
 
 
 def _decode_cold_warm(step_parts, dev, reps=8, flush_bytes=512 << 20):

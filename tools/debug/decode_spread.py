@@ -3,11 +3,14 @@ decode time and k_decode<2>'s mean TCC hit / miss counts per launch."""
 import csv
 import glob
 import json
+import os
+
+OUT = os.environ.get("OUT_DIR", "bench_out")
 
 for i in range(1, 6):
-    line = next((json.loads(l) for l in open(f"gpurun_out/dsp_{i}.log") if l.startswith('{"metric"')), None)
+    line = next((json.loads(l) for l in open(f"{OUT}/dsp_{i}.log") if l.startswith('{"metric"')), None)
     hits, miss, n = 0.0, 0.0, 0
-    for f in glob.glob(f"gpurun_out/dsp/p{i}/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{OUT}/dsp/p{i}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             if "k_decode<2" not in r["Kernel_Name"]:
                 continue

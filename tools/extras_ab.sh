@@ -1,8 +1,11 @@
 #!/bin/bash
-# GPU box: the default bench (extras included) once per library, alternating;
-# prints every extra's compress / decompress ms side by side.
+# GPU box: the full bench (extras included) once per library, alternating;
+# prints every extra's compress / decompress ms side by side.  Logs go to
+# $OUT_DIR (default bench_out/).
 #   usage: PASSES=1 bash tools/extras_ab.sh default lib.so ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+export OUT=${OUT_DIR:-bench_out}
+mkdir -p "$OUT"
 LIB=dietgpu_fork_amd/_lib/libdietgpu_amd.so
 cp "$LIB" /tmp/xab_default.so
 trap 'cp /tmp/xab_default.so "$LIB"' EXIT
@@ -10,7 +13,7 @@ for p in $(seq 1 ${PASSES:-1}); do
   for L in "$@"; do
     T=$(basename "$L" .so)
     if [ "$L" = default ]; then cp /tmp/xab_default.so "$LIB"; else cp "$L" "$LIB"; fi
-    timeout -k 10 400 python3 -u bench.py --no-cpu-baseline --steps 20 > gpurun_out/xab_${T}_$p.json 2>/dev/null || { echo "$T FAILED"; exit 1; }
+    timeout -k 10 400 python3 -u bench.py --full --no-cpu-baseline --steps 20 > "$OUT/xab_${T}_$p.json" 2>/dev/null || { echo "$T FAILED"; exit 1; }
   done
 done
 python3 - "$@" <<'PY'
@@ -18,7 +21,7 @@ import json, sys, glob, os
 libs = [os.path.basename(a).replace('.so', '') for a in sys.argv[1:]]
 rows = {}
 for t in libs:
-    for f in sorted(glob.glob(f"gpurun_out/xab_{t}_*.json")):
+    for f in sorted(glob.glob(os.path.join(os.environ["OUT"], f"xab_{t}_*.json"))):
         d = json.loads(open(f).read().splitlines()[-1])
         rows.setdefault("c2 step", {}).setdefault(t, []).append(d["ms_per_step"])
         for e in d["extras"]:

@@ -11,6 +11,6 @@ tail -3 gpurun_out/t_$TAG.log
 bash tools/profile_gpu.sh ${TAG}_driver_cmd --gpus 1 --steps 20 --warmup 5 || exit 1
 grep '^{"metric"' gpurun_out/prof_${TAG}_driver_cmd/trace.log | python3 -c "
 import json,sys
-d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernels'], d['roofline']['frac'])"
+d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['ratio'])"
 [ -n "$NO_EXTRAS" ] || bash tools/pmc_extras.sh ${TAG}_extras || exit 1
 echo final done

@@ -2,7 +2,7 @@
 # GPU box: VERDICT r5 #8 -- the exact multi-GPU step (RCCL process group, the
 # size all-gather inside every timed step, barriers, max over ranks) run once
 # on one GPU through torch.distributed.run, on BASELINE's c5 batch (8192 x 1
-# MiB bf16); compare with the c5-at-G=1 extra of the default bench.
+# MiB bf16); compare with the c5-at-G=1 extra of `bench.py --full`.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \

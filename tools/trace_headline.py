@@ -1,7 +1,8 @@
 """Per-kernel duration stats of the HEADLINE phase of a profiled bench.py run:
 the dispatches before the first k_hist dispatch (the c3 extra's first
-kernel: the bench runs its c2 warm-up, settle, timed region, profiled pass
-and cold-decode measurement first, then the CPU baseline, then the extras).
+kernel: with --full the bench runs its c2 warm-up, settle, timed region,
+profiled pass and cold-decode measurement first, then the CPU baseline, then
+the extras; a plain run has no k_hist dispatch and counts whole).
 The whole-run rocprofv3 --stats summary averages k_pcompress<2,..> over the
 extras too (small batches, c5 at G = 1, benchmark.py's shapes: the same
 kernel instance at other sizes), so this is the summary that compares with

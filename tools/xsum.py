@@ -1,5 +1,5 @@
-"""Dev tool: compact table of a bench.py JSON line's extras (compress /
-decompress ms, per-kernel ms), optionally against a second line.
+"""Dev tool: compact table of a `bench.py --full` JSON line's extras (compress
+/ decompress ms, per-kernel ms), optionally against a second line.
     usage: python tools/xsum.py new.json [old.json]"""
 import json
 import sys
