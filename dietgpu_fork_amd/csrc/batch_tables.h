@@ -1,0 +1,167 @@
+// Per-call parameter tables of a batch (the reference's BatchProvider pointer /
+// size arrays), built on the host by every pointer and split-size entry point
+// of the dense and sparse codecs.  Host code only.
+//
+// Small tables (allowInline, <= 8 KB) ride in the InlineTable kernel argument
+// of k_pcompress / k_decode: the BatchDesc fields then hold byte offsets into
+// it (biased by 8, so none is 0) and BatchDesc::inl says which.  Any other
+// kernel gets a device copy made in its driver's scope (DeviceDescs).  Larger
+// tables, or callers that need device pointers, get one upload here.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+#include <initializer_list>
+#include <memory>
+#include <type_traits>
+#include <vector>
+
+#include "batch.h"
+#include "common.h"
+#include "dietgpu/StackDeviceMemory.h"
+
+namespace dietgpu {
+
+struct DeviceTables {
+  GpuMemoryReservation<uint8_t> mem;
+  std::vector<uint8_t> host;
+  std::unique_ptr<InlineTable> image;  // kernarg image when inline
+  bool inl = false;
+  std::vector<const uint64_t*> u64;  // the u64 columns, in the order given
+  const uint32_t* u32 = nullptr;     // the u32 column that follows them
+
+  // mark the table-backed fields of a descriptor built from u64 / u32
+  BatchDesc tag(BatchDesc d) const {
+    if (!inl) return d;
+    if (d.ptrs) d.inl |= BatchDesc::kInlPtrs;
+    if (d.sizes) d.inl |= BatchDesc::kInlSizes;
+    if (d.offsets) d.inl |= BatchDesc::kInlOffsets;
+    return d;
+  }
+};
+constexpr size_t kInlineBias = 8;
+
+inline const InlineTable& kernargTable(const DeviceTables* t) {
+  static const InlineTable kEmpty{};
+  return t && t->inl ? *t->image : kEmpty;
+}
+
+// One table of the u64 columns `cols` followed by the u32 column `last`
+// (either may be empty).
+inline DeviceTables uploadTables(StackDeviceMemory& res, hipStream_t s,
+                                 std::initializer_list<const std::vector<uint64_t>*> cols,
+                                 const std::vector<uint32_t>& last, bool allowInline = false) {
+  DeviceTables t;
+  size_t bytes = last.size() * 4;
+  for (const auto* c : cols) bytes += c->size() * 8;
+  t.host.resize(bytes);
+  size_t off = 0;  // column offsets now, addresses once the base is known
+  for (const auto* c : cols) {
+    t.u64.push_back(reinterpret_cast<const uint64_t*>(off));
+    if (!c->empty()) std::memcpy(t.host.data() + off, c->data(), c->size() * 8);
+    off += c->size() * 8;
+  }
+  if (!last.empty()) std::memcpy(t.host.data() + off, last.data(), last.size() * 4);
+  t.inl = allowInline && kInlineBias + bytes <= sizeof(InlineTable);
+  uintptr_t base;
+  if (t.inl) {
+    t.image.reset(new InlineTable());
+    std::memcpy(reinterpret_cast<uint8_t*>(t.image->w) + kInlineBias, t.host.data(), bytes);
+    base = kInlineBias;
+  } else {
+    t.mem = res.alloc<uint8_t>(s, std::max<size_t>(bytes, 1));
+    StackDeviceMemory::copyToDevice(t.mem.data(), t.host.data(), bytes, s);
+    base = reinterpret_cast<uintptr_t>(t.mem.data());
+  }
+  for (auto& p : t.u64) p = reinterpret_cast<const uint64_t*>(base + reinterpret_cast<uintptr_t>(p));
+  t.u32 = reinterpret_cast<const uint32_t*>(base + off);
+  return t;
+}
+
+// The addresses of a host array of nb pointers, as a table column.
+template <typename P>
+std::vector<uint64_t> addressColumn(P* const* p, uint32_t nb) {
+  std::vector<uint64_t> v(nb);
+  for (uint32_t i = 0; i < nb; ++i) v[i] = reinterpret_cast<uint64_t>(p[i]);
+  return v;
+}
+
+inline bool allAligned16(const std::vector<uint64_t>& addrs) {
+  for (uint64_t a : addrs)
+    if (a % 16) return false;
+  return true;
+}
+
+// A u32 column (sizes or capacities) and its largest entry.
+struct SizeColumn {
+  std::vector<uint32_t> sizes;
+  uint32_t maxSize = 0;
+  SizeColumn(const uint32_t* v, uint32_t nb) : sizes(v, v + nb) {
+    for (uint32_t x : sizes) maxSize = std::max(maxSize, x);
+  }
+};
+
+// The columns of a split-size batch: element i starts `unitBytes` x (the sum
+// of the earlier sizes) bytes into the base buffer.  aligned16: every offset
+// is a multiple of 16.
+struct SplitColumns : SizeColumn {
+  std::vector<uint64_t> offsets;
+  bool aligned16 = true;
+  SplitColumns(const uint32_t* v, uint32_t nb, uint32_t unitBytes) : SizeColumn(v, nb), offsets(nb) {
+    uint64_t run = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+      offsets[i] = run * unitBytes;
+      run += sizes[i];
+    }
+    aligned16 = allAligned16(offsets);
+  }
+};
+
+// Device copy of inline tables for kernels without an InlineTable argument,
+// allocated in the calling driver's scope (the arena is LIFO) and only when
+// the tables are inline.  A one-element batch needs no copy at all: its
+// descriptors become stride descriptors of that element (its address, and
+// its size as the fixed size), so the three-kernel path of a batch-1
+// pointer / split-size call launches no upload kernel (fp64 1 x 16M words
+// and the float_benchmark's batch-1 grid: a 4.7 us k_table launch before
+// k_hist).
+struct DeviceDescs {
+  GpuMemoryReservation<uint8_t> mem;
+  uintptr_t base = 0;
+  const InlineTable* single = nullptr;  // nb == 1: entries read from the kernarg image
+  DeviceDescs(StackDeviceMemory& res, hipStream_t s, const DeviceTables* t, uint32_t nb) {
+    if (!t || !t->inl) return;
+    if (nb == 1) {
+      single = t->image.get();
+      return;
+    }
+    mem = res.alloc<uint8_t>(s, std::max<size_t>(t->host.size(), 1));
+    StackDeviceMemory::copyToDevice(mem.data(), t->host.data(), t->host.size(), s);
+    base = reinterpret_cast<uintptr_t>(mem.data()) - kInlineBias;
+  }
+  BatchDesc map(BatchDesc d) const {
+    if (!d.inl) return d;
+    if (single) {
+      auto entry = [&](auto p) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(p)>>;
+        T v;
+        std::memcpy(&v, reinterpret_cast<const uint8_t*>(single->w) + reinterpret_cast<uintptr_t>(p), sizeof(T));
+        return v;
+      };
+      uint8_t* start = d.mode == BatchDesc::kPointer ? reinterpret_cast<uint8_t*>(entry(d.ptrs))
+                       : d.mode == BatchDesc::kSplit ? d.base + entry(d.offsets)
+                                                     : d.base;
+      DG_CHECK(!d.sizes || (d.inl & BatchDesc::kInlSizes), "mixed inline / device size table");
+      const uint32_t size = d.sizes ? entry(d.sizes) : d.fixedSize;
+      return BatchDesc::strided(start, 0, size);
+    }
+    auto rebase = [&](auto p) { return reinterpret_cast<decltype(p)>(base + reinterpret_cast<uintptr_t>(p)); };
+    if (d.inl & BatchDesc::kInlPtrs) d.ptrs = rebase(d.ptrs);
+    if (d.inl & BatchDesc::kInlSizes) d.sizes = rebase(d.sizes);
+    if (d.inl & BatchDesc::kInlOffsets) d.offsets = rebase(d.offsets);
+    d.inl = 0;
+    return d;
+  }
+};
+
+}  // namespace dietgpu

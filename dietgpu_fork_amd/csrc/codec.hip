@@ -6,14 +6,14 @@
 //
 // Launch sequence per call (all stream-ordered, no host sync unless a
 // checksum has to be verified):
-//   compress:   k_hist -> k_normalize -> k_encode (+ k_coalesce for fp64)
+//   compress:   k_pcompress (single pass, compressPersistent) when
+//               encodeBatchDevice's rule prefers it, else
+//               k_hist -> k_normalize -> k_encode (+ k_coalesce for fp64)
+//               (compressThreeKernel)
 //   decompress: k_decode (table build + rANS decode + float join fused)
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <sstream>
 #include <tuple>
 #include <type_traits>
@@ -30,8 +30,6 @@
 namespace dietgpu {
 
 namespace {
-constexpr uint32_t kMaxGridY = 65535;
-
 // k_hist chunk (words): 4 K .. 64 K words, halved while the batch has fewer
 // than 2,048 chunks -- for single-segment formats only down to 16 K words
 // once there are 512: a k_hist workgroup zeroes and sums 32 KB of LDS
@@ -51,36 +49,22 @@ uint32_t histChunkWords(uint32_t nb, uint32_t maxSize, int segs) {
 }
 
 // workgroups of `kernel` resident on the whole device at once (cached per
-// device, kernel and LDS size: the queries cost host time on every call)
+// device, kernel and LDS size)
 uint32_t residentSlots(const void* kernel, int threads, uint32_t dynLds) {
-  static std::mutex m;
-  static std::map<std::tuple<int, const void*, int, uint32_t>, uint32_t> cache;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  const auto key = std::make_tuple(dev, kernel, threads, dynLds);
-  std::lock_guard<std::mutex> g(m);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int cus = 0, perCU = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, dynLds));
-  const uint32_t v = uint32_t(std::max(1, cus) * std::max(1, perCU));
-  cache[key] = v;
-  return v;
+  return cachedPerDevice<uint32_t>(std::make_tuple(kernel, threads, dynLds), [&](int dev) {
+    int cus = 0, perCU = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, dynLds));
+    return uint32_t(std::max(1, cus) * std::max(1, perCU));
+  });
 }
 
 uint32_t residentCUs() {
-  static std::mutex m;
-  static std::map<int, uint32_t> cache;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> g(m);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int cus = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  cache[dev] = uint32_t(std::max(1, cus));
-  return cache[dev];
+  return cachedPerDevice<uint32_t>(0, [](int dev) {
+    int cus = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return uint32_t(std::max(1, cus));
+  });
 }
 
 void checkProbBits(int pb) {
@@ -88,113 +72,6 @@ void checkProbBits(int pb) {
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------------------
-// parameter tables (the reference's BatchProvider pointer / size arrays)
-// ---------------------------------------------------------------------------
-// Small tables (allowInline, <= 8 KB) ride in the InlineTable kernel argument
-// of k_pcompress / k_decode: the BatchDesc fields then hold byte offsets into
-// it (biased by 8, so none is 0) and BatchDesc::inl says which.  Any other
-// kernel gets a device copy made in its driver's scope (DeviceDescs).  Larger
-// tables, or callers that need device pointers, get one upload here.
-struct DeviceTables {
-  GpuMemoryReservation<uint8_t> mem;
-  std::vector<uint8_t> host;
-  std::unique_ptr<InlineTable> image;  // kernarg image when inline
-  bool inl = false;
-  const uint64_t* u64a = nullptr;
-  const uint64_t* u64b = nullptr;
-  const uint32_t* u32a = nullptr;
-
-  // mark the table-backed fields of a descriptor built from u64a/u64b/u32a
-  BatchDesc tag(BatchDesc d) const {
-    if (!inl) return d;
-    if (d.ptrs) d.inl |= BatchDesc::kInlPtrs;
-    if (d.sizes) d.inl |= BatchDesc::kInlSizes;
-    if (d.offsets) d.inl |= BatchDesc::kInlOffsets;
-    return d;
-  }
-};
-constexpr size_t kInlineBias = 8;
-
-const InlineTable& kernargTable(const DeviceTables* t) {
-  static const InlineTable kEmpty{};
-  return t && t->inl ? *t->image : kEmpty;
-}
-
-DeviceTables uploadTables(StackDeviceMemory& res, hipStream_t s, uint32_t nb,
-                          const std::vector<uint64_t>& a, const std::vector<uint64_t>& b,
-                          const std::vector<uint32_t>& c, bool allowInline = false) {
-  const size_t bytesA = a.size() * 8, bytesB = b.size() * 8, bytesC = c.size() * 4;
-  DeviceTables t;
-  t.host.resize(bytesA + bytesB + bytesC);
-  if (bytesA) std::memcpy(t.host.data(), a.data(), bytesA);
-  if (bytesB) std::memcpy(t.host.data() + bytesA, b.data(), bytesB);
-  if (bytesC) std::memcpy(t.host.data() + bytesA + bytesB, c.data(), bytesC);
-  t.inl = allowInline && kInlineBias + t.host.size() <= sizeof(InlineTable);
-  uintptr_t base;
-  if (t.inl) {
-    t.image.reset(new InlineTable());
-    std::memcpy(reinterpret_cast<uint8_t*>(t.image->w) + kInlineBias, t.host.data(), t.host.size());
-    base = kInlineBias;
-  } else {
-    t.mem = res.alloc<uint8_t>(s, std::max<size_t>(t.host.size(), 1));
-    StackDeviceMemory::copyToDevice(t.mem.data(), t.host.data(), t.host.size(), s);
-    base = reinterpret_cast<uintptr_t>(t.mem.data());
-  }
-  t.u64a = reinterpret_cast<const uint64_t*>(base);
-  t.u64b = reinterpret_cast<const uint64_t*>(base + bytesA);
-  t.u32a = reinterpret_cast<const uint32_t*>(base + bytesA + bytesB);
-  (void)nb;
-  return t;
-}
-
-// Device copy of inline tables for kernels without an InlineTable argument,
-// allocated in the calling driver's scope (the arena is LIFO) and only when
-// the tables are inline.  A one-element batch needs no copy at all: its
-// descriptors become stride descriptors of that element (its address, and
-// its size as the fixed size), so the three-kernel path of a batch-1
-// pointer / split-size call launches no upload kernel (fp64 1 x 16M words
-// and the float_benchmark's batch-1 grid: a 4.7 us k_table launch before
-// k_hist).
-struct DeviceDescs {
-  GpuMemoryReservation<uint8_t> mem;
-  uintptr_t base = 0;
-  const InlineTable* single = nullptr;  // nb == 1: entries read from the kernarg image
-  DeviceDescs(StackDeviceMemory& res, hipStream_t s, const DeviceTables* t, uint32_t nb) {
-    if (!t || !t->inl) return;
-    if (nb == 1) {
-      single = t->image.get();
-      return;
-    }
-    mem = res.alloc<uint8_t>(s, std::max<size_t>(t->host.size(), 1));
-    StackDeviceMemory::copyToDevice(mem.data(), t->host.data(), t->host.size(), s);
-    base = reinterpret_cast<uintptr_t>(mem.data()) - kInlineBias;
-  }
-  BatchDesc map(BatchDesc d) const {
-    if (!d.inl) return d;
-    if (single) {
-      auto entry = [&](auto p) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(p)>>;
-        T v;
-        std::memcpy(&v, reinterpret_cast<const uint8_t*>(single->w) + reinterpret_cast<uintptr_t>(p), sizeof(T));
-        return v;
-      };
-      uint8_t* start = d.mode == BatchDesc::kPointer ? reinterpret_cast<uint8_t*>(entry(d.ptrs))
-                       : d.mode == BatchDesc::kSplit ? d.base + entry(d.offsets)
-                                                     : d.base;
-      DG_CHECK(!d.sizes || (d.inl & BatchDesc::kInlSizes), "mixed inline / device size table");
-      const uint32_t size = d.sizes ? entry(d.sizes) : d.fixedSize;
-      return BatchDesc::strided(start, 0, size);
-    }
-    auto rebase = [&](auto p) { return reinterpret_cast<decltype(p)>(base + reinterpret_cast<uintptr_t>(p)); };
-    if (d.inl & BatchDesc::kInlPtrs) d.ptrs = rebase(d.ptrs);
-    if (d.inl & BatchDesc::kInlSizes) d.sizes = rebase(d.sizes);
-    if (d.inl & BatchDesc::kInlOffsets) d.offsets = rebase(d.offsets);
-    d.inl = 0;
-    return d;
-  }
-};
 
 // ---------------------------------------------------------------------------
 // generic drivers
@@ -206,17 +83,11 @@ struct DeviceDescs {
 __device__ uint32_t g_dgErrors[2];
 
 uint32_t* deviceErrorWord() {
-  static std::mutex m;
-  static std::map<int, uint32_t*> addr;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> g(m);
-  auto it = addr.find(dev);
-  if (it != addr.end()) return it->second;
-  void* p = nullptr;
-  HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_dgErrors)));
-  addr[dev] = static_cast<uint32_t*>(p);
-  return static_cast<uint32_t*>(p);
+  return cachedPerDevice<uint32_t*>(0, [](int) {
+    void* p = nullptr;
+    HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_dgErrors)));
+    return static_cast<uint32_t*>(p);
+  });
 }
 
 static uint32_t readErrorWord(uint32_t k, bool reset) {
@@ -230,6 +101,18 @@ static uint32_t readErrorWord(uint32_t k, bool reset) {
 
 uint32_t deviceErrorCount(bool reset) { return readErrorWord(0, reset); }
 uint32_t barrierFallbackCount(bool reset) { return readErrorWord(1, reset); }
+
+// One slice (elements y0 .. y0 + ny) of the XOR checksums of the first
+// in.size(b) bytes of each element, into ck (zeroed by the caller).  The
+// float codecs pass word counts: the reference checksums float-word counts
+// as byte counts (float/GpuFloatCompress.cuh:709).
+static void launchChecksum(const BatchDesc& in, uint32_t y0, uint32_t ny, uint32_t maxSize, uint32_t* ck,
+                           hipStream_t s) {
+  const uint32_t ckChunk = 1u << 20;
+  dim3 g(std::max(1u, divUp(maxSize, ckChunk)), ny);
+  k_checksum<<<g, kThreads, 0, s>>>(in, y0, 1, ckChunk, ck);
+  HIP_LAUNCH_CHECK();
+}
 
 // Single-pass compression (k_pcompress, pcompress.h) for single-segment
 // formats without a caller-supplied histogram, elements of at most
@@ -297,11 +180,12 @@ void launchPersistent(uint32_t grid, hipStream_t s, const DeviceTables* tabs, co
 }
 
 template <int FT, bool kCk>
-bool compressPersistent(StackDeviceMemory& res, int pb, bool useChecksum, uint32_t nb,
-                        const BatchDesc& in, uint32_t maxSize, const BatchDesc& out,
-                        uint32_t* outSize_dev, hipStream_t s, const DeviceTables* tabs,
-                        const uint32_t* sparseN) {
-  const PersistentPlan plan = planPersistent<FT>(nb, maxSize);
+bool compressPersistent(const CompressCall& c) {
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const uint32_t nb = c.nb;
+  const bool floatCk = FT != 0 && c.useChecksum;
+  const PersistentPlan plan = planPersistent<FT>(nb, c.maxSize);
   const uint32_t team = plan.team;
   if (team == 0) return false;
   const uint64_t items64 = uint64_t(team) * nb;
@@ -311,8 +195,8 @@ bool compressPersistent(StackDeviceMemory& res, int pb, bool useChecksum, uint32
   const uint32_t grid = plan.teamsPerRound * team;
 
   auto slotMem = res.alloc<uint8_t>(s, size_t(grid) * pc::kBlocksPerItem * kSlotDataBytes);
-  auto ck = res.alloc<uint32_t>(s, FT != 0 && useChecksum ? nb : 1);
-  DeviceDescs dd(res, s, FT != 0 && useChecksum ? tabs : nullptr, nb);  // k_checksum's view
+  auto ck = res.alloc<uint32_t>(s, floatCk ? nb : 1);
+  DeviceDescs dd(res, s, floatCk ? c.tabs : nullptr, nb);  // k_checksum's view
   // epoch-tagged state in this stream's persistent arena (no per-call
   // zeroing), one region per kind of word: the dequeue counters (at a fixed
   // place: a call zeroes the next call's), the look-back flags, the tagged
@@ -326,17 +210,9 @@ bool compressPersistent(StackDeviceMemory& res, int pb, bool useChecksum, uint32
   const size_t regions[kSyncRegions] = {16, size_t(items) * 8, partBytes + (kCk ? size_t(items) * 4 : 0),
                                         size_t(teams) * maxR * 8, 0};
   SyncLease lease(res, s, regions, /*dequeue=*/true);
-  if (FT != 0 && useChecksum) {
+  if (floatCk) {
     zeroAsync(ck.data(), sizeof(uint32_t) * nb, s);
-    // float checksum: the reference passes float-word counts as byte counts
-    // (float/GpuFloatCompress.cuh:709)
-    const uint32_t ckChunk = 1u << 20;
-    for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-      const uint32_t ny = std::min(kMaxGridY, nb - y0);
-      dim3 g(std::max(1u, divUp(maxSize, ckChunk)), ny);
-      k_checksum<<<g, kThreads, 0, s>>>(dd.map(in), y0, 1, ckChunk, ck.data());
-      HIP_LAUNCH_CHECK();
-    }
+    forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) { launchChecksum(dd.map(c.in), y0, ny, c.maxSize, ck.data(), s); });
   }
   PCompArgs a;
   a.ctr = static_cast<uint64_t*>(lease.base[kSyncCounters]);
@@ -348,9 +224,9 @@ bool compressPersistent(StackDeviceMemory& res, int pb, bool useChecksum, uint32
   a.slotSpan = std::max(1u, residentCUs());
   a.err = deviceErrorWord();
   a.slots = slotMem.data();
-  a.ckIn = FT != 0 && useChecksum ? ck.data() : nullptr;
-  a.outSize = outSize_dev;
-  a.sparseN = sparseN;
+  a.ckIn = floatCk ? ck.data() : nullptr;
+  a.outSize = c.outSize_dev;
+  a.sparseN = c.sparseN;
   a.items = items;
   a.team = team;
   a.nb = nb;
@@ -358,28 +234,28 @@ bool compressPersistent(StackDeviceMemory& res, int pb, bool useChecksum, uint32
   a.epoch = lease.epoch;
   a.spinCap = spinCap();
   a.fallbackTicks = barrierBudgetTicks();
-  a.pb = pb;
-  a.useChecksum = useChecksum;
+  a.pb = c.pb;
+  a.useChecksum = c.useChecksum;
   prof::Scope p("compress", s);
-  if (xcdTeams) launchPersistent<FT, kCk, true>(grid, s, tabs, in, out, a);
-  else launchPersistent<FT, kCk, false>(grid, s, tabs, in, out, a);
+  if (xcdTeams) launchPersistent<FT, kCk, true>(grid, s, c.tabs, c.in, c.out, a);
+  else launchPersistent<FT, kCk, false>(grid, s, c.tabs, c.in, c.out, a);
   return true;
 }
 
-// inAligned16: every element's input starts 16 B-aligned (the single-pass
-// compressor reads whole 16 B vectors; anything else takes three kernels)
+// The three-kernel path: k_hist -> (k_histReduce / k_normalize) -> k_encode
+// (+ k_coalesce for fp64), on plain device tables.
 template <int FT>
-void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_t nb,
-                       const BatchDesc& inArg, uint32_t maxSize, const uint32_t* hist_dev,
-                       const BatchDesc& outArg, uint32_t* outSize_dev, hipStream_t s,
-                       const DeviceTables* tabs, bool inAligned16, const PartialHist* pre = nullptr,
-                       const uint32_t* sparseN = nullptr) {
-  checkProbBits(pb);
-  if (nb == 0) return;
+void compressThreeKernel(const CompressCall& c) {
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const uint32_t nb = c.nb, maxSize = c.maxSize;
+  const int pb = c.pb;
+  const bool useChecksum = c.useChecksum;
+  const PartialHist* const pre = c.pre;
   constexpr int kSegs = FloatTraits<FT>::kSegs;
   constexpr bool kFused = kSegs == 1;  // k_encode writes the archive itself
   const uint32_t MB = divUp(maxSize, kBlockSize);
-  const bool userHist = FT == 0 && hist_dev != nullptr;
+  const bool userHist = FT == 0 && c.hist_dev != nullptr;
   const bool preHist = FT != 0 && pre != nullptr;  // partial rows counted by the caller
   const bool preNorm = preHist && pre->table != nullptr;  // ... and normalised
   const uint32_t chunkWords = histChunkWords(nb, maxSize, kSegs);
@@ -387,20 +263,8 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
   const bool runHist = !preHist && (!userHist || useChecksum);
   const bool rawCk = FT == 0 && useChecksum;
   const uint32_t nW = std::max(1u, divUp(MB, EncCfg<FT>::kBlocksPerWG));
-  if constexpr (kFused) {
-    // (byte archives with a checksum stay single-pass: the three-kernel path
-    // has no prologue normalisation for them)
-    if (!userHist && inAligned16 && ((rawCk && compressPath() != 2) || persistentPreferred<FT>(nb, maxSize))) {
-      const bool done = rawCk ? compressPersistent<FT, FT == 0>(res, pb, useChecksum, nb, inArg,
-                                                                 maxSize, outArg, outSize_dev, s, tabs, sparseN)
-                              : compressPersistent<FT, false>(res, pb, useChecksum, nb, inArg, maxSize,
-                                                              outArg, outSize_dev, s, tabs, sparseN);
-      if (done) return;
-    }
-  }
-  // three-kernel path: plain device tables
-  DeviceDescs dd(res, s, tabs, nb);
-  const BatchDesc in = dd.map(inArg), out = dd.map(outArg);
+  DeviceDescs dd(res, s, c.tabs, nb);
+  const BatchDesc in = dd.map(c.in), out = dd.map(c.out);
 
   // Prologue normalisation (k_encode<.., kPro>, encode.h proNormalize):
   // when the encode grid is at most two generations of resident workgroups,
@@ -437,7 +301,6 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
   // workgroups pays a wait for its rows' write-through stores and a counter
   // round trip: with many (c3's k_hist: 65,536) that costs more than the
   // launch (c3 hist 0.74 -> 1.09 ms), so k_normalize runs there.
-  const bool finalInReduce = reduce2;
   const bool finalInHist = !reduce2 && !pro && runHist && uint64_t(chunks) * nb <= 4096;
   // k_encode's look-back flags (one per segment, element and encode
   // workgroup, epoch-tagged, never zeroed; fp64's end as the prefixes
@@ -456,7 +319,7 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
                                                                 : nullptr;
   NormArgs na;
   na.in = in;
-  na.hist = userHist ? hist_dev : (reduce2 ? groupHist.data() : chunkRows);
+  na.hist = userHist ? c.hist_dev : (reduce2 ? groupHist.data() : chunkRows);
   na.rows = userHist ? 1u : (reduce2 ? groups : chunks);
   na.pb = pb;
   na.table = tableMem.data();
@@ -471,17 +334,8 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
   if (FT != 0 && useChecksum) {
     zeroAsync(ck.data(), sizeof(uint32_t) * nb, s);
   }
-  // launch groups: histogram -> (normalise) -> encode per group of elements
-  // (kMallSliceBytes > 0: groups of about that many input bytes, so that the
-  // encoder re-reads its input from the 256 MiB Infinity Cache; 0: one group
-  // up to the grid limit)
-  constexpr size_t kMallSliceBytes = 0;
-  uint32_t slice = kMaxGridY;
-  if (kMallSliceBytes && runHist && !pro)
-    slice = uint32_t(std::max<size_t>(1, std::min<size_t>(kMaxGridY, kMallSliceBytes / std::max<size_t>(
-                                                                            1, size_t(maxSize) * sizeof(typename FloatTraits<FT>::WordT)))));
-  for (uint32_t y0 = 0; y0 < nb; y0 += slice) {
-    const uint32_t ny = std::min(slice, nb - y0);
+  // histogram -> (normalise) -> encode per slice of elements
+  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
     if (runHist) {
       prof::Scope p("hist", s);
       dim3 g(chunks, ny);
@@ -499,23 +353,15 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
       }
       HIP_LAUNCH_CHECK();
     }
-    if (FT != 0 && useChecksum) {
-      // float checksum: the reference passes float-word counts as byte counts
-      // (float/GpuFloatCompress.cuh:709)
-      const uint32_t ckChunk = 1u << 20;
-      dim3 g(std::max(1u, divUp(maxSize, ckChunk)), ny);
-      k_checksum<<<g, kThreads, 0, s>>>(in, y0, 1, ckChunk, ck.data());
-      HIP_LAUNCH_CHECK();
-    }
+    if (FT != 0 && useChecksum) launchChecksum(in, y0, ny, maxSize, ck.data(), s);
     if (reduce2) {
       prof::Scope p("normalize", s);
       dim3 g(groups, ny, kSegs);
       k_histReduce<<<g, kThreads, 0, s>>>(y0, nb, chunks, groups, chunkRows, rawCk ? partCk.data() : nullptr,
-                                          groupHist.data(), rawCk ? groupCk.data() : nullptr,
-                                          finalInReduce ? naFinal : na, kSegs);
+                                          groupHist.data(), rawCk ? groupCk.data() : nullptr, naFinal, kSegs);
       HIP_LAUNCH_CHECK();
     }
-    if (!finalInReduce && !finalInHist && !preNorm && !pro) {
+    if (!reduce2 && !finalInHist && !preNorm && !pro) {
       prof::Scope p("normalize", s);
       dim3 g(ny, kSegs);
       k_normalize<<<g, kThreads, 0, s>>>(na, y0, nb);
@@ -524,8 +370,8 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
     if (MB > 0 || kFused) {
       prof::Scope p("encode", s);
       dim3 g(nW, ny);
-      EncTail tail{pdf, ck.data(), outSize_dev, flagsFor, nW, pb, useChecksum, spinCap(), deviceErrorWord(),
-                   sparseN};
+      EncTail tail{pdf, ck.data(), c.outSize_dev, flagsFor, nW, pb, useChecksum, spinCap(), deviceErrorWord(),
+                   c.sparseN};
       tail.epoch = lease.epoch;
       tail.skew = dispatchSkew();
       if (pro) {
@@ -555,26 +401,41 @@ void encodeBatchDevice(StackDeviceMemory& res, int pb, bool useChecksum, uint32_
       cp.err = deviceErrorWord();
       k_coalesce<FT><<<g, kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), bpw, slots.data(),
                                             cw.data(), pdf, pb, useChecksum, ck.data(),
-                                            outSize_dev, sparseN, cp);
+                                            c.outSize_dev, c.sparseN, cp);
       HIP_LAUNCH_CHECK();
     }
-  }
+  });
 }
 
 template <int FT>
-void decodeBatchDevice(StackDeviceMemory& res, int pb, uint32_t nb, const BatchDesc& in,
-                       const BatchDesc& out, uint32_t maxCapacity, uint8_t* outSuccess_dev,
-                       uint32_t* outSize_dev, hipStream_t s, const DeviceTables* tabs = nullptr,
-                       bool streamOut = true, bool capacityOnly = false) {
-  checkProbBits(pb);
-  if (nb == 0) return;
-  const uint32_t maxBlocks = divUp(maxCapacity, kBlockSize);
+void encodeBatchDevice(const CompressCall& c) {
+  checkProbBits(c.pb);
+  if (c.nb == 0) return;
+  if constexpr (FloatTraits<FT>::kSegs == 1) {
+    const bool userHist = FT == 0 && c.hist_dev != nullptr;
+    const bool rawCk = FT == 0 && c.useChecksum;
+    // (byte archives with a checksum stay single-pass: the three-kernel path
+    // has no prologue normalisation for them)
+    if (!userHist && c.inAligned16 &&
+        ((rawCk && compressPath() != 2) || persistentPreferred<FT>(c.nb, c.maxSize))) {
+      if (rawCk ? compressPersistent<FT, FT == 0>(c) : compressPersistent<FT, false>(c)) return;
+    }
+  }
+  compressThreeKernel<FT>(c);
+}
+
+template <int FT>
+void decodeBatchDevice(const DecodeCall& c) {
+  checkProbBits(c.pb);
+  if (c.nb == 0) return;
+  const hipStream_t s = c.s;
+  const int pb = c.pb;
+  const uint32_t maxBlocks = divUp(c.maxCapacity, kBlockSize);
   auto launch = [&](auto kTag, auto ntTag) {
     constexpr int KK = decltype(kTag)::value;
     constexpr bool NT = decltype(ntTag)::value;
     using Cfg = DecCfg<FT, KK>;
-    for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-      const uint32_t ny = std::min(kMaxGridY, nb - y0);
+    forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
       prof::Scope p("decode", s);
       // about one generation of resident workgroups; each decodes P chunks
       // (one table build per P chunks).  P is capped at kMaxDecodeChunks:
@@ -591,7 +452,7 @@ void decodeBatchDevice(StackDeviceMemory& res, int pb, uint32_t nb, const BatchD
       // workgroup, so the chunks that exist run side by side instead of P
       // passes of a workgroup while the grid's upper part exits at once
       // (5 x 15M fp32 at 50 % zeros: the list decode 77 -> see DESIGN)
-      const uint32_t P = capacityOnly ? 1u
+      const uint32_t P = c.capacityOnly ? 1u
                                       : std::min(kMaxDecodeChunks,
                                                  std::max(1u, uint32_t((uint64_t(chunks) * ny + slots / 2) / slots)));
       dim3 g(divUp(chunks, P), ny);
@@ -600,43 +461,36 @@ void decodeBatchDevice(StackDeviceMemory& res, int pb, uint32_t nb, const BatchD
       // (c3 decode 2.02 ms without, 2.32 ms with, same-box A/B).  A template
       // parameter: a runtime flag changed the step loop's code (c2 +25 %)
       if (uint64_t(g.x) * ny <= slots)
-        k_decode<FT, KK, NT, true><<<g, dec::kThreads, lds, s>>>(kernargTable(tabs), in, out, y0, pb, P,
-                                                                 outSuccess_dev, outSize_dev);
+        k_decode<FT, KK, NT, true><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
+                                                                 c.outSuccess_dev, c.outSize_dev);
       else
-        k_decode<FT, KK, NT, false><<<g, dec::kThreads, lds, s>>>(kernargTable(tabs), in, out, y0, pb, P,
-                                                                  outSuccess_dev, outSize_dev);
+        k_decode<FT, KK, NT, false><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
+                                                                  c.outSuccess_dev, c.outSize_dev);
       HIP_LAUNCH_CHECK();
-    }
+    });
   };
   // streaming stores when nobody re-reads the output right away (fp64's
   // 8-dword rows measured slower with them)
   if constexpr (FT != 4) {
-    if (streamOut) return launch(std::integral_constant<int, 0>{}, std::true_type{});
+    if (c.streamOut) return launch(std::integral_constant<int, 0>{}, std::true_type{});
   }
   launch(std::integral_constant<int, 0>{}, std::false_type{});
 }
 
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
-// (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112).  Host sync.
-std::vector<std::pair<int, std::string>> verifyChecksums(StackDeviceMemory& res, uint32_t nb,
-                                                         const BatchDesc& archivesArg, bool isFloat,
-                                                         const BatchDesc& decodedArg,
-                                                         uint32_t maxBytes, hipStream_t s,
-                                                         const DeviceTables* tabs) {
+// (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112; the float
+// codec checksums `capacity` bytes, float words treated as bytes).  Host sync.
+std::vector<std::pair<int, std::string>> verifyChecksums(const DecodeCall& c, bool isFloat) {
   std::vector<std::pair<int, std::string>> errs;
+  const uint32_t nb = c.nb;
+  const hipStream_t s = c.s;
   if (nb == 0) return errs;
-  DeviceDescs dd(res, s, tabs, nb);
-  const BatchDesc archives = dd.map(archivesArg), decoded = dd.map(decodedArg);
-  auto now = res.alloc<uint32_t>(s, nb);
-  auto old = res.alloc<uint32_t>(s, nb);
+  DeviceDescs dd(c.res, s, c.tabs, nb);
+  const BatchDesc archives = dd.map(c.in), decoded = dd.map(c.out);
+  auto now = c.res.alloc<uint32_t>(s, nb);
+  auto old = c.res.alloc<uint32_t>(s, nb);
   zeroAsync(now.data(), sizeof(uint32_t) * nb, s);
-  const uint32_t ckChunk = 1u << 20;
-  for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-    const uint32_t ny = std::min(kMaxGridY, nb - y0);
-    dim3 g(std::max(1u, divUp(maxBytes, ckChunk)), ny);
-    k_checksum<<<g, kThreads, 0, s>>>(decoded, y0, 1, ckChunk, now.data());
-    HIP_LAUNCH_CHECK();
-  }
+  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) { launchChecksum(decoded, y0, ny, c.maxCapacity, now.data(), s); });
   k_info<<<divUp(nb, 128), 128, 0, s>>>(archives, nb, isFloat, nullptr, nullptr, old.data());
   HIP_LAUNCH_CHECK();
   auto a = now.copyToHost(s);
@@ -652,15 +506,100 @@ std::vector<std::pair<int, std::string>> verifyChecksums(StackDeviceMemory& res,
   return errs;
 }
 
-static bool allAligned16(const std::vector<uint64_t>& addrs) {
-  for (uint64_t a : addrs)
-    if (a % 16) return false;
-  return true;
-}
-
 static void checkOutAligned(const void* p, const char* what) {
   DG_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0,
            what << " must be 16-byte aligned (archives are written with 16 B stores)");
+}
+
+
+// ---------------------------------------------------------------------------
+// batch tables of the pointer and split-size entry points.  `unit` is the
+// size of the codec's unit in bytes: 1 for the byte codec, the word size for
+// the float codec (whose pointers must be aligned to it).
+// ---------------------------------------------------------------------------
+struct BatchTables {
+  DeviceTables t;
+  BatchDesc in, out;
+  uint32_t maxSize = 0;      // the largest size (compress) or capacity (decode)
+  bool inAligned16 = false;  // compress: every input starts 16 B-aligned
+};
+
+// in[i] -> out[i]; `sizes` are the inputs' sizes (compress) or the outputs'
+// capacities (decode)
+static BatchTables pointerBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void** in, void** out,
+                                const uint32_t* sizes, bool compress, uint32_t unit) {
+  const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
+  for (uint32_t i = 0; i < nb; ++i) {
+    if (compress) {
+      DG_CHECK(ip[i] % unit == 0, "float input " << i << " not aligned to its word size");
+      checkOutAligned(out[i], "out[i]");
+    } else {
+      DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
+    }
+  }
+  const SizeColumn sz(sizes, nb);
+  BatchTables b;
+  b.t = uploadTables(res, s, {&ip, &op}, sz.sizes, true);
+  b.in = b.t.tag(BatchDesc::pointers(b.t.u64[0], compress ? b.t.u32 : nullptr));
+  b.out = b.t.tag(BatchDesc::pointers(b.t.u64[1], compress ? nullptr : b.t.u32));
+  b.maxSize = sz.maxSize;
+  b.inAligned16 = allAligned16(ip);
+  return b;
+}
+
+// Compress: the elements of `base` -> rows of out_dev.  Decode (archives
+// non-null): archives[i] -> the elements of `base`.
+static BatchTables splitBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void* base,
+                              const uint32_t* splitSizes, uint32_t unit, const void** archives, void* out_dev,
+                              uint32_t outStride) {
+  const SplitColumns sc(splitSizes, nb, unit);
+  BatchTables b;
+  if (archives) {
+    const auto ip = addressColumn(archives, nb);
+    b.t = uploadTables(res, s, {&ip, &sc.offsets}, sc.sizes, true);
+    b.in = b.t.tag(BatchDesc::pointers(b.t.u64[0], nullptr));
+    b.out = b.t.tag(BatchDesc::split(base, b.t.u64[1], b.t.u32));
+  } else {
+    b.t = uploadTables(res, s, {&sc.offsets}, sc.sizes, true);
+    b.in = b.t.tag(BatchDesc::split(base, b.t.u64[0], b.t.u32));
+    b.out = BatchDesc::strided(out_dev, outStride, 0);
+  }
+  b.maxSize = sc.maxSize;
+  b.inAligned16 = reinterpret_cast<uintptr_t>(base) % 16 == 0 && sc.aligned16;
+  return b;
+}
+
+static void checkInteriorSplits(const uint32_t* splitSizes, uint32_t nb) {
+  for (uint32_t i = 0; i + 1 < nb; ++i)
+    DG_CHECK(splitSizes[i] % kANSRequiredAlignment == 0,
+             "interior split sizes must be multiples of " << kANSRequiredAlignment);
+}
+
+// the calls of a batch built above
+static CompressCall compressCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
+                                 uint32_t* outSize_dev) {
+  CompressCall c{res, s};
+  c.nb = nb;
+  c.in = b.in;
+  c.maxSize = b.maxSize;
+  c.out = b.out;
+  c.outSize_dev = outSize_dev;
+  c.tabs = &b.t;
+  c.inAligned16 = b.inAligned16;
+  return c;
+}
+
+static DecodeCall decodeCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
+                             uint8_t* outSuccess_dev, uint32_t* outSize_dev) {
+  DecodeCall c{res, s};
+  c.nb = nb;
+  c.in = b.in;
+  c.out = b.out;
+  c.maxCapacity = b.maxSize;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  c.tabs = &b.t;
+  return c;
 }
 
 // ---------------------------------------------------------------------------
@@ -675,6 +614,13 @@ uint32_t getMaxCompressedSize(uint32_t bytes) {
   return uint32_t(raw);
 }
 
+static void ansEncode(const ANSCodecConfig& config, const uint32_t* histogram_dev, CompressCall c) {
+  c.pb = config.probBits;
+  c.useChecksum = config.useChecksum;
+  c.hist_dev = histogram_dev;
+  encodeBatchDevice<0>(c);
+}
+
 void ansEncodeBatchStride(StackDeviceMemory& res, const ANSCodecConfig& config,
                           uint32_t numInBatch, const void* in_dev, uint32_t inPerBatchSize,
                           uint32_t inPerBatchStride, const uint32_t* histogram_dev,
@@ -683,11 +629,14 @@ void ansEncodeBatchStride(StackDeviceMemory& res, const ANSCodecConfig& config,
   if (numInBatch == 0) return;
   checkOutAligned(out_dev, "out_dev");
   DG_CHECK(outPerBatchStride % 16 == 0, "outPerBatchStride must be a multiple of 16");
-  auto in = BatchDesc::strided(in_dev, inPerBatchStride, inPerBatchSize);
-  auto out = BatchDesc::strided(out_dev, outPerBatchStride, 0);
-  const bool al = reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && inPerBatchStride % 16 == 0;
-  encodeBatchDevice<0>(res, config.probBits, config.useChecksum, numInBatch, in, inPerBatchSize,
-                       histogram_dev, out, outBatchSize_dev, stream, nullptr, al);
+  CompressCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = BatchDesc::strided(in_dev, inPerBatchStride, inPerBatchSize);
+  c.maxSize = inPerBatchSize;
+  c.out = BatchDesc::strided(out_dev, outPerBatchStride, 0);
+  c.outSize_dev = outBatchSize_dev;
+  c.inAligned16 = reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && inPerBatchStride % 16 == 0;
+  ansEncode(config, histogram_dev, c);
 }
 
 void ansEncodeBatchPointer(StackDeviceMemory& res, const ANSCodecConfig& config,
@@ -695,21 +644,8 @@ void ansEncodeBatchPointer(StackDeviceMemory& res, const ANSCodecConfig& config,
                            const uint32_t* histogram_dev, void** out, uint32_t* outSize_dev,
                            hipStream_t stream) {
   if (numInBatch == 0) return;
-  std::vector<uint64_t> ip(numInBatch), op(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint32_t maxSize = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    op[i] = reinterpret_cast<uint64_t>(out[i]);
-    checkOutAligned(out[i], "out[i]");
-    sz[i] = inSize[i];
-    maxSize = std::max(maxSize, inSize[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, op, sz, true);
-  auto inD = t.tag(BatchDesc::pointers(t.u64a, t.u32a));
-  auto outD = t.tag(BatchDesc::pointers(t.u64b, nullptr));
-  encodeBatchDevice<0>(res, config.probBits, config.useChecksum, numInBatch, inD, maxSize,
-                       histogram_dev, outD, outSize_dev, stream, &t, allAligned16(ip));
+  const auto b = pointerBatch(res, stream, numInBatch, in, out, inSize, true, 1);
+  ansEncode(config, histogram_dev, compressCall(res, stream, numInBatch, b, outSize_dev));
 }
 
 void ansEncodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecConfig& config,
@@ -722,39 +658,16 @@ void ansEncodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecConfig& confi
            "in_dev must be " << kANSRequiredAlignment << "-byte aligned");
   checkOutAligned(out_dev, "out_dev");
   DG_CHECK(outStride % 16 == 0, "outStride must be a multiple of 16");
-  std::vector<uint64_t> off(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint64_t run = 0;
-  uint32_t maxSize = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    if (i + 1 != numInBatch) {
-      DG_CHECK(inSplitSizes[i] % kANSRequiredAlignment == 0,
-               "interior split sizes must be multiples of " << kANSRequiredAlignment);
-    }
-    off[i] = run;
-    sz[i] = inSplitSizes[i];
-    run += inSplitSizes[i];
-    maxSize = std::max(maxSize, inSplitSizes[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, off, {}, sz, true);
-  auto inD = t.tag(BatchDesc::split(in_dev, t.u64a, t.u32a));
-  auto outD = BatchDesc::strided(out_dev, outStride, 0);
-  const bool al = reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && allAligned16(off);
-  encodeBatchDevice<0>(res, config.probBits, config.useChecksum, numInBatch, inD, maxSize,
-                       histogram_dev, outD, outSize_dev, stream, &t, al);
+  checkInteriorSplits(inSplitSizes, numInBatch);
+  const auto b = splitBatch(res, stream, numInBatch, in_dev, inSplitSizes, 1, nullptr, out_dev, outStride);
+  ansEncode(config, histogram_dev, compressCall(res, stream, numInBatch, b, outSize_dev));
 }
 
-static ANSDecodeStatus ansDecodeCommon(StackDeviceMemory& res, const ANSCodecConfig& config,
-                                       uint32_t nb, const BatchDesc& in, const BatchDesc& out,
-                                       uint32_t maxCap, uint8_t* succ, uint32_t* sizes,
-                                       hipStream_t s, const DeviceTables* tabs = nullptr) {
-  ANSDecodeStatus status;
-  decodeBatchDevice<0>(res, config.probBits, nb, in, out, maxCap, succ, sizes, s, tabs, !config.useChecksum);
-  if (config.useChecksum) {
-    status.errorInfo = verifyChecksums(res, nb, in, false, out, maxCap, s, tabs);
-    if (!status.errorInfo.empty()) status.error = ANSDecodeError::ChecksumMismatch;
-  }
-  return status;
+static ANSDecodeStatus ansDecodeCommon(const ANSCodecConfig& config, DecodeCall c) {
+  c.pb = config.probBits;
+  c.streamOut = !config.useChecksum;
+  decodeBatchDevice<0>(c);
+  return config.useChecksum ? verifiedStatus<ANSDecodeStatus>(c, false) : ANSDecodeStatus();
 }
 
 ANSDecodeStatus ansDecodeBatchStride(StackDeviceMemory& res, const ANSCodecConfig& config,
@@ -764,10 +677,14 @@ ANSDecodeStatus ansDecodeBatchStride(StackDeviceMemory& res, const ANSCodecConfi
                                      uint8_t* outSuccess_dev, uint32_t* outSize_dev,
                                      hipStream_t stream) {
   if (numInBatch == 0) return ANSDecodeStatus();
-  auto in = BatchDesc::strided(in_dev, inPerBatchStride, 0);
-  auto out = BatchDesc::strided(out_dev, outPerBatchStride, outPerBatchCapacity);
-  return ansDecodeCommon(res, config, numInBatch, in, out, outPerBatchCapacity, outSuccess_dev,
-                         outSize_dev, stream);
+  DecodeCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = BatchDesc::strided(in_dev, inPerBatchStride, 0);
+  c.out = BatchDesc::strided(out_dev, outPerBatchStride, outPerBatchCapacity);
+  c.maxCapacity = outPerBatchCapacity;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  return ansDecodeCommon(config, c);
 }
 
 ANSDecodeStatus ansDecodeBatchPointer(StackDeviceMemory& res, const ANSCodecConfig& config,
@@ -775,20 +692,8 @@ ANSDecodeStatus ansDecodeBatchPointer(StackDeviceMemory& res, const ANSCodecConf
                                       const uint32_t* outCapacity, uint8_t* outSuccess_dev,
                                       uint32_t* outSize_dev, hipStream_t stream) {
   if (numInBatch == 0) return ANSDecodeStatus();
-  std::vector<uint64_t> ip(numInBatch), op(numInBatch);
-  std::vector<uint32_t> cap(numInBatch);
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    op[i] = reinterpret_cast<uint64_t>(out[i]);
-    cap[i] = outCapacity[i];
-    maxCap = std::max(maxCap, cap[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, op, cap, true);
-  auto inD = t.tag(BatchDesc::pointers(t.u64a, nullptr));
-  auto outD = t.tag(BatchDesc::pointers(t.u64b, t.u32a));
-  return ansDecodeCommon(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev,
-                         stream, &t);
+  const auto b = pointerBatch(res, stream, numInBatch, in, out, outCapacity, false, 1);
+  return ansDecodeCommon(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
 }
 
 ANSDecodeStatus ansDecodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecConfig& config,
@@ -798,46 +703,41 @@ ANSDecodeStatus ansDecodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecCo
   if (numInBatch == 0) return ANSDecodeStatus();
   DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % kANSRequiredAlignment == 0,
            "out_dev must be " << kANSRequiredAlignment << "-byte aligned");
-  std::vector<uint64_t> ip(numInBatch), off(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint64_t run = 0;
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    if (i + 1 != numInBatch) {
-      DG_CHECK(outSplitSizes[i] % kANSRequiredAlignment == 0,
-               "interior split sizes must be multiples of " << kANSRequiredAlignment);
-    }
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    off[i] = run;
-    sz[i] = outSplitSizes[i];
-    run += outSplitSizes[i];
-    maxCap = std::max(maxCap, sz[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, off, sz, true);
-  auto inD = t.tag(BatchDesc::pointers(t.u64a, nullptr));
-  auto outD = t.tag(BatchDesc::split(out_dev, t.u64b, t.u32a));
-  return ansDecodeCommon(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev,
-                         stream, &t);
+  checkInteriorSplits(outSplitSizes, numInBatch);
+  const auto b = splitBatch(res, stream, numInBatch, out_dev, outSplitSizes, 1, in, nullptr, 0);
+  return ansDecodeCommon(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
+}
+
+// k_info over a device array of archive addresses (the byte codec has no
+// type word)
+static void launchInfo(const void** in_dev, uint32_t nb, bool isFloat, uint32_t* outSizes_dev,
+                       uint32_t* outTypes_dev, uint32_t* outChecksum_dev, hipStream_t stream) {
+  if (nb == 0 || (!outSizes_dev && !outTypes_dev && !outChecksum_dev)) return;
+  auto inD = BatchDesc::pointers(reinterpret_cast<const uint64_t*>(in_dev), nullptr);
+  k_info<<<divUp(nb, 128), 128, 0, stream>>>(inD, nb, isFloat, outSizes_dev, outTypes_dev, outChecksum_dev);
+  HIP_LAUNCH_CHECK();
+}
+
+// ... over a host array: one upload
+static void uploadAndLaunchInfo(StackDeviceMemory& res, const void** in, uint32_t nb, bool isFloat,
+                                uint32_t* outSizes_dev, uint32_t* outTypes_dev, uint32_t* outChecksum_dev,
+                                hipStream_t stream) {
+  if (nb == 0 || (!outSizes_dev && !outTypes_dev && !outChecksum_dev)) return;
+  const auto ip = addressColumn(in, nb);
+  const auto t = uploadTables(res, stream, {&ip}, {});
+  launchInfo(reinterpret_cast<const void**>(const_cast<uint64_t*>(t.u64[0])), nb, isFloat, outSizes_dev,
+             outTypes_dev, outChecksum_dev, stream);
 }
 
 void ansGetCompressedInfoDevice(StackDeviceMemory& res, const void** in_dev, uint32_t numInBatch,
                                 uint32_t* outSizes_dev, uint32_t* outChecksum_dev,
                                 hipStream_t stream) {
-  if (numInBatch == 0 || (!outSizes_dev && !outChecksum_dev)) return;
-  auto inD = BatchDesc::pointers(reinterpret_cast<const uint64_t*>(in_dev), nullptr);
-  k_info<<<divUp(numInBatch, 128), 128, 0, stream>>>(inD, numInBatch, false, outSizes_dev,
-                                                      nullptr, outChecksum_dev);
-  HIP_LAUNCH_CHECK();
+  launchInfo(in_dev, numInBatch, false, outSizes_dev, nullptr, outChecksum_dev, stream);
 }
 
 void ansGetCompressedInfo(StackDeviceMemory& res, const void** in, uint32_t numInBatch,
                           uint32_t* outSizes_dev, uint32_t* outChecksum_dev, hipStream_t stream) {
-  if (numInBatch == 0 || (!outSizes_dev && !outChecksum_dev)) return;
-  std::vector<uint64_t> ip(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) ip[i] = reinterpret_cast<uint64_t>(in[i]);
-  auto t = uploadTables(res, stream, numInBatch, ip, {}, {});
-  ansGetCompressedInfoDevice(res, reinterpret_cast<const void**>(const_cast<uint64_t*>(t.u64a)),
-                             numInBatch, outSizes_dev, outChecksum_dev, stream);
+  uploadAndLaunchInfo(res, in, numInBatch, false, outSizes_dev, nullptr, outChecksum_dev, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -866,64 +766,21 @@ static void checkFloatConfig(const FloatCodecConfig& c) {
   DG_CHECK(c.floatType != FloatType::kUndefined && uint32_t(c.floatType) <= 4, "bad float type");
 }
 
-void floatCompressDescs(StackDeviceMemory& res, const FloatCompressConfig& config, uint32_t nb,
-                        const BatchDesc& in, uint32_t maxSize, const BatchDesc& out,
-                        uint32_t* outSize_dev, hipStream_t s, const DeviceTables* tabs,
-                        bool inAligned16, const PartialHist* pre, const uint32_t* sparseN) {
+void floatCompressDescs(const FloatCompressConfig& config, CompressCall c) {
   checkFloatConfig(config);
-  const int pb = config.ansConfig.probBits;
-  switch (config.floatType) {
-    case FloatType::kFloat16:
-      encodeBatchDevice<1>(res, pb, config.useChecksum, nb, in, maxSize, nullptr, out, outSize_dev, s,
-                             tabs, inAligned16, pre, sparseN);
-      break;
-    case FloatType::kBFloat16:
-      encodeBatchDevice<2>(res, pb, config.useChecksum, nb, in, maxSize, nullptr, out, outSize_dev, s,
-                             tabs, inAligned16, pre, sparseN);
-      break;
-    case FloatType::kFloat32:
-      encodeBatchDevice<3>(res, pb, config.useChecksum, nb, in, maxSize, nullptr, out, outSize_dev, s,
-                             tabs, inAligned16, pre, sparseN);
-      break;
-    default:
-      encodeBatchDevice<4>(res, pb, config.useChecksum, nb, in, maxSize, nullptr, out, outSize_dev, s,
-                             tabs, inAligned16, pre, sparseN);
-      break;
-  }
+  c.pb = config.ansConfig.probBits;
+  c.useChecksum = config.useChecksum;
+  c.hist_dev = nullptr;
+  dispatchFloatType(config.floatType, [&](auto ft) { encodeBatchDevice<decltype(ft)::value>(c); });
 }
 
-FloatDecompressStatus floatDecompressDescs(StackDeviceMemory& res,
-                                           const FloatDecompressConfig& config, uint32_t nb,
-                                           const BatchDesc& in, const BatchDesc& out,
-                                           uint32_t maxCap, uint8_t* succ, uint32_t* sizes,
-                                           hipStream_t s, const DeviceTables* tabs, bool streamOut,
-                                           bool capacityOnly) {
+FloatDecompressStatus floatDecompressDescs(const FloatDecompressConfig& config, DecodeCall c) {
   checkFloatConfig(config);
-  const int pb = config.ansConfig.probBits;
+  c.pb = config.ansConfig.probBits;
   // streaming output stores unless the output is read back (checksum)
-  const bool nt = streamOut && !config.useChecksum;
-  switch (config.floatType) {
-    case FloatType::kFloat16:
-      decodeBatchDevice<1>(res, pb, nb, in, out, maxCap, succ, sizes, s, tabs, nt, capacityOnly);
-      break;
-    case FloatType::kBFloat16:
-      decodeBatchDevice<2>(res, pb, nb, in, out, maxCap, succ, sizes, s, tabs, nt, capacityOnly);
-      break;
-    case FloatType::kFloat32:
-      decodeBatchDevice<3>(res, pb, nb, in, out, maxCap, succ, sizes, s, tabs, nt, capacityOnly);
-      break;
-    default:
-      decodeBatchDevice<4>(res, pb, nb, in, out, maxCap, succ, sizes, s, tabs, nt, capacityOnly);
-      break;
-  }
-  FloatDecompressStatus status;
-  if (config.useChecksum) {
-    // checksums `capacity` bytes (float words treated as bytes), as the
-    // reference does (float/GpuFloatDecompress.cuh:1077-1112)
-    status.errorInfo = verifyChecksums(res, nb, in, true, out, maxCap, s, tabs);
-    if (!status.errorInfo.empty()) status.error = FloatDecompressError::ChecksumMismatch;
-  }
-  return status;
+  c.streamOut = c.streamOut && !config.useChecksum;
+  dispatchFloatType(config.floatType, [&](auto ft) { decodeBatchDevice<decltype(ft)::value>(c); });
+  return config.useChecksum ? verifiedStatus<FloatDecompressStatus>(c, true) : FloatDecompressStatus();
 }
 
 void floatCompress(StackDeviceMemory& res, const FloatCompressConfig& config, uint32_t numInBatch,
@@ -931,22 +788,8 @@ void floatCompress(StackDeviceMemory& res, const FloatCompressConfig& config, ui
                    hipStream_t stream) {
   if (numInBatch == 0) return;
   checkFloatConfig(config);
-  const uint32_t ws = floatWordBytes(int(config.floatType));
-  std::vector<uint64_t> ip(numInBatch), op(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint32_t maxSize = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    op[i] = reinterpret_cast<uint64_t>(out[i]);
-    DG_CHECK(ip[i] % ws == 0, "float input " << i << " not aligned to its word size");
-    checkOutAligned(out[i], "out[i]");
-    sz[i] = inSize[i];
-    maxSize = std::max(maxSize, inSize[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, op, sz, true);
-  floatCompressDescs(res, config, numInBatch, t.tag(BatchDesc::pointers(t.u64a, t.u32a)), maxSize,
-                     t.tag(BatchDesc::pointers(t.u64b, nullptr)), outSize_dev, stream, &t,
-                     allAligned16(ip));
+  const auto b = pointerBatch(res, stream, numInBatch, in, out, inSize, true, floatWordBytes(int(config.floatType)));
+  floatCompressDescs(config, compressCall(res, stream, numInBatch, b, outSize_dev));
 }
 
 void floatCompressSplitSize(StackDeviceMemory& res, const FloatCompressConfig& config,
@@ -959,20 +802,8 @@ void floatCompressSplitSize(StackDeviceMemory& res, const FloatCompressConfig& c
   DG_CHECK(outStride % 16 == 0, "outStride must be a multiple of 16");
   const uint32_t ws = floatWordBytes(int(config.floatType));
   DG_CHECK(reinterpret_cast<uintptr_t>(in_dev) % ws == 0, "in_dev not word aligned");
-  std::vector<uint64_t> off(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint64_t run = 0;
-  uint32_t maxSize = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    off[i] = run * ws;
-    sz[i] = inSplitSizes[i];
-    run += inSplitSizes[i];
-    maxSize = std::max(maxSize, sz[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, off, {}, sz, true);
-  floatCompressDescs(res, config, numInBatch, t.tag(BatchDesc::split(in_dev, t.u64a, t.u32a)),
-                     maxSize, BatchDesc::strided(out_dev, outStride, 0), outSize_dev, stream, &t,
-                     reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && allAligned16(off));
+  const auto b = splitBatch(res, stream, numInBatch, in_dev, inSplitSizes, ws, nullptr, out_dev, outStride);
+  floatCompressDescs(config, compressCall(res, stream, numInBatch, b, outSize_dev));
 }
 
 void floatCompressBatchStride(StackDeviceMemory& res, const FloatCompressConfig& config,
@@ -983,11 +814,14 @@ void floatCompressBatchStride(StackDeviceMemory& res, const FloatCompressConfig&
   if (numInBatch == 0) return;
   checkOutAligned(out_dev, "out_dev");
   DG_CHECK(outPerBatchStrideBytes % 16 == 0, "out stride must be a multiple of 16");
-  floatCompressDescs(res, config, numInBatch,
-                     BatchDesc::strided(in_dev, inPerBatchStrideBytes, inPerBatchWords),
-                     inPerBatchWords, BatchDesc::strided(out_dev, outPerBatchStrideBytes, 0),
-                     outSize_dev, stream, nullptr,
-                     reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && inPerBatchStrideBytes % 16 == 0);
+  CompressCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = BatchDesc::strided(in_dev, inPerBatchStrideBytes, inPerBatchWords);
+  c.maxSize = inPerBatchWords;
+  c.out = BatchDesc::strided(out_dev, outPerBatchStrideBytes, 0);
+  c.outSize_dev = outSize_dev;
+  c.inAligned16 = reinterpret_cast<uintptr_t>(in_dev) % 16 == 0 && inPerBatchStrideBytes % 16 == 0;
+  floatCompressDescs(config, c);
 }
 
 FloatDecompressStatus floatDecompress(StackDeviceMemory& res, const FloatDecompressConfig& config,
@@ -996,21 +830,9 @@ FloatDecompressStatus floatDecompress(StackDeviceMemory& res, const FloatDecompr
                                       uint32_t* outSize_dev, hipStream_t stream) {
   if (numInBatch == 0) return FloatDecompressStatus();
   checkFloatConfig(config);
-  const uint32_t ws = floatWordBytes(int(config.floatType));
-  std::vector<uint64_t> ip(numInBatch), op(numInBatch);
-  std::vector<uint32_t> cap(numInBatch);
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    op[i] = reinterpret_cast<uint64_t>(out[i]);
-    DG_CHECK(op[i] % ws == 0, "float output " << i << " not aligned to its word size");
-    cap[i] = outCapacity[i];
-    maxCap = std::max(maxCap, cap[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, op, cap, true);
-  return floatDecompressDescs(res, config, numInBatch, t.tag(BatchDesc::pointers(t.u64a, nullptr)),
-                              t.tag(BatchDesc::pointers(t.u64b, t.u32a)), maxCap, outSuccess_dev,
-                              outSize_dev, stream, &t);
+  const auto b =
+      pointerBatch(res, stream, numInBatch, in, out, outCapacity, false, floatWordBytes(int(config.floatType)));
+  return floatDecompressDescs(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
 }
 
 FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,
@@ -1023,21 +845,8 @@ FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,
   checkFloatConfig(config);
   const uint32_t ws = floatWordBytes(int(config.floatType));
   DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % ws == 0, "out_dev not word aligned");
-  std::vector<uint64_t> ip(numInBatch), off(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint64_t run = 0;
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    off[i] = run * ws;
-    sz[i] = outSplitSizes[i];
-    run += outSplitSizes[i];
-    maxCap = std::max(maxCap, sz[i]);
-  }
-  auto t = uploadTables(res, stream, numInBatch, ip, off, sz, true);
-  return floatDecompressDescs(res, config, numInBatch, t.tag(BatchDesc::pointers(t.u64a, nullptr)),
-                              t.tag(BatchDesc::split(out_dev, t.u64b, t.u32a)), maxCap,
-                              outSuccess_dev, outSize_dev, stream, &t);
+  const auto b = splitBatch(res, stream, numInBatch, out_dev, outSplitSizes, ws, in, nullptr, 0);
+  return floatDecompressDescs(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
 }
 
 FloatDecompressStatus floatDecompressBatchStride(StackDeviceMemory& res,
@@ -1049,31 +858,26 @@ FloatDecompressStatus floatDecompressBatchStride(StackDeviceMemory& res,
                                                  uint8_t* outSuccess_dev, uint32_t* outSize_dev,
                                                  hipStream_t stream) {
   if (numInBatch == 0) return FloatDecompressStatus();
-  return floatDecompressDescs(
-      res, config, numInBatch, BatchDesc::strided(in_dev, inPerBatchStrideBytes, 0),
-      BatchDesc::strided(out_dev, outPerBatchStrideBytes, outPerBatchCapacityWords),
-      outPerBatchCapacityWords, outSuccess_dev, outSize_dev, stream);
+  DecodeCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = BatchDesc::strided(in_dev, inPerBatchStrideBytes, 0);
+  c.out = BatchDesc::strided(out_dev, outPerBatchStrideBytes, outPerBatchCapacityWords);
+  c.maxCapacity = outPerBatchCapacityWords;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  return floatDecompressDescs(config, c);
 }
 
 void floatGetCompressedInfoDevice(StackDeviceMemory& res, const void** in_dev, uint32_t numInBatch,
                                   uint32_t* outSizes_dev, uint32_t* outTypes_dev,
                                   uint32_t* outChecksum_dev, hipStream_t stream) {
-  if (numInBatch == 0 || (!outSizes_dev && !outTypes_dev && !outChecksum_dev)) return;
-  auto inD = BatchDesc::pointers(reinterpret_cast<const uint64_t*>(in_dev), nullptr);
-  k_info<<<divUp(numInBatch, 128), 128, 0, stream>>>(inD, numInBatch, true, outSizes_dev,
-                                                      outTypes_dev, outChecksum_dev);
-  HIP_LAUNCH_CHECK();
+  launchInfo(in_dev, numInBatch, true, outSizes_dev, outTypes_dev, outChecksum_dev, stream);
 }
 
 void floatGetCompressedInfo(StackDeviceMemory& res, const void** in, uint32_t numInBatch,
                             uint32_t* outSizes_dev, uint32_t* outTypes_dev,
                             uint32_t* outChecksum_dev, hipStream_t stream) {
-  if (numInBatch == 0 || (!outSizes_dev && !outTypes_dev && !outChecksum_dev)) return;
-  std::vector<uint64_t> ip(numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) ip[i] = reinterpret_cast<uint64_t>(in[i]);
-  auto t = uploadTables(res, stream, numInBatch, ip, {}, {});
-  floatGetCompressedInfoDevice(res, reinterpret_cast<const void**>(const_cast<uint64_t*>(t.u64a)),
-                               numInBatch, outSizes_dev, outTypes_dev, outChecksum_dev, stream);
+  uploadAndLaunchInfo(res, in, numInBatch, true, outSizes_dev, outTypes_dev, outChecksum_dev, stream);
 }
 
 }  // namespace dietgpu

@@ -1,16 +1,19 @@
 // Internal entry points shared by the dense and sparse float drivers.
 #pragma once
 
+#include <algorithm>
+#include <map>
+#include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "batch.h"
+#include "batch_tables.h"
 #include "dietgpu/GpuFloatCodec.h"
 
 namespace dietgpu {
-
-struct DeviceTables;  // codec.hip: per-call pointer tables (maybe kernel-argument inline)
 
 // Partial symbol histograms of the float words counted by the caller (the
 // sparse compressor counts its nonzeros as it compacts them, so the dense
@@ -26,11 +29,81 @@ struct PartialHist {
   const uint16_t* pdf = nullptr;
 };
 
-void floatCompressDescs(StackDeviceMemory& res, const FloatCompressConfig& config, uint32_t nb,
-                        const BatchDesc& in, uint32_t maxSize, const BatchDesc& out,
-                        uint32_t* outSize_dev, hipStream_t s, const DeviceTables* tabs = nullptr,
-                        bool inAligned16 = false, const PartialHist* pre = nullptr,
-                        const uint32_t* sparseN = nullptr);
+// One compress call of the generic drivers (codec.hip): nb elements `in` of at
+// most maxSize units (bytes, or float words) into the archives `out`.
+struct CompressCall {
+  StackDeviceMemory& res;
+  hipStream_t s;
+  int pb = 0;
+  bool useChecksum = false;
+  uint32_t nb = 0;
+  BatchDesc in;
+  uint32_t maxSize = 0;
+  BatchDesc out;
+  uint32_t* outSize_dev = nullptr;
+  const uint32_t* hist_dev = nullptr;  // byte codec: the caller's histograms
+  const DeviceTables* tabs = nullptr;  // the tables `in` / `out` refer to
+  // every element's input starts 16 B-aligned (the single-pass compressor
+  // reads whole 16 B vectors; anything else takes three kernels)
+  bool inAligned16 = false;
+  const PartialHist* pre = nullptr;
+  // the sparse codec's N per element: the archive's size writer adds the
+  // sparse header and bitmap to outSize (EncTail::sparseN)
+  const uint32_t* sparseN = nullptr;
+};
+
+// One decode call: nb archives `in` into `out` (capacities: out.size(b), at
+// most maxCapacity units).
+struct DecodeCall {
+  StackDeviceMemory& res;
+  hipStream_t s;
+  int pb = 0;
+  uint32_t nb = 0;
+  BatchDesc in, out;
+  uint32_t maxCapacity = 0;
+  uint8_t* outSuccess_dev = nullptr;
+  uint32_t* outSize_dev = nullptr;
+  const DeviceTables* tabs = nullptr;
+  bool streamOut = true;      // streaming output stores (nobody re-reads it right away)
+  bool capacityOnly = false;  // maxCapacity may far exceed the archives' sizes
+};
+
+// f(std::integral_constant<int, FT>{}) for the float type's FT (1 fp16,
+// 2 bf16, 3 fp32, 4 fp64; the type has been validated).
+template <typename F>
+decltype(auto) dispatchFloatType(FloatType ft, F&& f) {
+  switch (ft) {
+    case FloatType::kFloat16: return f(std::integral_constant<int, 1>{});
+    case FloatType::kBFloat16: return f(std::integral_constant<int, 2>{});
+    case FloatType::kFloat32: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+// f(y0, ny) for each slice of a batch that fits a grid's y dimension.
+constexpr uint32_t kMaxGridY = 65535;
+template <typename F>
+void forGridYSlices(uint32_t nb, F&& f) {
+  for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) f(y0, std::min(kMaxGridY, nb - y0));
+}
+
+// query(device) for the current device, cached per (device, key): the
+// runtime's queries cost host time on every call.  Each call site has a cache
+// of its own (its lambda's type instantiates the function).
+template <typename V, typename K, typename Q>
+V cachedPerDevice(const K& key, Q&& query) {
+  static std::mutex m;
+  static std::map<std::pair<int, K>, V> cache;
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> g(m);
+  auto it = cache.find({dev, key});
+  if (it == cache.end()) it = cache.emplace(std::make_pair(dev, key), query(dev)).first;
+  return it->second;
+}
+
+// c.pb / c.useChecksum come from the config.
+void floatCompressDescs(const FloatCompressConfig& config, CompressCall c);
 
 // Whether encodeBatchDevice compresses nb 16 B-aligned elements of at most
 // maxWords words of a single-segment format (FT 0-3) with the single-pass
@@ -38,20 +111,22 @@ void floatCompressDescs(StackDeviceMemory& res, const FloatCompressConfig& confi
 template <int FT>
 bool persistentPreferred(uint32_t nb, uint32_t maxWords);
 
-FloatDecompressStatus floatDecompressDescs(StackDeviceMemory& res,
-                                           const FloatDecompressConfig& config, uint32_t nb,
-                                           const BatchDesc& in, const BatchDesc& out,
-                                           uint32_t maxCap, uint8_t* succ, uint32_t* sizes,
-                                           hipStream_t s, const DeviceTables* tabs = nullptr,
-                                           bool streamOut = true, bool capacityOnly = false);
+// c.pb comes from the config; a checksummed call reads its output back, so
+// it never streams.
+FloatDecompressStatus floatDecompressDescs(const FloatDecompressConfig& config, DecodeCall c);
 
-// Compare archive checksums with the XOR of `decoded.size(b)` bytes of each
-// decoded element; synchronises `s`.
-std::vector<std::pair<int, std::string>> verifyChecksums(StackDeviceMemory& res, uint32_t nb,
-                                                         const BatchDesc& archives, bool isFloat,
-                                                         const BatchDesc& decoded,
-                                                         uint32_t maxBytes, hipStream_t s,
-                                                         const DeviceTables* tabs = nullptr);
+// Compare the checksums stored in the archives c.in with the XOR of the
+// first c.out.size(b) bytes of each decoded element; synchronises c.s.
+std::vector<std::pair<int, std::string>> verifyChecksums(const DecodeCall& c, bool isFloat);
+
+// The status of a checksummed decode call (verifyChecksums).
+template <typename Status>
+Status verifiedStatus(const DecodeCall& c, bool isFloat) {
+  Status status;
+  status.errorInfo = verifyChecksums(c, isFloat);
+  if (!status.errorInfo.empty()) status.error = decltype(status.error)::ChecksumMismatch;
+  return status;
+}
 
 // The device error word (elements whose compression was abandoned after a
 // bounded wait ran out; their outSize is 0), codec.hip.

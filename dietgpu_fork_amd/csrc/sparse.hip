@@ -23,8 +23,6 @@
 // reference's n-2 quirk (fill_comp_input :162-184): when x[N-2] == 0 one extra
 // slot (written as 0 here, uninitialised in the reference) precedes x[N-1].
 #include <algorithm>
-#include <cstring>
-#include <optional>
 #include <vector>
 
 #include "codec_internal.h"
@@ -40,7 +38,6 @@ namespace dietgpu {
 namespace {
 
 constexpr uint32_t kTileWords = 4096;   // 4 waves x 16 steps x 64 lanes
-constexpr uint32_t kMaxGridY = 65535;
 
 template <int FT>
 using WordOf = typename FloatTraits<FT>::WordT;
@@ -429,15 +426,15 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   }
 }
 
-// in: the sparse inputs (sizes = N); outD: the sparse archives; denseOut:
-// where each dense archive starts; sparseN: a device array holding each
-// element's N (the dense archive's size writer adds the sparse header and
-// bitmap to outSize, EncTail::sparseN).
+// c: the sparse inputs (sizes = N, at most c.maxSize) -> the sparse archives
+// c.out; denseOut: where each dense archive starts; c.sparseN: a device array
+// holding each element's N (the dense archive's size writer adds the sparse
+// header and bitmap to outSize, EncTail::sparseN).
 template <int FT>
-void sparseCompressT(StackDeviceMemory& res, const FloatCompressConfig& config, uint32_t nb,
-                     const BatchDesc& in, uint32_t maxN, const BatchDesc& outD,
-                     const BatchDesc& denseOut, const uint32_t* sparseN, uint32_t* outSize_dev, hipStream_t s,
-                     bool inAligned16) {
+void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, const BatchDesc& denseOut) {
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const uint32_t nb = c.nb, maxN = c.maxSize;
   const uint32_t tiles = std::max(1u, divUp(maxN, kTileWords));
   auto tileCounts = res.alloc<uint32_t>(s, size_t(nb) * tiles);
   auto listLen = res.alloc<uint32_t>(s, nb);
@@ -458,60 +455,71 @@ void sparseCompressT(StackDeviceMemory& res, const FloatCompressConfig& config, 
   bool countHist = nb == 1;
   if constexpr (FT != 4) countHist = countHist && !persistentPreferred<FT>(nb, maxN);
   constexpr int kSegs = FloatTraits<FT>::kSegs;
-  // histogram rows: up to 64 per element, accumulated with atomics into this
-  // stream's sync-arena row buffer (zero on entry; k_sparseCount zeroes the
-  // other buffer for the next call).  The lease is released before the dense
-  // codec takes its own.
   const uint32_t G = tiles;
   const uint32_t R = std::min(tiles, kReduceRows);
   const size_t rowsBytes = countHist ? size_t(kSegs) * nb * R * kNumSymbols * 4 : 0;
-  std::optional<SyncLease> lease;
-  if (countHist) lease.emplace(res, s, kNoSyncRegions, false, rowsBytes);
-  uint32_t* const histRows = countHist ? static_cast<uint32_t*>(lease->rows[0]) : nullptr;
-  uint32_t* const zeroNext = countHist ? static_cast<uint32_t*>(lease->rows[1]) : nullptr;
   auto table = res.alloc<uint4>(s, countHist ? size_t(kSegs) * nb * kNumSymbols : 1);
   auto pdf = res.alloc<uint16_t>(s, countHist ? size_t(kSegs) * nb * kNumSymbols : 1);
-  NormArgs na{};
-  na.in = in;
-  na.hist = histRows;
-  na.rows = R;
-  na.pb = config.ansConfig.probBits;
-  na.table = table.data();
-  na.pdf = pdf.data();
-  na.totalFromHist = true;  // the list length is written by this same launch
-  for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-    const uint32_t ny = std::min(kMaxGridY, nb - y0);
-    prof::Scope p("sparse", s);
-    auto launch = [&](auto vecTag, auto histTag) {
-      k_sparseCount<FT, decltype(vecTag)::value, decltype(histTag)::value><<<dim3(G, ny), kThreads, 0, s>>>(
-          in, outD, y0, nb, tiles, tileCounts.data(), staging.data(), histRows, zeroNext, R);
-    };
-    if (inAligned16) {
-      if (countHist) launch(std::true_type{}, std::true_type{});
-      else launch(std::true_type{}, std::false_type{});
-    } else {
-      if (countHist) launch(std::false_type{}, std::true_type{});
-      else launch(std::false_type{}, std::false_type{});
-    }
-    HIP_LAUNCH_CHECK();
-    k_sparseGather<FT><<<dim3(tiles + (countHist ? 1 : 0), ny), kThreads, 0, s>>>(
-        in, y0, nb, tiles, tileCounts.data(), listLen.data(), staging.data(), lists, na);
-    HIP_LAUNCH_CHECK();
-  }
-  lease.reset();
-  PartialHist pre{histRows, R};
+  PartialHist pre{nullptr, R};
   pre.table = table.data();
   pre.pdf = pdf.data();
-  floatCompressDescs(res, config, nb, lists, maxN, denseOut, outSize_dev, s, nullptr, true,
-                     countHist ? &pre : nullptr, sparseN);
+  auto launchAll = [&](uint32_t* histRows, uint32_t* zeroNext) {
+    NormArgs na{};
+    na.in = c.in;
+    na.hist = histRows;
+    na.rows = R;
+    na.pb = config.ansConfig.probBits;
+    na.table = table.data();
+    na.pdf = pdf.data();
+    na.totalFromHist = true;  // the list length is written by this same launch
+    forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
+      prof::Scope p("sparse", s);
+      auto launch = [&](auto vecTag, auto histTag) {
+        k_sparseCount<FT, decltype(vecTag)::value, decltype(histTag)::value><<<dim3(G, ny), kThreads, 0, s>>>(
+            c.in, c.out, y0, nb, tiles, tileCounts.data(), staging.data(), histRows, zeroNext, R);
+      };
+      if (c.inAligned16) {
+        if (countHist) launch(std::true_type{}, std::true_type{});
+        else launch(std::true_type{}, std::false_type{});
+      } else {
+        if (countHist) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+      }
+      HIP_LAUNCH_CHECK();
+      k_sparseGather<FT><<<dim3(tiles + (countHist ? 1 : 0), ny), kThreads, 0, s>>>(
+          c.in, y0, nb, tiles, tileCounts.data(), listLen.data(), staging.data(), lists, na);
+      HIP_LAUNCH_CHECK();
+    });
+  };
+  if (countHist) {
+    // histogram rows: up to 64 per element, accumulated with atomics into this
+    // stream's sync-arena row buffer (zero on entry; k_sparseCount zeroes the
+    // other buffer for the next call).  The lease is the arena's newest
+    // allocation and ends with this scope, before the dense codec takes its
+    // own (the arena's mutex is not recursive).
+    SyncLease lease(res, s, kNoSyncRegions, false, rowsBytes);
+    pre.rows = static_cast<uint32_t*>(lease.rows[0]);
+    launchAll(static_cast<uint32_t*>(lease.rows[0]), static_cast<uint32_t*>(lease.rows[1]));
+  } else {
+    launchAll(nullptr, nullptr);
+  }
+  CompressCall dense{res, s};
+  dense.nb = nb;
+  dense.in = lists;
+  dense.maxSize = maxN;
+  dense.out = denseOut;
+  dense.outSize_dev = c.outSize_dev;
+  dense.inAligned16 = true;
+  dense.pre = countHist ? &pre : nullptr;
+  dense.sparseN = c.sparseN;
+  floatCompressDescs(config, dense);
 }
 
 template <int FT>
-FloatDecompressStatus sparseDecompressT(StackDeviceMemory& res,
-                                        const FloatDecompressConfig& config, uint32_t nb,
-                                        const BatchDesc& in, const BatchDesc& out,
-                                        uint32_t maxCap, uint8_t* outSuccess_dev,
-                                        uint32_t* outSize_dev, hipStream_t s) {
+FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, const DecodeCall& c) {
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const uint32_t nb = c.nb, maxCap = c.maxCapacity;
   const uint32_t chunks = std::max(1u, divUp(maxCap, kChunkWords));
   const uint32_t cblocks = divUp(chunks, kThreads);  // k_sparseChunks workgroups per element
   auto densePtrs = res.alloc<uint64_t>(s, nb);
@@ -519,48 +527,44 @@ FloatDecompressStatus sparseDecompressT(StackDeviceMemory& res,
   auto denseOk = res.alloc<uint8_t>(s, nb);
   const uint64_t listStride = uint64_t(roundUp(maxCap, 16) + 16) * sizeof(WordOf<FT>);
   auto list = res.alloc<uint8_t>(s, size_t(nb) * listStride);
-  const BatchDesc lists = BatchDesc::strided(list.data(), listStride, maxCap + 1);
   auto chunkPre = res.alloc<uint32_t>(s, size_t(nb) * chunks);
   auto blockTot = res.alloc<uint32_t>(s, size_t(nb) * cblocks);
-  for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-    const uint32_t ny = std::min(kMaxGridY, nb - y0);
+  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
     prof::Scope p("sparse", s);
-    k_sparseChunks<<<dim3(cblocks, ny), kThreads, 0, s>>>(in, y0, chunks, cblocks, densePtrs.data(), sizes.data(),
+    k_sparseChunks<<<dim3(cblocks, ny), kThreads, 0, s>>>(c.in, y0, chunks, cblocks, densePtrs.data(), sizes.data(),
                                                           chunkPre.data(), blockTot.data());
     HIP_LAUNCH_CHECK();
-  }
+  });
   // dense decode of the nonzero list (capacity: the largest output)
+  DecodeCall dense{res, s};
+  dense.nb = nb;
+  dense.in = BatchDesc::pointers(densePtrs.data(), nullptr);
+  dense.out = BatchDesc::strided(list.data(), listStride, maxCap + 1);
+  dense.maxCapacity = maxCap + 1;
+  dense.outSuccess_dev = denseOk.data();
+  dense.streamOut = false;  // the expansion reads it
+  dense.capacityOnly = true;
+  const BatchDesc lists = dense.out;
   auto cfg = config;
   cfg.useChecksum = false;
-  floatDecompressDescs(res, cfg, nb, BatchDesc::pointers(densePtrs.data(), nullptr),
-                       lists, maxCap + 1,
-                       denseOk.data(), nullptr, s, nullptr, /*streamOut=*/false,  // the expansion reads it
-                       /*capacityOnly=*/true);
+  floatDecompressDescs(cfg, dense);
   FloatDecompressStatus status;
   if (config.useChecksum) {
     // verify the dense archive's checksum over the bytes it was computed on
     // (the first listLen bytes of the nonzero list)
     auto denseLen = res.alloc<uint32_t>(s, nb);
-    k_info<<<divUp(nb, 128), 128, 0, s>>>(BatchDesc::pointers(densePtrs.data(), nullptr), nb, true,
-                                          denseLen.data(), nullptr, nullptr);
+    k_info<<<divUp(nb, 128), 128, 0, s>>>(dense.in, nb, true, denseLen.data(), nullptr, nullptr);
     HIP_LAUNCH_CHECK();
-    status.errorInfo = verifyChecksums(res, nb, BatchDesc::pointers(densePtrs.data(), nullptr), true,
-                                       [&] {
-                                         BatchDesc d = lists;
-                                         d.sizes = denseLen.data();
-                                         return d;
-                                       }(),
-                                       maxCap + 1, s);
-    if (!status.errorInfo.empty()) status.error = FloatDecompressError::ChecksumMismatch;
+    dense.out.sizes = denseLen.data();
+    status = verifiedStatus<FloatDecompressStatus>(dense, true);
   }
-  for (uint32_t y0 = 0; y0 < nb; y0 += kMaxGridY) {
-    const uint32_t ny = std::min(kMaxGridY, nb - y0);
+  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
     prof::Scope p("sparse", s);
     k_sparseExpand<FT><<<dim3(divUp(chunks, kWaves), ny), kThreads, 0, s>>>(
-        in, out, y0, chunks, cblocks, sizes.data(), chunkPre.data(), blockTot.data(), lists, denseOk.data(),
-        outSuccess_dev, outSize_dev);
+        c.in, c.out, y0, chunks, cblocks, sizes.data(), chunkPre.data(), blockTot.data(), lists, denseOk.data(),
+        c.outSuccess_dev, c.outSize_dev);
     HIP_LAUNCH_CHECK();
-  }
+  });
   return status;
 }
 
@@ -572,6 +576,9 @@ uint32_t getMaxSparseFloatCompressedSize(FloatType ft, uint32_t size) {
   return uint32_t(v);
 }
 
+// The sparse kernels take no InlineTable: DeviceDescs turns the tables into
+// one device upload, or for one element (the reference's SparseFloatBenchmark
+// shape) into stride descriptors without any upload.
 void floatCompressSparse(StackDeviceMemory& res, const FloatCompressConfig& config,
                          uint32_t numInBatch, const void** in, const uint32_t* inSize, void** out,
                          uint32_t* outSize_dev, hipStream_t stream) {
@@ -580,55 +587,28 @@ void floatCompressSparse(StackDeviceMemory& res, const FloatCompressConfig& conf
   const int ft = int(config.floatType);
   DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
   const uint32_t ws = floatWordBytes(ft);
-  std::vector<uint64_t> ip(numInBatch), op(numInBatch), dp(numInBatch);
-  std::vector<uint32_t> sz(numInBatch);
-  uint32_t maxN = 0;
+  const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
+  const SizeColumn sz(inSize, numInBatch);
+  std::vector<uint64_t> dp(numInBatch);  // the dense archives, after header and bitmap
   for (uint32_t i = 0; i < numInBatch; ++i) {
-    ip[i] = reinterpret_cast<uint64_t>(in[i]);
-    op[i] = reinterpret_cast<uint64_t>(out[i]);
     DG_CHECK(op[i] % 16 == 0, "out[i] must be 16-byte aligned");
     DG_CHECK(ip[i] % ws == 0, "input not word aligned");
-    sz[i] = inSize[i];
-    dp[i] = op[i] + 16 + roundUp((sz[i] + 7) / 8, 16);
-    maxN = std::max(maxN, sz[i]);
+    dp[i] = op[i] + 16 + roundUp((sz.sizes[i] + 7) / 8, 16);
   }
-  bool aligned = true;
-  for (uint32_t i = 0; i < numInBatch; ++i) aligned = aligned && ip[i] % 16 == 0;
-  GpuMemoryReservation<uint8_t> tbl;
-  BatchDesc inD, outD, denseOut;
-  const uint32_t* sparseN;
-  if (numInBatch == 1) {
-    // one element (the reference's SparseFloatBenchmark shape): stride
-    // descriptors, no table upload; the dense archive's size writer reads N
-    // from the sparse header k_sparseCount writes first (word 0 of the archive)
-    inD = BatchDesc::strided(in[0], 0, sz[0]);
-    outD = BatchDesc::strided(out[0], 0, 0);
-    denseOut = BatchDesc::strided(reinterpret_cast<void*>(dp[0]), 0, 0);
-    sparseN = reinterpret_cast<const uint32_t*>(out[0]);
-  } else {
-    std::vector<uint64_t> ptrs(ip);
-    ptrs.insert(ptrs.end(), op.begin(), op.end());
-    ptrs.insert(ptrs.end(), dp.begin(), dp.end());
-    tbl = res.alloc<uint8_t>(stream, ptrs.size() * 8 + sz.size() * 4);
-    std::vector<uint8_t> host(ptrs.size() * 8 + sz.size() * 4);
-    std::memcpy(host.data(), ptrs.data(), ptrs.size() * 8);
-    std::memcpy(host.data() + ptrs.size() * 8, sz.data(), sz.size() * 4);
-    StackDeviceMemory::copyToDevice(tbl.data(), host.data(), host.size(), stream);
-    const uint64_t* ipD = reinterpret_cast<const uint64_t*>(tbl.data());
-    const uint64_t* opD = ipD + numInBatch;
-    const uint64_t* dpD = opD + numInBatch;
-    const uint32_t* szD = reinterpret_cast<const uint32_t*>(dpD + numInBatch);
-    inD = BatchDesc::pointers(ipD, szD);
-    outD = BatchDesc::pointers(opD, nullptr);
-    denseOut = BatchDesc::pointers(dpD, nullptr);
-    sparseN = szD;
-  }
-  switch (ft) {
-    case 1: sparseCompressT<1>(res, config, numInBatch, inD, maxN, outD, denseOut, sparseN, outSize_dev, stream, aligned); break;
-    case 2: sparseCompressT<2>(res, config, numInBatch, inD, maxN, outD, denseOut, sparseN, outSize_dev, stream, aligned); break;
-    case 3: sparseCompressT<3>(res, config, numInBatch, inD, maxN, outD, denseOut, sparseN, outSize_dev, stream, aligned); break;
-    default: sparseCompressT<4>(res, config, numInBatch, inD, maxN, outD, denseOut, sparseN, outSize_dev, stream, aligned); break;
-  }
+  const auto t = uploadTables(res, stream, {&ip, &op, &dp}, sz.sizes, true);
+  const DeviceDescs dd(res, stream, &t, numInBatch);
+  CompressCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], t.u32)));
+  c.maxSize = sz.maxSize;
+  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], nullptr)));
+  c.outSize_dev = outSize_dev;
+  c.inAligned16 = allAligned16(ip);
+  // one element: the dense archive's size writer reads N from the sparse
+  // header k_sparseCount writes first (word 0 of the archive)
+  c.sparseN = numInBatch == 1 ? reinterpret_cast<const uint32_t*>(out[0]) : c.in.sizes;
+  const BatchDesc denseOut = dd.map(t.tag(BatchDesc::pointers(t.u64[2], nullptr)));
+  dispatchFloatType(config.floatType, [&](auto f) { sparseCompressT<decltype(f)::value>(config, c, denseOut); });
 }
 
 FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
@@ -640,38 +620,19 @@ FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
   DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
   const int ft = int(config.floatType);
   DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
-  std::vector<uint64_t> ptrs(2 * numInBatch);
-  std::vector<uint32_t> cap(numInBatch);
-  uint32_t maxCap = 0;
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    ptrs[i] = reinterpret_cast<uint64_t>(in[i]);
-    ptrs[numInBatch + i] = reinterpret_cast<uint64_t>(out[i]);
-    cap[i] = outCapacity[i];
-    maxCap = std::max(maxCap, cap[i]);
-  }
-  GpuMemoryReservation<uint8_t> tbl;
-  BatchDesc inD, outD;
-  if (numInBatch == 1) {  // stride descriptors, no table upload
-    inD = BatchDesc::strided(in[0], 0, 0);
-    outD = BatchDesc::strided(out[0], 0, cap[0]);
-  } else {
-    tbl = res.alloc<uint8_t>(stream, ptrs.size() * 8 + cap.size() * 4);
-    std::vector<uint8_t> host(ptrs.size() * 8 + cap.size() * 4);
-    std::memcpy(host.data(), ptrs.data(), ptrs.size() * 8);
-    std::memcpy(host.data() + ptrs.size() * 8, cap.data(), cap.size() * 4);
-    StackDeviceMemory::copyToDevice(tbl.data(), host.data(), host.size(), stream);
-    const uint64_t* ipD = reinterpret_cast<const uint64_t*>(tbl.data());
-    const uint64_t* opD = ipD + numInBatch;
-    const uint32_t* capD = reinterpret_cast<const uint32_t*>(opD + numInBatch);
-    inD = BatchDesc::pointers(ipD, nullptr);
-    outD = BatchDesc::pointers(opD, capD);
-  }
-  switch (ft) {
-    case 1: return sparseDecompressT<1>(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev, stream);
-    case 2: return sparseDecompressT<2>(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev, stream);
-    case 3: return sparseDecompressT<3>(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev, stream);
-    default: return sparseDecompressT<4>(res, config, numInBatch, inD, outD, maxCap, outSuccess_dev, outSize_dev, stream);
-  }
+  const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
+  const SizeColumn cap(outCapacity, numInBatch);
+  const auto t = uploadTables(res, stream, {&ip, &op}, cap.sizes, true);
+  const DeviceDescs dd(res, stream, &t, numInBatch);
+  DecodeCall c{res, stream};
+  c.nb = numInBatch;
+  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], nullptr)));
+  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], t.u32)));
+  c.maxCapacity = cap.maxSize;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  return dispatchFloatType(config.floatType,
+                           [&](auto f) { return sparseDecompressT<decltype(f)::value>(config, c); });
 }
 
 }  // namespace dietgpu

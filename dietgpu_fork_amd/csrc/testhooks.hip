@@ -50,8 +50,9 @@ __global__ __launch_bounds__(kThreads) void k_sumChunkRows(const uint32_t* part,
 
 // hist[b][256] = byte histogram of element b of a stride batch (elements of
 // `size` bytes, `stride` bytes apart): k_hist<0> (the compressor's own
-// histogram kernel, chunked exactly as encodeBatchDevice chunks it) and a row
-// sum.  ansHistogramBatch (ans/GpuANSStatistics.cuh:113-143).
+// histogram kernel, in 64 K-byte chunks, doubled while an element has more
+// than 4096: without the halving for small batches of the compressor's
+// histChunkWords) and a row sum.  ansHistogramBatch (ans/GpuANSStatistics.cuh:113-143).
 void testHistogram(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void* in_dev, uint32_t size,
                    uint32_t stride, uint32_t* hist_dev) {
   if (nb == 0) return;

@@ -142,6 +142,47 @@ int64_t max_any_compressed_size(int64_t bytes) {
 
 // ------------------------------------------------------------- compress ----
 
+// The caller's out_compressed / out_compressed_bytes, validated for n rows of
+// cols bytes on `dev`, or fresh tensors with the options of `like`.
+std::pair<at::Tensor, at::Tensor> outputTensors(const std::optional<at::Tensor>& outCompressed,
+                                                const std::optional<at::Tensor>& outSizes, int64_t n,
+                                                int64_t cols, int dev, const at::Tensor& like) {
+  at::Tensor comp;
+  if (outCompressed) {
+    const auto& c = *outCompressed;
+    TORCH_CHECK(c.scalar_type() == at::kByte && c.device().type() == at::kCUDA && c.is_contiguous());
+    TORCH_CHECK(c.dim() == 2 && c.size(0) >= n && c.size(1) >= cols);
+    TORCH_CHECK(c.get_device() == dev);
+    comp = c;
+  } else {
+    comp = at::empty({n, cols}, like.options().dtype(at::kByte));
+  }
+  at::Tensor sizes;
+  if (outSizes) {
+    const auto& s = *outSizes;
+    TORCH_CHECK(s.scalar_type() == at::kInt && s.device().type() == at::kCUDA && s.dim() == 1);
+    TORCH_CHECK(s.is_contiguous() && s.size(0) >= n && s.get_device() == dev);
+    sizes = s;
+  } else {
+    sizes = at::empty({n}, like.options().dtype(at::kInt));
+  }
+  return {comp, sizes};
+}
+
+// Row i of `matrix` narrowed to its archive's size (host sizes h, checked).
+std::vector<at::Tensor> narrowRows(const at::Tensor& matrix, const int32_t* h, int64_t n, bool clone) {
+  checkArchiveSizes(h, n);
+  const at::Tensor flat = matrix.view({-1});
+  const int64_t cols = matrix.size(1);
+  std::vector<at::Tensor> out;
+  out.reserve(size_t(n));
+  for (int64_t i = 0; i < n; ++i) {
+    const at::Tensor row = flat.narrow(0, i * cols, h[i]);
+    out.push_back(clone ? row.clone() : row);
+  }
+  return out;
+}
+
 // compress_data_res, DietGpu.cpp:161-287
 std::tuple<at::Tensor, at::Tensor, int64_t> compressRes(bool asFloat, StackDeviceMemory& res,
                                                         const std::vector<at::Tensor>& ts, bool checksum,
@@ -159,25 +200,7 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compressRes(bool asFloat, StackDevic
     }
   }
   const auto n = int64_t(ts.size());
-  at::Tensor comp;
-  if (outCompressed) {
-    const auto& c = *outCompressed;
-    TORCH_CHECK(c.scalar_type() == at::kByte && c.device().type() == at::kCUDA && c.is_contiguous());
-    TORCH_CHECK(c.dim() == 2 && c.size(0) >= n && c.size(1) >= cols);
-    TORCH_CHECK(c.get_device() == dev);
-    comp = c;
-  } else {
-    comp = at::empty({n, cols}, ts.front().options().dtype(at::kByte));
-  }
-  at::Tensor sizes;
-  if (outSizes) {
-    const auto& s = *outSizes;
-    TORCH_CHECK(s.scalar_type() == at::kInt && s.device().type() == at::kCUDA && s.dim() == 1);
-    TORCH_CHECK(s.is_contiguous() && s.size(0) >= n && s.get_device() == dev);
-    sizes = s;
-  } else {
-    sizes = at::empty({n}, ts.front().options().dtype(at::kInt));
-  }
+  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, ts.front());
   std::vector<const void*> in(ts.size());
   std::vector<uint32_t> inSize(ts.size());
   std::vector<void*> out(ts.size());
@@ -216,14 +239,7 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data(bool asFloat, const st
 // compressedMatrixToTensors, DietGpu.cpp:84-108
 std::vector<at::Tensor> matrixToTensors(int64_t n, const at::Tensor& matrix, const at::Tensor& sizes) {
   const at::Tensor host = sizes.narrow(0, 0, n).to(at::kCPU);
-  const int32_t* h = host.data_ptr<int32_t>();
-  checkArchiveSizes(h, n);
-  const at::Tensor flat = matrix.view({-1});
-  const int64_t cols = matrix.size(1);
-  std::vector<at::Tensor> out;
-  out.reserve(size_t(n));
-  for (int64_t i = 0; i < n; ++i) out.push_back(flat.narrow(0, i * cols, h[i]));
-  return out;
+  return narrowRows(matrix, host.data_ptr<int32_t>(), n, /*clone=*/false);
 }
 
 // DietGpu.cpp:322-470
@@ -255,24 +271,7 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
     }
   }
   const int64_t cols = asFloat ? int64_t(getMaxFloatCompressedSize(ft, mx)) : int64_t(getMaxCompressedSize(mx));
-  at::Tensor comp;
-  if (outCompressed) {
-    const auto& c = *outCompressed;
-    TORCH_CHECK(c.scalar_type() == at::kByte && c.device().type() == at::kCUDA && c.is_contiguous());
-    TORCH_CHECK(c.dim() == 2 && c.size(0) >= n && c.size(1) >= cols && c.get_device() == dev);
-    comp = c;
-  } else {
-    comp = at::empty({n, cols}, tIn.options().dtype(at::kByte));
-  }
-  at::Tensor sizes;
-  if (outSizes) {
-    const auto& s = *outSizes;
-    TORCH_CHECK(s.scalar_type() == at::kInt && s.device().type() == at::kCUDA && s.dim() == 1);
-    TORCH_CHECK(s.is_contiguous() && s.size(0) >= n && s.get_device() == dev);
-    sizes = s;
-  } else {
-    sizes = at::empty({n}, tIn.options().dtype(at::kInt));
-  }
+  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, tIn);
   auto res = makeStack(dev, tempMem);
   const hipStream_t s = currentStream(dev);
   auto* osz = reinterpret_cast<uint32_t*>(sizes.data_ptr<int32_t>());
@@ -302,14 +301,7 @@ std::vector<at::Tensor> compress_data_simple(bool asFloat, const std::vector<at:
   const at::Tensor& comp = std::get<0>(out);
   const at::Tensor host = std::get<1>(out).to(at::kCPU);
   TORCH_CHECK(host.size(0) == int64_t(tsIn.size()));
-  const int32_t* h = host.data_ptr<int32_t>();
-  checkArchiveSizes(h, host.size(0));
-  const at::Tensor flat = comp.view({-1});
-  const int64_t cols = comp.size(1);
-  std::vector<at::Tensor> lst;
-  lst.reserve(tsIn.size());
-  for (int64_t i = 0; i < int64_t(tsIn.size()); ++i) lst.push_back(flat.narrow(0, i * cols, h[i]).clone());
-  return lst;
+  return narrowRows(comp, host.data_ptr<int32_t>(), host.size(0), /*clone=*/true);
 }
 
 // ----------------------------------------------------------- decompress ----

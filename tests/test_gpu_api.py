@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD, exp_bytes, float_words
+from tests.util import NP_WORD, exp_bytes, float_words, sparsify
 
 pytestmark = pytest.mark.gpu
 
@@ -138,7 +138,7 @@ def test_float_split_size_parity(C, N, ws, ft, checksum):
 def test_single_element_table_apis(C, N, ws, n, checksum):
     """One-element pointer and split-size calls: the three-kernel path gets
     stride descriptors of that element instead of an uploaded table
-    (DeviceDescs, codec.hip), for the encoder, the float checksum view and
+    (DeviceDescs, batch_tables.h), for the encoder, the float checksum view and
     the decoder's checksum verification alike.  The element sits at a 2-byte
     offset (not 16 B-aligned: always the three-kernel path) and, for the
     float codecs, in every float type; archives equal the oracle's, roundtrips
@@ -393,6 +393,46 @@ def test_graph_capture_replay(C):
             ref = O.float_compress(w[i * n:(i + 1) * n], 2)
             assert got[i] == ref.size
             np.testing.assert_array_equal(arch[i, :ref.size].cpu().numpy(), ref)
+
+
+def test_graph_capture_replay_sparse(C):
+    """A one-element sparse compress + decompress captured in a hipGraph and
+    replayed with new data.  5,000 fp32 words at about 50 % zeros are one item
+    of the size rule, so the dense codec takes the three-kernel path and the
+    sparse compressor counts the list's histogram in a sync-arena lease
+    (sparseCompressT, sparse.hip); under capture that lease is workspace
+    memory and has to be released in stack order.  No upload and no host sync:
+    every replay's archive equals the oracle's, the roundtrip is exact."""
+    n = 5000
+    ws = C.Workspace(64 << 20)
+    x = torch.empty([n], dtype=torch.float32, device=DEV)
+    y = torch.empty_like(x)
+
+    def load(seed):
+        w = sparsify(float_words(3, n, seed=seed), 0.5, seed=seed)
+        x.copy_(torch.from_numpy(w.view(np.int32)).view(torch.float32))
+        return w
+
+    load(1)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):  # warm-up outside the capture
+        arch, sizes = C.sparse_compress([x], ws=ws)
+        C.sparse_decompress([arch[0]], [y], ws=ws)
+    stream.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=stream):
+        arch, sizes = C.sparse_compress([x], ws=ws)
+        ok, dsz = C.sparse_decompress([arch[0]], [y], ws=ws)
+    for rep in range(3):
+        w = load(100 + rep)
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        ref = O.sparse_compress(w, 3)
+        assert int(sizes[0]) == ref.size, f"replay {rep}"
+        np.testing.assert_array_equal(arch[0, :ref.size].cpu().numpy(), ref, err_msg=f"replay {rep}")
+        assert ok.cpu().tolist() == [1] and dsz.cpu().tolist() == [n]
+        assert torch.equal(y.view(torch.int32), x.view(torch.int32)), f"replay {rep}"
 
 
 @pytest.mark.parametrize("path", ["auto", "single-pass", "three-kernel"])

@@ -1,8 +1,9 @@
-"""GPU parity of the two compression paths (csrc/codec.hip encodeBatchDevice):
-the single-pass k_pcompress (teams of at most pc::kMaxTeam = 32 workgroups,
-i.e. elements of at most 1 MiB of ANS symbols) and the three-kernel
-k_hist -> k_encode path (k_normalize / k_histReduce, or the encoder's
-prologue normalisation) taken otherwise.  Both must write the
+"""GPU parity of the two compression paths encodeBatchDevice (csrc/codec.hip)
+selects between: the single-pass k_pcompress (compressPersistent: teams of at
+most pc::kMaxTeam = 32 workgroups, i.e. elements of at most 1 MiB of ANS
+symbols) and the three-kernel k_hist -> k_encode path (compressThreeKernel:
+k_normalize / k_histReduce, or the encoder's prologue normalisation) taken
+otherwise.  Both must write the
 oracle's archive byte for byte, including dense blocks whose output spills
 out of the 1024-word LDS rings and blocks that emit no words."""
 import numpy as np

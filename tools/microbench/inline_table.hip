@@ -36,7 +36,7 @@ int main() {
     B[i] = 0x7ff0fff00000ull + 8192ull * i + 16;
     S[i] = 1000 + 3 * i;
   }
-  // same packing as codec.hip uploadTables: [8 B bias] A | B | S
+  // same packing as batch_tables.h uploadTables: [8 B bias] A | B | S
   InlineTable* t = new InlineTable();
   uint8_t* w = reinterpret_cast<uint8_t*>(t->w);
   std::memcpy(w + 8, A.data(), nb * 8);
