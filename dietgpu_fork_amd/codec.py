@@ -256,6 +256,90 @@ def float_decompress_pointer(archives, outs, ft=None, prob_bits=10, checksum=Fal
     return ok, sz
 
 
+# ---------------------------------------------------------------- range ----
+
+def _range_launch(fn, head, dev, nb, in_ptrs, firsts, counts, out_ptrs, ws):
+    """The C-ABI call on host arrays (ctypes arrays or array addresses)."""
+    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
+    sz = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    N.check(fn(ws.h, *head, nb, in_ptrs, firsts, counts, out_ptrs, ok.data_ptr(), sz.data_ptr(), _s()))
+    return ok, sz
+
+
+def _range_call(fn, head, archives, firsts, counts, outs, ws):
+    nb = len(archives)
+    if not (len(firsts) == len(counts) == len(outs) == nb):
+        raise ValueError("archives, firsts, counts and outs must have one entry per member")
+    for v in list(firsts) + list(counts):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"range bound {int(v)} is outside [0, 2^32)")
+    for o, c in zip(outs, counts):
+        if o.numel() < int(c) or not o.is_contiguous():
+            raise ValueError("every out must be contiguous and hold its count")
+    ok, sz = _range_launch(fn, head, archives[0].device, nb, N.ptr_array([a.data_ptr() for a in archives]),
+                           N.u32_array([int(f) for f in firsts]), N.u32_array([int(c) for c in counts]),
+                           N.ptr_array([o.data_ptr() for o in outs]), ws)
+    return outs, ok, sz
+
+
+def ans_decode_range(archives, firsts, counts, outs=None, prob_bits=10, ws=None):
+    """Bytes [firsts[i], firsts[i] + counts[i]) of the element each byte
+    archive encodes, into outs[i] (uint8 CUDA tensors of at least counts[i]
+    bytes; allocated when None) -> (outs, ok, sz).  An archive may appear in
+    any number of members."""
+    if outs is None:
+        outs = [torch.empty([int(c)], dtype=torch.uint8, device=archives[0].device) for c in counts]
+    return _range_call(N.lib().dietgpu_ans_decode_batch_range, (prob_bits,), archives, firsts, counts,
+                       outs, ws)
+
+
+def float_decompress_range(archives, firsts, counts, outs=None, dtype=None, prob_bits=10, ws=None):
+    """Float words [firsts[i], firsts[i] + counts[i]) of each dense float
+    archive into outs[i] -> (outs, ok, sz).  dtype: the archives' float type
+    (default: that of outs[0]); sparse archives are not supported."""
+    if outs is None:
+        outs = [torch.empty([int(c)], dtype=dtype, device=archives[0].device) for c in counts]
+    ft = FLOAT_TYPE[dtype if dtype is not None else outs[0].dtype]
+    return _range_call(N.lib().dietgpu_float_decompress_range, (ft, prob_bits), archives, firsts,
+                       counts, outs, ws)
+
+
+def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None):
+    """Rows `rows` (a list or CPU tensor of row indices, repeats allowed) of a
+    [R, row_words] table stored as one archive, into one [len(rows),
+    row_words] tensor: one batched range decode whose members all read
+    `archive`.  dtype torch.uint8 reads a byte archive.  Returns the tensor;
+    reads the status back (a host synchronisation) and raises if any row
+    lies outside the table."""
+    import numpy as np
+
+    rows = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int64).reshape(-1)
+    nb = int(rows.size)
+    out = out if out is not None else torch.empty([nb, row_words], dtype=dtype, device=archive.device)
+    if not (out.is_contiguous() and tuple(out.shape) == (nb, row_words) and out.dtype == dtype):
+        raise ValueError("out must be a contiguous [len(rows), row_words] tensor of dtype")
+    if nb == 0 or row_words == 0:
+        return out
+    if int(rows.min()) < 0 or (int(rows.max()) + 1) * row_words > 1 << 32:
+        raise N.DietGpuError("gather_rows: a row lies outside the table")
+    # the host arrays of the call, built without a Python loop over the rows
+    firsts = (rows * row_words).astype(np.uint32)
+    counts = np.full(nb, row_words, dtype=np.uint32)
+    in_ptrs = np.full(nb, archive.data_ptr(), dtype=np.uint64)
+    out_ptrs = np.uint64(out.data_ptr()) + np.arange(nb, dtype=np.uint64) * np.uint64(row_words * out.element_size())
+    if dtype == torch.uint8:
+        fn, head = N.lib().dietgpu_ans_decode_batch_range, (prob_bits,)
+    else:
+        fn, head = N.lib().dietgpu_float_decompress_range, (FLOAT_TYPE[dtype], prob_bits)
+    ok, _ = _range_launch(fn, head, archive.device, nb, in_ptrs.ctypes.data, firsts.ctypes.data,
+                          counts.ctypes.data, out_ptrs.ctypes.data, ws)
+    if not bool(ok.all()):
+        raise N.DietGpuError("gather_rows: a row lies outside the table, or the archive does not "
+                             "match dtype / prob_bits")
+    return out
+
+
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
     nb = len(ts)

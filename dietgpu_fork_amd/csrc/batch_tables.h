@@ -29,6 +29,7 @@ struct DeviceTables {
   bool inl = false;
   std::vector<const uint64_t*> u64;  // the u64 columns, in the order given
   const uint32_t* u32 = nullptr;     // the u32 column that follows them
+  const uint32_t* u32b = nullptr;    // the second u32 column (range decode: `first`), if given
 
   // mark the table-backed fields of a descriptor built from u64 / u32
   BatchDesc tag(BatchDesc d) const {
@@ -47,12 +48,13 @@ inline const InlineTable& kernargTable(const DeviceTables* t) {
 }
 
 // One table of the u64 columns `cols` followed by the u32 column `last`
-// (either may be empty).
+// (either may be empty) and, if given, a second u32 column `last2`.
 inline DeviceTables uploadTables(StackDeviceMemory& res, hipStream_t s,
                                  std::initializer_list<const std::vector<uint64_t>*> cols,
-                                 const std::vector<uint32_t>& last, bool allowInline = false) {
+                                 const std::vector<uint32_t>& last, bool allowInline = false,
+                                 const std::vector<uint32_t>* last2 = nullptr) {
   DeviceTables t;
-  size_t bytes = last.size() * 4;
+  size_t bytes = last.size() * 4 + (last2 ? last2->size() * 4 : 0);
   for (const auto* c : cols) bytes += c->size() * 8;
   t.host.resize(bytes);
   size_t off = 0;  // column offsets now, addresses once the base is known
@@ -62,6 +64,8 @@ inline DeviceTables uploadTables(StackDeviceMemory& res, hipStream_t s,
     off += c->size() * 8;
   }
   if (!last.empty()) std::memcpy(t.host.data() + off, last.data(), last.size() * 4);
+  const size_t off2 = off + last.size() * 4;
+  if (last2 && !last2->empty()) std::memcpy(t.host.data() + off2, last2->data(), last2->size() * 4);
   t.inl = allowInline && kInlineBias + bytes <= sizeof(InlineTable);
   uintptr_t base;
   if (t.inl) {
@@ -75,6 +79,7 @@ inline DeviceTables uploadTables(StackDeviceMemory& res, hipStream_t s,
   }
   for (auto& p : t.u64) p = reinterpret_cast<const uint64_t*>(base + reinterpret_cast<uintptr_t>(p));
   t.u32 = reinterpret_cast<const uint32_t*>(base + off);
+  if (last2) t.u32b = reinterpret_cast<const uint32_t*>(base + off2);
   return t;
 }
 

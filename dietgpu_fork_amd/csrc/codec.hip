@@ -477,6 +477,29 @@ void decodeBatchDevice(const DecodeCall& c) {
   launch(std::integral_constant<int, 0>{}, std::false_type{});
 }
 
+// Range decode: words [first, first + count) of archive b
+// into c.out, where first = c.in.size(b) (the `first` table rides as the size
+// column of the input descriptor, which the full decode leaves empty) and
+// count = c.out.size(b).  maxRangeBlocks: the most 4096-word blocks any
+// member's range touches.  One chunk of 8 blocks per workgroup, as
+// capacityOnly: ranges are short, so the chunks run side by side; no
+// remaining-work priorities.  Plain (not streaming) stores: a range is read
+// right after it is fetched, and its edge rows are partial cache lines.
+template <int FT>
+void decodeRangeBatchDevice(const DecodeCall& c, uint32_t maxRangeBlocks) {
+  checkProbBits(c.pb);
+  if (c.nb == 0) return;
+  using Cfg = DecCfg<FT, 0>;
+  const uint32_t lds = Cfg::ldsBytes(c.pb);
+  forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
+    prof::Scope p("decode_range", c.s);
+    dim3 g(std::max(1u, divUp(maxRangeBlocks, uint32_t(Cfg::kBlocksPerWG))), ny);
+    k_decode<FT, 0, false, false, true><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
+                                                                      1u, c.outSuccess_dev, c.outSize_dev);
+    HIP_LAUNCH_CHECK();
+  });
+}
+
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
 // (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112; the float
 // codec checksums `capacity` bytes, float words treated as bytes).  Host sync.
@@ -566,6 +589,31 @@ static BatchTables splitBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb
   }
   b.maxSize = sc.maxSize;
   b.inAligned16 = reinterpret_cast<uintptr_t>(base) % 16 == 0 && sc.aligned16;
+  return b;
+}
+
+// Range decode: words [first[i], first[i] + count[i]) of in[i] -> out[i].
+// The `first` column becomes the input descriptor's size column.
+static BatchTables rangeBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void** in,
+                              const uint32_t* first, const uint32_t* count, void** out, uint32_t unit) {
+  const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
+  for (uint32_t i = 0; i < nb; ++i) {
+    DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
+    // (the decoder reads the headers with scalar loads, which drop the low
+    // two address bits)
+    DG_CHECK(ip[i] % 4 == 0, "archive " << i << " must be 4-byte aligned");
+  }
+  const SizeColumn cnt(count, nb), fst(first, nb);
+  BatchTables b;
+  b.t = uploadTables(res, s, {&ip, &op}, cnt.sizes, true, &fst.sizes);
+  b.in = b.t.tag(BatchDesc::pointers(b.t.u64[0], b.t.u32b));
+  b.out = b.t.tag(BatchDesc::pointers(b.t.u64[1], b.t.u32));
+  // maxSize: the most blocks a range touches (a range past its element's end
+  // fails on the device, where the element's size is known)
+  for (uint32_t i = 0; i < nb; ++i) {
+    const uint64_t end = uint64_t(first[i]) + count[i];
+    b.maxSize = std::max(b.maxSize, uint32_t((end + kBlockSize - 1) / kBlockSize - first[i] / kBlockSize));
+  }
   return b;
 }
 
@@ -708,6 +756,17 @@ ANSDecodeStatus ansDecodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecCo
   return ansDecodeCommon(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
 }
 
+void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config, uint32_t numInBatch,
+                         const void** in, const uint32_t* first, const uint32_t* count, void** out,
+                         uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  if (numInBatch == 0) return;
+  const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, 1);
+  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
+  c.pb = config.probBits;
+  decodeRangeBatchDevice<0>(c, b.maxSize);
+}
+
 // k_info over a device array of archive addresses (the byte codec has no
 // type word)
 static void launchInfo(const void** in_dev, uint32_t nb, bool isFloat, uint32_t* outSizes_dev,
@@ -833,6 +892,19 @@ FloatDecompressStatus floatDecompress(StackDeviceMemory& res, const FloatDecompr
   const auto b =
       pointerBatch(res, stream, numInBatch, in, out, outCapacity, false, floatWordBytes(int(config.floatType)));
   return floatDecompressDescs(config, decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
+}
+
+void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,
+                          const void** in, const uint32_t* first, const uint32_t* count, void** out,
+                          uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  checkFloatConfig(config);
+  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  if (numInBatch == 0) return;
+  const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, floatWordBytes(int(config.floatType)));
+  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
+  c.pb = config.ansConfig.probBits;
+  dispatchFloatType(config.floatType,
+                    [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, b.maxSize); });
 }
 
 FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,

@@ -25,6 +25,8 @@
 //  * 8-step segments are unrolled (constant LDS offsets); each lane joins 8
 //    words of the segment with their raw float bytes (loaded a segment
 //    earlier) and writes them with 16 B stores.
+//  * The same kernel body decodes a word range of an element (RNG, DESIGN.md
+//    5.2b): only the blocks the range touches, masked at the range's edges.
 #pragma once
 
 #include <type_traits>
@@ -364,7 +366,16 @@ __device__ __forceinline__ void buildLut64(gp<const uint16_t> pdfIn, lp<u32x2> l
 // of 77-180, their single-generation grids (sized by the API's answer) ran a
 // second generation.  (fp64, VGPR-bound at four workgroups per CU, spills a
 // few SGPRs to VGPR lanes instead: its decode time is unchanged.)
-template <int FT, int KK, bool NT, bool BAL>
+// RNG: range decode: words [first, first + count) of element
+// b, first = in.size(b), count = out.size(b), go to out[0 .. count).  The grid
+// covers blocks [first / 4096, divUp(first + count, 4096)) only: workgroup x
+// takes the 8 blocks from the range's first block + 8 x, each wave a pair.  A
+// block is decoded from its top down to the lowest segment the range needs
+// (the state chain runs through the segments above the range; those below
+// it are never reached).  Chunks of 8 words wholly inside the range whose
+// destination is 16 B-aligned take the vector join, every other chunk the
+// masked scalar one: nothing outside out[0 .. count) is written.
+template <int FT, int KK, bool NT, bool BAL, bool RNG = false>
 __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(4))) void k_decode(const InlineTable,
                                                           BatchDesc in, BatchDesc out,
                                                           uint32_t batchOffset, int pb,
@@ -403,13 +414,34 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
     gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
     ok = ok && ah[0] == kANSMagicVersion && (ah[4] & 0xfu) == uint32_t(pb) && ah[2] == n;
   }
-  const bool success = ok && out.size(b) >= n;
-  if (blockIdx.x == 0 && tid == 0) {
-    if (outSuccess) outSuccess[b] = success ? 1 : 0;
-    if (outSize) outSize[b] = ok ? n : 0u;
+  // range form: words [rlo, rhi) of the element, blocks [blkFirst, blkEnd)
+  uint32_t rlo = 0, rhi = 0;
+  bool success;
+  if constexpr (RNG) {
+    static_assert(K == 1 && !BAL, "range decode: one block pair per wave, no priorities");
+    rlo = in.size(b);
+    const uint32_t count = out.size(b);
+    success = ok && rlo <= n && count <= n - rlo;
+    rhi = success ? rlo + count : rlo;
+    if (blockIdx.x == 0 && tid == 0) {
+      if (outSuccess) outSuccess[b] = success ? 1 : 0;
+      if (outSize) outSize[b] = success ? count : 0u;
+    }
+  } else {
+    success = ok && out.size(b) >= n;
+    if (blockIdx.x == 0 && tid == 0) {
+      if (outSuccess) outSuccess[b] = success ? 1 : 0;
+      if (outSize) outSize[b] = ok ? n : 0u;
+    }
   }
   const uint32_t nBlocks = divUp(n, kBlockSize);
-  if (!success || blockIdx.x * chunksPerWG * Cfg::kBlocksPerWG >= nBlocks) return;
+  const uint32_t blkFirst = RNG ? rlo / kBlockSize : 0u;
+  const uint32_t blkEnd = RNG ? divUp(rhi, kBlockSize) : nBlocks;
+  if constexpr (RNG) {
+    if (!success || rhi == rlo || blkFirst + blockIdx.x * chunksPerWG * Cfg::kBlocksPerWG >= blkEnd) return;
+  } else {
+    if (!success || blockIdx.x * chunksPerWG * Cfg::kBlocksPerWG >= nBlocks) return;
+  }
 
   const uint32_t w = readfirst(tid >> 6), lane = tid & 63, l = lane & 31;
   uint32_t hv = lane >= 32 ? ~0u : 0u;
@@ -417,7 +449,15 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 
   const bool vecIn = (reinterpret_cast<uintptr_t>(base) & 15) == 0;
   gp<uint8_t> outB = startOf(out, b);
+  // range form: outB is where word 0 of the element would lie, so that word
+  // i goes to outB[i] as in the full decode (only [rlo, rhi) is written)
+  if constexpr (RNG)
+    outB = (gp<uint8_t>)(reinterpret_cast<uintptr_t>(outB) - uint64_t(rlo) * sizeof(WordT));
   const bool vecOut = (reinterpret_cast<uintptr_t>(outB) & 15) == 0;
+  // whether the 8-word chunk at word i0 is joined as a vector
+  auto wholeInRange = [&](uint32_t i0) __attribute__((always_inline)) {
+    return !RNG || (i0 >= rlo && i0 + dec::kChunk <= rhi);
+  };
   gp<const uint8_t> raw = base + 32;
   const uint32_t mask = (1u << pb) - 1;
   lp<const u32x2> lut[S];
@@ -442,27 +482,27 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
       const uint32_t bkMine = blk0 + 2 * c + (lane >> 5);
       // the first segment decoded is the block pair's top one; full (and so
       // loadable unmasked) when both blocks of every pair are whole
-      const uint32_t uwMin = min(blk0 + 2 * c + 1 < nBlocks ? min(kBlockSize, n - (blk0 + 2 * c + 1) * kBlockSize) : 0u,
-                                 blk0 + 2 * c < nBlocks ? min(kBlockSize, n - (blk0 + 2 * c) * kBlockSize) : 0u);
-      if (FT != 0 && vecIO && uwMin == kBlockSize)
-        Join<FT>::load(rvA[c], raw, n, bkMine * kBlockSize + (kBlockSize / 32 / dec::kSegSteps - 1) * dec::kSegWords + off);
+      const uint32_t uwMin = min(blk0 + 2 * c + 1 < blkEnd ? min(kBlockSize, n - (blk0 + 2 * c + 1) * kBlockSize) : 0u,
+                                 blk0 + 2 * c < blkEnd ? min(kBlockSize, n - (blk0 + 2 * c) * kBlockSize) : 0u);
+      const uint32_t iTop = bkMine * kBlockSize + (kBlockSize / 32 / dec::kSegSteps - 1) * dec::kSegWords + off;
+      if (FT != 0 && vecIO && uwMin == kBlockSize && wholeInRange(iTop)) Join<FT>::load(rvA[c], raw, n, iTop);
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         gp<const uint8_t> states = arch[s] + kANSHeaderBytes + kPdfBytes;
         gp<const uint2> bw = (gp<const uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks);
-        x0[c][s] = bkMine < nBlocks ? ((gp<const uint32_t>)(states + uint64_t(kStateBytesPerBlock) * bkMine))[l]
+        x0[c][s] = bkMine < blkEnd ? ((gp<const uint32_t>)(states + uint64_t(kStateBytesPerBlock) * bkMine))[l]
                                     : kMinState;
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           const uint32_t bk = blk0 + 2 * c + hh;
-          bwE[c][s][hh] = bk < nBlocks ? ld8(bw + bk) : make_uint2(0, 0);
+          bwE[c][s][hh] = bk < blkEnd ? ld8(bw + bk) : make_uint2(0, 0);
         }
       }
     }
   };
   {
-    const uint32_t blk00 = blockIdx.x * chunksPerWG * Cfg::kBlocksPerWG + w * Cfg::kBlocksPerWave;
-    if (blk00 < nBlocks) issue(blk00);
+    const uint32_t blk00 = blkFirst + blockIdx.x * chunksPerWG * Cfg::kBlocksPerWG + w * Cfg::kBlocksPerWave;
+    if (blk00 < blkEnd) issue(blk00);
   }
 #pragma unroll
   for (int s = 0; s < S; ++s) {
@@ -474,8 +514,9 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   // Persistent over chunksPerWG consecutive chunks of this element (the grid
   // is one generation of resident workgroups; one table build per WG).
   for (uint32_t pass = 0; pass < chunksPerWG; ++pass) {
-    const uint32_t blk0 = (blockIdx.x * chunksPerWG + pass) * Cfg::kBlocksPerWG + w * Cfg::kBlocksPerWave;
-    if (blk0 >= nBlocks) break;
+    const uint32_t blk0 =
+        blkFirst + (blockIdx.x * chunksPerWG + pass) * Cfg::kBlocksPerWG + w * Cfg::kBlocksPerWave;
+    if (blk0 >= blkEnd) break;
     if (pass > 0) issue(blk0);
 
     // per pair c: blocks blk0 + 2c (lanes 0-31) and blk0 + 2c + 1 (lanes 32-63)
@@ -487,8 +528,16 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         const uint32_t bk = blk0 + 2 * c + hh;
-        uwH[c][hh] = bk < nBlocks ? min(kBlockSize, n - bk * kBlockSize) : 0u;
+        uwH[c][hh] = bk < blkEnd ? min(kBlockSize, n - bk * kBlockSize) : 0u;
       }
+    // range form: the lowest segment decoded.  Above 0 only for the pair whose
+    // one block holds the whole range (any other pair has a block that the
+    // range enters from below, so its segment 0 is needed); that pair has no
+    // second block, so all of its segments are partial ones (nFull = 0).
+    int32_t gMin = 0;
+    if constexpr (RNG) {
+      if (blk0 == blkFirst && blk0 + 1 >= blkEnd) gMin = int32_t((rlo - blkFirst * kBlockSize) / dec::kSegWords);
+    }
     uint32_t T = 0;
 #pragma unroll
     for (int c = 0; c < K; ++c) T = max(T, max(divUp(uwH[c][0], 32), divUp(uwH[c][1], 32)));
@@ -520,7 +569,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
           d.lo[hh] = 0;
           d.data[hh] = data;
           d.pf[hh] = u32x2{0, 0};
-          if (bk < nBlocks) {
+          if (bk < blkEnd) {
             const uint2 e = bwE[c][s][hh];
             const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
             const int32_t cw = int32_t(ex & 0xffffu);
@@ -569,7 +618,8 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         for (int c = 0; c < K; ++c) {
           const uint32_t uw = lane >= 32 ? uwH[c][1] : uwH[c][0];
           const uint32_t bk = blk0 + 2 * c + (lane >> 5);
-          if (FT != 0 && kVec && (fullSeg || segW0 + off + dec::kChunk <= uw))
+          if (FT != 0 && kVec && (fullSeg || segW0 + off + dec::kChunk <= uw) &&
+              wholeInRange(bk * kBlockSize + segW0 + off))
             Join<FT>::load(rv[c], raw, n, bk * kBlockSize + segW0 + off);
         }
       };
@@ -582,9 +632,16 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
           if (!fullSeg && segW0 + off >= uw) continue;
           const uint32_t cnt = fullSeg ? dec::kChunk : min(dec::kChunk, uw - segW0 - off);
           const uint32_t i0 = bk * kBlockSize + segW0 + off;
+          // range form: words [k0, k1) of the chunk lie in the range
+          uint32_t k0 = 0, k1 = cnt;
+          if constexpr (RNG) {
+            k0 = i0 < rlo ? min(cnt, rlo - i0) : 0u;
+            k1 = rhi > i0 ? min(cnt, rhi - i0) : 0u;
+            if (k0 >= k1) continue;
+          }
           lp<const uint16_t> q0 = segLane[c][0] - l + off;
           lp<const uint16_t> q1 = segLane[c][S - 1] - l + off;
-          if (kVec && cnt == dec::kChunk) {
+          if (kVec && cnt == dec::kChunk && wholeInRange(i0)) {
             uint32_t sv[4], sv1[4];
             const u32x4 a0 = *(lp<const u32x4>)q0;
             sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
@@ -598,7 +655,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
             Join<FT>::template vec<NT>(outB, i0, sv, sv1, rv[c]);
           } else {
             gp<WordT> o = (gp<WordT>)outB;
-            for (uint32_t k = 0; k < cnt; ++k)
+            for (uint32_t k = k0; k < k1; ++k)
               o[i0 + k] = Join<FT>::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
           }
         }
@@ -610,7 +667,8 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
       // (constant LDS offsets, the ring checked every kUnroll steps); steps
       // past a block's end are no-ops of the masked step.  A per-step loop
       // here cost such pairs 7-8 us (1 x 4096 words: decode 33.6 -> 25.7 us)
-      for (int32_t g = nSeg - 1; g >= int32_t(nFull); --g) {
+      const int32_t gStop = RNG ? max(int32_t(nFull), gMin) : int32_t(nFull);
+      for (int32_t g = nSeg - 1; g >= gStop; --g) {
         const int32_t tBot = g * int32_t(dec::kSegSteps);
 #pragma unroll
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
@@ -641,7 +699,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         __builtin_amdgcn_wave_barrier();
         join(g, false, rvA);
         __builtin_amdgcn_wave_barrier();
-        if (g > 0) loadRaw(g - 1, uint32_t(g - 1) < nFull, rvA);
+        if (g > gMin) loadRaw(g - 1, uint32_t(g - 1) < nFull, rvA);
       }
       // full segments: unrolled, unmasked
       auto fullSeg = [&](int32_t g, const uint32_t (&cur)[K][R], uint32_t (&nxt)[K][R]) {

@@ -15,6 +15,7 @@
 
 #include "capi_internal.h"
 #include "common.h"
+#include "dietgpu/GpuFloatCodec.h"
 #include "dietgpu/StackDeviceMemory.h"
 #include "dietgpu_testhooks.h"
 #include "encode.h"
@@ -121,6 +122,25 @@ int dietgpu_test_histogram(dietgpu_stack* res, uint32_t nb, const void* in_dev, 
   return guardedTest([&] {
     DG_CHECK(res && res->mem, "null dietgpu_stack");
     dietgpu::testHistogram(*res->mem, reinterpret_cast<hipStream_t>(stream), nb, in_dev, size, stride, hist_dev);
+  });
+}
+
+int dietgpu_test_range_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                              uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
+                              uint32_t* out_size_dev, void* stream) {
+  return guardedTest([&] {
+    using namespace dietgpu;
+    DG_CHECK(res && res->mem, "null dietgpu_stack");
+    DG_CHECK(float_type >= 0 && float_type <= 4, "float_type must be 0..4");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (float_type == 0) {
+      ansDecodeBatchRange(*res->mem, ANSCodecConfig(kANSDefaultProbBits, use_checksum != 0), 1, &in, &first,
+                          &count, &out, out_success_dev, out_size_dev, s);
+    } else {
+      const FloatDecompressConfig cfg(FloatType(float_type), ANSCodecConfig(kANSDefaultProbBits), false,
+                                      use_checksum != 0);
+      floatDecompressRange(*res->mem, cfg, 1, &in, &first, &count, &out, out_success_dev, out_size_dev, s);
+    }
   });
 }
 

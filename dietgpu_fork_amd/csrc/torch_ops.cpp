@@ -11,7 +11,9 @@
 // too (the reference rejects them at DietGpu.cpp:569-573 / 742-746 although
 // its compressor produces them), and an archive the compressor had to abandon
 // (outSize 0, see dietgpu_device_error_count in include/dietgpu_c.h) raises
-// instead of being returned as an empty tensor.
+// instead of being returned as an empty tensor.  An eleventh operator,
+// decompress_data_range, is not in the reference at all: it decodes a word
+// range of each archive (floatDecompressRange / ansDecodeBatchRange).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -382,6 +384,59 @@ int64_t decompress_data(bool asFloat, const std::vector<at::Tensor>& tsIn, const
   return decompressRes(asFloat, res, tsIn, tsOut, checksum, status, sizes);
 }
 
+// Extension (no reference counterpart): words [t_first[i], t_first[i] +
+// ts_out[i].numel()) of archive ts_in[i] into ts_out[i] (bytes of the element
+// when !asFloat: the range is then first byte + ts_out[i]'s size in bytes).
+int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
+                              const std::vector<at::Tensor>& tsOut, const at::Tensor& tFirst,
+                              const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
+                              const std::optional<at::Tensor>& sizes) {
+  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size());
+  const int dev = tsIn.front().get_device();
+  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  c10::hip::HIPGuard guard(dev);
+  TORCH_CHECK(tFirst.is_contiguous() && tFirst.device().type() == at::kCPU && tFirst.scalar_type() == at::kLong,
+              "t_first must be a contiguous CPU int64 tensor");
+  TORCH_CHECK(tFirst.numel() == int64_t(tsIn.size()), "one t_first entry per compressed input");
+  const int64_t* fp = tFirst.data_ptr<int64_t>();
+  std::vector<const void*> in(tsIn.size());
+  std::vector<void*> out(tsIn.size());
+  std::vector<uint32_t> first(tsIn.size()), count(tsIn.size());
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    const auto& ti = tsIn[i];
+    const auto& to = tsOut[i];
+    TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous());
+    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous());
+    TORCH_CHECK(ti.scalar_type() == at::kByte, "compressed inputs must be uint8");
+    if (asFloat) {
+      checkOutDtype(to);
+      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs must share a dtype");
+    }
+    const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
+    TORCH_CHECK(c <= kU32Max);
+    TORCH_CHECK(fp[i] >= 0 && uint64_t(fp[i]) <= kU32Max, "t_first[", i, "] = ", fp[i], " is outside [0, 2^32)");
+    in[i] = ti.data_ptr();
+    out[i] = to.data_ptr();
+    first[i] = uint32_t(fp[i]);
+    count[i] = uint32_t(c);
+  }
+  checkStatusTensors(status, sizes, int64_t(tsIn.size()), dev);
+  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
+  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
+  auto res = makeStack(dev, tempMem);
+  const hipStream_t s = currentStream(dev);
+  if (asFloat) {
+    const FloatDecompressConfig cfg(floatTypeOf(tsOut.front().scalar_type()), ANSCodecConfig(kDefaultPrecision),
+                                    false, false);
+    floatDecompressRange(res, cfg, uint32_t(tsIn.size()), in.data(), first.data(), count.data(), out.data(), st, sz,
+                         s);
+  } else {
+    ansDecodeBatchRange(res, ANSCodecConfig(kDefaultPrecision, false), uint32_t(tsIn.size()), in.data(),
+                        first.data(), count.data(), out.data(), st, sz, s);
+  }
+  return int64_t(res.getMaxMemoryUsage());
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -497,6 +552,10 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "decompress_data_simple(bool compress_as_float, Tensor[] ts_in, bool checksum=False, int? temp_mem=67108864) "
       "-> Tensor[]");
+  // extension: not one of the reference's ten operators
+  m.def(
+      "decompress_data_range(bool compress_as_float, Tensor[] ts_in, Tensor[] ts_out, Tensor t_first, Tensor? "
+      "temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -510,4 +569,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("decompress_data", &dietgpu::decompress_data);
   m.impl("decompress_data_split_size", &dietgpu::decompress_data_split_size);
   m.impl("decompress_data_simple", &dietgpu::decompress_data_simple);
+  m.impl("decompress_data_range", &dietgpu::decompress_data_range);
 }

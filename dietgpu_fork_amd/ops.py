@@ -3,8 +3,10 @@
 The operators are native: ``TORCH_LIBRARY(dietgpu)`` in
 ``csrc/torch_ops.cpp``, built into ``_lib/libdietgpu_torch.so`` and loaded
 with ``torch.ops.load_library`` exactly as the reference's harnesses load its
-``DietGpu.cpp`` extension (dietgpu/DietGpu.cpp:921-978: same ten operators,
-schemas, validation and return values).  This module only loads that library
+``DietGpu.cpp`` extension (dietgpu/DietGpu.cpp:921-978: its ten operators
+with the same schemas, validation and return values).  An eleventh,
+``decompress_data_range``, is an extension the reference does not have: it
+decodes a word range of each archive.  This module only loads that library
 and forwards ``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.
 """
 import os
@@ -26,6 +28,8 @@ OPS = (
     "decompress_data",
     "decompress_data_split_size",
     "decompress_data_simple",
+    # extension (not in the reference)
+    "decompress_data_range",
 )
 
 _LOADED = False

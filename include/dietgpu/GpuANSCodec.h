@@ -100,4 +100,19 @@ void ansGetCompressedInfoDevice(StackDeviceMemory& res, const void** in_dev,
                                 uint32_t numInBatch, uint32_t* outSizes_dev,
                                 uint32_t* outChecksum_dev, hipStream_t stream);
 
+// ---- MI355X extension (not in the reference API) ----
+// Range decode: out[b][j] = byte first[b] + j of the element that in[b]
+// encodes, 0 <= j < count[b]; nothing else is written.  in / first / count /
+// out are host arrays; the same archive may appear in any number of members.
+// outSuccess_dev[b] = 1 iff the archive is valid for this config and
+// first[b] + count[b] does not pass its end; outSize_dev[b] = count[b] then,
+// else 0 (and out[b] is untouched).  A range cannot be checked against the
+// element's checksum: config.useChecksum must be false (archives written
+// with one decode normally).  No host synchronisation.
+void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config,
+                         uint32_t numInBatch, const void** in,
+                         const uint32_t* first, const uint32_t* count,
+                         void** out, uint8_t* outSuccess_dev,
+                         uint32_t* outSize_dev, hipStream_t stream);
+
 } // namespace dietgpu

@@ -127,4 +127,14 @@ FloatDecompressStatus floatDecompressBatchStride(
     void* out_dev, uint64_t outPerBatchStrideBytes, uint32_t outPerBatchCapacityWords,
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream);
 
+// Range decode of dense float archives (see ansDecodeBatchRange): first /
+// count in float words, out[b] word-aligned.  Sparse archives are not
+// supported (a word's position in the nonzero list needs a bitmap rank).
+void floatDecompressRange(StackDeviceMemory& res,
+                          const FloatDecompressConfig& config,
+                          uint32_t numInBatch, const void** in,
+                          const uint32_t* first, const uint32_t* count,
+                          void** out, uint8_t* outSuccess_dev,
+                          uint32_t* outSize_dev, hipStream_t stream);
+
 } // namespace dietgpu

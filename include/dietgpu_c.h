@@ -28,6 +28,9 @@
  *   dietgpu_stack_*                          utils/StackDeviceMemory.h:127-272
  * MI355X extensions (no reference counterpart; zero host->device copies):
  *   dietgpu_float_compress_batch_stride, dietgpu_float_decompress_batch_stride
+ *   dietgpu_ans_decode_batch_range, dietgpu_float_decompress_range (words
+ *   [first, first + count) of an archive; no checksum flag: a range cannot be
+ *   checked against a whole element's checksum)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -162,8 +165,23 @@ int dietgpu_float_decompress_batch_stride(dietgpu_stack* res, int float_type, in
                                           uint8_t* out_success_dev, uint32_t* out_size_dev,
                                           void* stream);
 
+/* Range decode: out[b][j] = word first[b] + j of the element in[b] encodes,
+ * 0 <= j < count[b] (bytes for the byte codec, float words for the float
+ * codec); nothing else is written.  in / first / count / out are host arrays;
+ * an archive may appear in any number of members (a row gather).
+ * out_success_dev[b] = 1 iff the archive is valid and the range lies inside
+ * the element; out_size_dev[b] = count[b] then, else 0. */
+int dietgpu_ans_decode_batch_range(dietgpu_stack* res, int prob_bits, uint32_t num_in_batch,
+                                   const void** in, const uint32_t* first, const uint32_t* count,
+                                   void** out, uint8_t* out_success_dev, uint32_t* out_size_dev,
+                                   void* stream);
+int dietgpu_float_decompress_range(dietgpu_stack* res, int float_type, int prob_bits,
+                                   uint32_t num_in_batch, const void** in, const uint32_t* first,
+                                   const uint32_t* count, void** out, uint8_t* out_success_dev,
+                                   uint32_t* out_size_dev, void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
- * named kernel family ("encode", "decode", "hist", "coalesce") is bracketed
+ * named kernel family ("encode", "decode", "decode_range", "hist", "coalesce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);

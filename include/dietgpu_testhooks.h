@@ -41,6 +41,16 @@ int dietgpu_test_histogram(dietgpu_stack* res, uint32_t nb, const void* in_dev, 
  * (ans/GpuANSEncode.cuh:63-89). */
 int dietgpu_test_enc_magic(uint32_t* magic_dev, void* stream);
 
+/* Calls the C++ range-decode entry points (floatDecompressRange,
+ * ansDecodeBatchRange) for one element with `use_checksum` set in their
+ * config (for the float codec: FloatCodecConfig.useChecksum) -- the C ABI's
+ * range entry points carry no checksum flag.  Returns what a C-ABI call would:
+ * DIETGPU_ERR_INVALID when the config is rejected (before the arguments are
+ * looked at), DIETGPU_OK after a decode.  float_type 0 = the byte codec. */
+int dietgpu_test_range_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                              uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
+                              uint32_t* out_size_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,106 @@
+"""What a range decode costs: ranges of 1 .. 1024 blocks
+starting mid-archive, and a 1024-row gather, of one 64 MiB bf16 element,
+against the full float_decompress of that element.
+
+Kernel times come from the library's event hook (profile_query of the
+"decode_range" / "decode" families), call times from a host clock around the
+call and a device synchronise.  Each figure is the median over windows of the
+mean of a window's calls; the cases alternate inside every window, so drift
+hits all of them alike.  Prints one JSON line per case and writes them to
+--out.
+
+    usage: python tools/range_decode_bench.py [--out profiles/range_decode.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+BLK = 4096
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/range_decode.json")
+    ap.add_argument("--mib", type=int, default=64)
+    ap.add_argument("--windows", type=int, default=9)
+    ap.add_argument("--calls", type=int, default=20)
+    a = ap.parse_args()
+
+    import dietgpu_fork_amd  # noqa: F401
+    from dietgpu_fork_amd import codec as C
+
+    dev = "cuda"
+    n = a.mib * (1 << 20) // 2
+    row_words, n_rows = 1024, 1024
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(n, generator=g).to(torch.bfloat16).to(dev)
+    ws = C.Workspace(256 << 20)
+    arch2d, sizes = C.float_compress_stride(x.view(1, n), ws=ws)
+    archive = arch2d[0, : int(sizes[0])]
+    full_out = torch.empty([1, n], dtype=torch.bfloat16, device=dev)
+    mid = (n // BLK // 2) * BLK
+    rows = np.random.default_rng(1).integers(0, n // row_words, n_rows).tolist()
+    gather_out = torch.empty([n_rows, row_words], dtype=torch.bfloat16, device=dev)
+
+    cases = {"full": ("decode", lambda: C.float_decompress_stride(arch2d, n, torch.bfloat16, ws=ws, out=full_out))}
+    for blocks in (1, 8, 64, 512, 1024):
+        cnt = blocks * BLK
+        out = torch.empty([cnt], dtype=torch.bfloat16, device=dev)
+        cases[f"range_{blocks}_blocks"] = ("decode_range", lambda cnt=cnt, out=out: C.float_decompress_range(
+            [archive], [mid], [cnt], [out], dtype=torch.bfloat16, ws=ws))
+    cases[f"gather_{n_rows}_rows_of_{row_words}"] = ("decode_range", lambda: C.gather_rows(
+        archive, row_words, rows, torch.bfloat16, out=gather_out, ws=ws))
+
+    # correctness at the sizes timed
+    for name, (_, f) in cases.items():
+        f()
+    torch.cuda.synchronize()
+    xi = x.view(torch.int16)
+    assert torch.equal(full_out.view(torch.int16).view(-1), xi)
+    assert torch.equal(gather_out.view(torch.int16), xi.view(-1, row_words)[rows])
+
+    C.profile(True)
+    kern = {k: [] for k in cases}
+    call = {k: [] for k in cases}
+    for w in range(a.windows + 1):  # window 0 is warm-up
+        for name, (family, f) in cases.items():
+            C.profile_reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.calls):
+                f()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            ms, launches = C.profile_query(family)
+            assert launches == a.calls, (name, launches)
+            if w:
+                kern[name].append(1e3 * ms / a.calls)
+                call[name].append(1e6 * dt / a.calls)
+    C.profile(False)
+
+    lines = []
+    base = statistics.median(kern["full"])
+    for name in cases:
+        k = statistics.median(kern[name])
+        lines.append({"case": name, "element_mib": a.mib, "dtype": "bf16", "kernel_us": round(k, 2),
+                      "kernel_us_min": round(min(kern[name]), 2), "kernel_us_max": round(max(kern[name]), 2),
+                      "call_us": round(statistics.median(call[name]), 2),
+                      "kernel_vs_full": round(k / base, 4), "windows": a.windows, "calls_per_window": a.calls,
+                      "device": torch.cuda.get_device_name(0)})
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        for ln in lines:
+            print(json.dumps(ln))
+            fh.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
