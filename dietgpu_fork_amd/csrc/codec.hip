@@ -278,7 +278,7 @@ void compressThreeKernel(const CompressCall& c) {
   constexpr size_t kProRowsBudget = 32ull << 20;
   const size_t proRowsBytes = size_t(kSegs) * nb * proRowsOf(chunks) * kNumSymbols * 4;
   const bool pro = runHist && !userHist && !rawCk && MB > 0 && proRowsBytes <= kProRowsBudget &&
-                   uint64_t(nb) * nW <= 2ull * residentSlots(reinterpret_cast<const void*>(&k_encode<FT, 0, true>),
+                   uint64_t(nb) * nW <= 2ull * residentSlots(reinterpret_cast<const void*>(&k_encode<FT, true>),
                                                              enc::kThreads, 0);
   auto partHist = res.alloc<uint32_t>(s, runHist && !pro ? size_t(kSegs) * nb * chunks * kNumSymbols : 1);
   auto partCk = res.alloc<uint32_t>(s, rawCk ? size_t(nb) * chunks : 1);
@@ -378,10 +378,10 @@ void compressThreeKernel(const CompressCall& c) {
         tail.rows = static_cast<const uint32_t*>(lease.rows[0]);
         tail.rowsPer = proRowsOf(chunks);
         tail.pdfOut = pdfMem.data();
-        k_encode<FT, 0, true><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
-                                                          slots.data(), cw.data(), tail);
+        k_encode<FT, true><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
+                                                       slots.data(), cw.data(), tail);
       } else {
-        k_encode<FT, 0><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
+        k_encode<FT><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
                                                  slots.data(), cw.data(), tail);
       }
       HIP_LAUNCH_CHECK();
@@ -431,10 +431,9 @@ void decodeBatchDevice(const DecodeCall& c) {
   const hipStream_t s = c.s;
   const int pb = c.pb;
   const uint32_t maxBlocks = divUp(c.maxCapacity, kBlockSize);
-  auto launch = [&](auto kTag, auto ntTag) {
-    constexpr int KK = decltype(kTag)::value;
+  auto launch = [&](auto ntTag) {
     constexpr bool NT = decltype(ntTag)::value;
-    using Cfg = DecCfg<FT, KK>;
+    using Cfg = DecCfg<FT>;
     forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
       prof::Scope p("decode", s);
       // about one generation of resident workgroups; each decodes P chunks
@@ -446,7 +445,7 @@ void decodeBatchDevice(const DecodeCall& c) {
       const uint32_t lds = Cfg::ldsBytes(pb);
       const uint32_t chunks = std::max(1u, divUp(maxBlocks, Cfg::kBlocksPerWG));
       const uint32_t slots =
-          residentSlots(reinterpret_cast<const void*>(&k_decode<FT, KK, NT, true>), dec::kThreads, lds);
+          residentSlots(reinterpret_cast<const void*>(&k_decode<FT, NT, true>), dec::kThreads, lds);
       // capacityOnly: the capacity is all the host knows and may far exceed
       // the archives' sizes (the sparse codec's nonzero lists): one chunk per
       // workgroup, so the chunks that exist run side by side instead of P
@@ -461,20 +460,20 @@ void decodeBatchDevice(const DecodeCall& c) {
       // (c3 decode 2.02 ms without, 2.32 ms with, same-box A/B).  A template
       // parameter: a runtime flag changed the step loop's code (c2 +25 %)
       if (uint64_t(g.x) * ny <= slots)
-        k_decode<FT, KK, NT, true><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
-                                                                 c.outSuccess_dev, c.outSize_dev);
+        k_decode<FT, NT, true><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
+                                                             c.outSuccess_dev, c.outSize_dev);
       else
-        k_decode<FT, KK, NT, false><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
-                                                                  c.outSuccess_dev, c.outSize_dev);
+        k_decode<FT, NT, false><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
+                                                              c.outSuccess_dev, c.outSize_dev);
       HIP_LAUNCH_CHECK();
     });
   };
   // streaming stores when nobody re-reads the output right away (fp64's
   // 8-dword rows measured slower with them)
   if constexpr (FT != 4) {
-    if (c.streamOut) return launch(std::integral_constant<int, 0>{}, std::true_type{});
+    if (c.streamOut) return launch(std::true_type{});
   }
-  launch(std::integral_constant<int, 0>{}, std::false_type{});
+  launch(std::false_type{});
 }
 
 // Range decode: words [first, first + count) of archive b
@@ -489,13 +488,13 @@ template <int FT>
 void decodeRangeBatchDevice(const DecodeCall& c, uint32_t maxRangeBlocks) {
   checkProbBits(c.pb);
   if (c.nb == 0) return;
-  using Cfg = DecCfg<FT, 0>;
+  using Cfg = DecCfg<FT>;
   const uint32_t lds = Cfg::ldsBytes(c.pb);
   forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
     prof::Scope p("decode_range", c.s);
     dim3 g(std::max(1u, divUp(maxRangeBlocks, uint32_t(Cfg::kBlocksPerWG))), ny);
-    k_decode<FT, 0, false, false, true><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
-                                                                      1u, c.outSuccess_dev, c.outSize_dev);
+    k_decode<FT, false, false, true><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
+                                                                   1u, c.outSuccess_dev, c.outSize_dev);
     HIP_LAUNCH_CHECK();
   });
 }

@@ -45,7 +45,15 @@ __host__ __device__ constexpr inline uint64_t roundUp64(uint64_t a, uint64_t b) 
   return (a + b - 1) / b * b;
 }
 
-// ANSCoalescedHeader::getCompressedOverhead (ans/GpuANSUtils.cuh:68-86)
+// Symbols of block bk of an n-symbol element; 0 for a block at or past `end`
+// (the element's block count, or the end of the blocks a caller works on).
+__host__ __device__ inline uint32_t blockSymbols(uint32_t bk, uint32_t end, uint32_t n) {
+  const uint32_t left = n - bk * kBlockSize;
+  return bk < end ? (left < kBlockSize ? left : kBlockSize) : 0u;
+}
+
+// ANSCoalescedHeader::getCompressedOverhead (ans/GpuANSUtils.cuh:68-86); the
+// sections it sums are laid out by AnsSections (device.h)
 __host__ __device__ inline uint64_t ansOverhead(uint32_t numBlocks) {
   return kANSHeaderBytes + kPdfBytes + uint64_t(kStateBytesPerBlock) * numBlocks +
       8ull * roundUp(numBlocks, 2);

@@ -7,8 +7,8 @@
 // MI355X design:
 //  * The step is a chain of two dependent LDS round trips (table entry, then
 //    the renormalisation word), so throughput comes from independent chains:
-//    256-thread workgroups (4 waves), every wave one block pair (K = 1; fp64:
-//    the pair's 2 streams) -- lanes 0-31 one block, lanes 32-63 the next (the
+//    256-thread workgroups (4 waves), every wave one block pair (fp64: the
+//    pair's 2 streams) -- lanes 0-31 one block, lanes 32-63 the next (the
 //    reference's 32-state interleaving) -- and many resident waves (more,
 //    smaller waves beat 2-4 interleaved pairs per wave, DecCfg below).
 //  * 64-bit decode table {pdf | sym << 24, slot - cdf}: the state update is
@@ -47,17 +47,16 @@ constexpr uint32_t kUnroll = 4;      // steps between ring checks
 constexpr uint32_t kChunk = kSegWords / 32;  // words joined per lane per segment
 }  // namespace dec
 
-// KK: block pairs per wave (0 = the default, 1).  One pair per wave beats
-// 2-4 interleaved pairs per wave at every batch size measured (c2 decode
-// 125 -> 102 us, c3 3.0 -> 2.3 ms): more, smaller waves hide the step's
-// latency better and fill the chip without generation quantisation.
-template <int FT, int KK = 0>
+// One pair per wave; 2-4 interleaved pairs measured slower at every batch
+// size (c2 decode 125 -> 102 us, c3 3.0 -> 2.3 ms with one): more, smaller
+// waves hide the step's latency better and fill the chip without generation
+// quantisation.
+template <int FT>
 struct DecCfg {
   static constexpr int S = FloatTraits<FT>::kSegs;  // ANS streams per word
-  static constexpr int K = KK ? KK : 1;             // block pairs per wave
-  static constexpr int kBlocksPerWave = 2 * K;
+  static constexpr int kBlocksPerWave = 2;
   static constexpr int kBlocksPerWG = dec::kWaves * kBlocksPerWave;
-  static constexpr uint32_t kHalfStreams = dec::kWaves * K * S * 2;
+  static constexpr uint32_t kHalfStreams = dec::kWaves * S * 2;
   static constexpr uint32_t kRingBytes = kHalfStreams * dec::kRing * 2;
   static constexpr uint32_t kSegBytes = kHalfStreams * dec::kSegWords * 2;
   // dynamic LDS: S tables of 8 << pb bytes, rings, segment buffers
@@ -375,16 +374,16 @@ __device__ __forceinline__ void buildLut64(gp<const uint16_t> pdfIn, lp<u32x2> l
 // it are never reached).  Chunks of 8 words wholly inside the range whose
 // destination is 16 B-aligned take the vector join, every other chunk the
 // masked scalar one: nothing outside out[0 .. count) is written.
-template <int FT, int KK, bool NT, bool BAL, bool RNG = false>
+template <int FT, bool NT, bool BAL, bool RNG = false>
 __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(4))) void k_decode(const InlineTable,
                                                           BatchDesc in, BatchDesc out,
                                                           uint32_t batchOffset, int pb,
                                                           uint32_t chunksPerWG,
                                                           uint8_t* __restrict__ outSuccess,
                                                           uint32_t* __restrict__ outSize) {
-  using Cfg = DecCfg<FT, KK>;
+  using Cfg = DecCfg<FT>;
   using WordT = typename FloatTraits<FT>::WordT;
-  constexpr int S = Cfg::S, K = Cfg::K, R = Join<FT>::kR;
+  constexpr int S = Cfg::S, R = Join<FT>::kR;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   lp<uint8_t> L = (lp<uint8_t>)smem;
   const uint32_t lutBytes = Cfg::lutBytes(pb);
@@ -400,15 +399,14 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   uint32_t n;
   bool ok;
   if constexpr (FT == 0) {
-    arch[0] = base;
     n = fh[2];
     ok = fh[0] == kANSMagicVersion;
   } else {
     n = fh[1];
     ok = fh[0] == kFloatMagicVersion && (fh[2] & 0xfu) == uint32_t(FT);
-    arch[0] = base + 32 + floatRawBytes(FT, n);
-    if constexpr (S == 2) arch[S - 1] = arch[0] + fh[4];
   }
+  arch[0] = ansArchiveOf<FT>(base, n);
+  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[4];
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
@@ -418,7 +416,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   uint32_t rlo = 0, rhi = 0;
   bool success;
   if constexpr (RNG) {
-    static_assert(K == 1 && !BAL, "range decode: one block pair per wave, no priorities");
+    static_assert(!BAL, "range decode: no priorities");
     rlo = in.size(b);
     const uint32_t count = out.size(b);
     success = ok && rlo <= n && count <= n - rlo;
@@ -472,31 +470,26 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   // two).  The first pass's are issued before the decode-table build, whose
   // pdf load and LDS passes they then overlap.
   const bool vecIO = vecIn && vecOut;
-  uint32_t x0[K][S];
-  uint2 bwE[K][S][2];
-  uint32_t rvA[K][R], rvB[K][R];
+  uint32_t x0[S];
+  uint2 bwE[S][2];
+  uint32_t rvA[R], rvB[R];
   auto issue = [&](uint32_t blk0) __attribute__((always_inline)) {
     const uint32_t off = dec::kChunk * l;
+    const uint32_t bkMine = blk0 + (lane >> 5);
+    // the first segment decoded is the block pair's top one; full (and so
+    // loadable unmasked) when both blocks of the pair are whole
+    const uint32_t uwMin = min(blockSymbols(blk0 + 1, blkEnd, n), blockSymbols(blk0, blkEnd, n));
+    const uint32_t iTop = bkMine * kBlockSize + (kBlockSize / 32 / dec::kSegSteps - 1) * dec::kSegWords + off;
+    if (FT != 0 && vecIO && uwMin == kBlockSize && wholeInRange(iTop)) Join<FT>::load(rvA, raw, n, iTop);
 #pragma unroll
-    for (int c = 0; c < K; ++c) {
-      const uint32_t bkMine = blk0 + 2 * c + (lane >> 5);
-      // the first segment decoded is the block pair's top one; full (and so
-      // loadable unmasked) when both blocks of every pair are whole
-      const uint32_t uwMin = min(blk0 + 2 * c + 1 < blkEnd ? min(kBlockSize, n - (blk0 + 2 * c + 1) * kBlockSize) : 0u,
-                                 blk0 + 2 * c < blkEnd ? min(kBlockSize, n - (blk0 + 2 * c) * kBlockSize) : 0u);
-      const uint32_t iTop = bkMine * kBlockSize + (kBlockSize / 32 / dec::kSegSteps - 1) * dec::kSegWords + off;
-      if (FT != 0 && vecIO && uwMin == kBlockSize && wholeInRange(iTop)) Join<FT>::load(rvA[c], raw, n, iTop);
+    for (int s = 0; s < S; ++s) {
+      const AnsSections arc(arch[s], nBlocks);
+      x0[s] = bkMine < blkEnd ? ((gp<const uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * bkMine))[l]
+                              : kMinState;
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        gp<const uint8_t> states = arch[s] + kANSHeaderBytes + kPdfBytes;
-        gp<const uint2> bw = (gp<const uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks);
-        x0[c][s] = bkMine < blkEnd ? ((gp<const uint32_t>)(states + uint64_t(kStateBytesPerBlock) * bkMine))[l]
-                                    : kMinState;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          const uint32_t bk = blk0 + 2 * c + hh;
-          bwE[c][s][hh] = bk < blkEnd ? ld8(bw + bk) : make_uint2(0, 0);
-        }
+      for (int hh = 0; hh < 2; ++hh) {
+        const uint32_t bk = blk0 + hh;
+        bwE[s][hh] = bk < blkEnd ? ld8(arc.bwords + bk) : make_uint2(0, 0);
       }
     }
   };
@@ -519,17 +512,12 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
     if (blk0 >= blkEnd) break;
     if (pass > 0) issue(blk0);
 
-    // per pair c: blocks blk0 + 2c (lanes 0-31) and blk0 + 2c + 1 (lanes 32-63)
-    uint32_t uwH[K][2];  // wave-uniform: block sizes follow from n alone
-    DStream st[K][S];
-    lp<uint16_t> segLane[K][S];
+    // the wave's pair: blocks blk0 (lanes 0-31) and blk0 + 1 (lanes 32-63)
+    uint32_t uwH[2];  // wave-uniform: block sizes follow from n alone
+    DStream st[S];
+    lp<uint16_t> segLane[S];
 #pragma unroll
-    for (int c = 0; c < K; ++c)
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const uint32_t bk = blk0 + 2 * c + hh;
-        uwH[c][hh] = bk < blkEnd ? min(kBlockSize, n - bk * kBlockSize) : 0u;
-      }
+    for (int hh = 0; hh < 2; ++hh) uwH[hh] = blockSymbols(blk0 + hh, blkEnd, n);
     // range form: the lowest segment decoded.  Above 0 only for the pair whose
     // one block holds the whole range (any other pair has a block that the
     // range enters from below, so its segment 0 is needed); that pair has no
@@ -538,73 +526,60 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
     if constexpr (RNG) {
       if (blk0 == blkFirst && blk0 + 1 >= blkEnd) gMin = int32_t((rlo - blkFirst * kBlockSize) / dec::kSegWords);
     }
-    uint32_t T = 0;
-#pragma unroll
-    for (int c = 0; c < K; ++c) T = max(T, max(divUp(uwH[c][0], 32), divUp(uwH[c][1], 32)));
-    // segments [0, nFull) are full for every block of the wave; the partial
+    const uint32_t T = max(divUp(uwH[0], 32), divUp(uwH[1], 32));
+    // segments [0, nFull) are full for both blocks of the pair; the partial
     // top segments (element tail / odd block count) are decoded first, masked
-    uint32_t nFull = ~0u;
-#pragma unroll
-    for (int c = 0; c < K; ++c) nFull = min(nFull, min(uwH[c][0], uwH[c][1]) / dec::kSegWords);
+    const uint32_t nFull = min(uwH[0], uwH[1]) / dec::kSegWords;
     const int32_t nSeg = int32_t(divUp(T, dec::kSegSteps));
     const uint32_t off = dec::kChunk * l;  // this lane's chunk in a segment
 
     const bool rawEarly = FT != 0 && vecIO && nSeg > 0 && uint32_t(nSeg - 1) < nFull;
 #pragma unroll
-    for (int c = 0; c < K; ++c) {
+    for (int s = 0; s < S; ++s) {
+      gp<const uint16_t> data = AnsSections(arch[s], nBlocks).words;
+      DStream& d = st[s];
+      const uint32_t hs = w * S + s;  // half-stream pair index
+      d.ring = ringAll + hs * 2 * dec::kRing;
+      d.ringLane = d.ring + (hv & dec::kRing);
+      segLane[s] = segAll + hs * 2 * dec::kSegWords + (hv & dec::kSegWords) + l;
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        gp<const uint8_t> states = arch[s] + kANSHeaderBytes + kPdfBytes;
-        gp<const uint2> bw = (gp<const uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks);
-        gp<const uint16_t> data = (gp<const uint16_t>)(bw + roundUp(nBlocks, 2));
-        DStream& d = st[c][s];
-        const uint32_t hs = (w * K + c) * S + s;  // half-stream pair index
-        d.ring = ringAll + hs * 2 * dec::kRing;
-        d.ringLane = d.ring + (hv & dec::kRing);
-        segLane[c][s] = segAll + hs * 2 * dec::kSegWords + (hv & dec::kSegWords) + l;
+      for (int hh = 0; hh < 2; ++hh) {
+        const uint32_t bk = blk0 + hh;
+        d.ptr[hh] = 0;
+        d.lo[hh] = 0;
+        d.data[hh] = data;
+        d.pf[hh] = u32x2{0, 0};
+        if (bk < blkEnd) {
+          const uint2 e = bwE[s][hh];
+          const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
+          const int32_t cw = int32_t(ex & 0xffffu);
+          d.ptr[hh] = cw;
+          d.data[hh] = data + ey;
+          const int32_t lo =
+              cw > int32_t(dec::kRing) ? int32_t(roundUp(uint32_t(cw) - dec::kRing, dec::kWPL)) : 0;
+          d.lo[hh] = lo;
+          // initial fill of [lo, cw) (<= 512 words: two wave-wide passes).
+          // The last lane may copy up to 3 words past cw (the block's
+          // 8-word padding) into slots below lo + 512: never a live slot.
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          const uint32_t bk = blk0 + 2 * c + hh;
-          d.ptr[hh] = 0;
-          d.lo[hh] = 0;
-          d.data[hh] = data;
-          d.pf[hh] = u32x2{0, 0};
-          if (bk < blkEnd) {
-            const uint2 e = bwE[c][s][hh];
-            const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
-            const int32_t cw = int32_t(ex & 0xffffu);
-            d.ptr[hh] = cw;
-            d.data[hh] = data + ey;
-            const int32_t lo =
-                cw > int32_t(dec::kRing) ? int32_t(roundUp(uint32_t(cw) - dec::kRing, dec::kWPL)) : 0;
-            d.lo[hh] = lo;
-            // initial fill of [lo, cw) (<= 512 words: two wave-wide passes).
-            // The last lane may copy up to 3 words past cw (the block's
-            // 8-word padding) into slots below lo + 512: never a live slot.
-#pragma unroll
-            for (int q = 0; q < int(dec::kRing / dec::kRefill); ++q) {
-              const int32_t a = lo + q * int32_t(dec::kRefill) + int32_t(dec::kWPL * lane);
-              if (a < cw)
-                *(lp<u32x2>)(d.ring + hh * dec::kRing + (a & (dec::kRing - 1))) = ld4w(d.data[hh] + a, vecIn);
-            }
-            ringPrefetch(d, hh, lane, vecIn);
+          for (int q = 0; q < int(dec::kRing / dec::kRefill); ++q) {
+            const int32_t a = lo + q * int32_t(dec::kRefill) + int32_t(dec::kWPL * lane);
+            if (a < cw)
+              *(lp<u32x2>)(d.ring + hh * dec::kRing + (a & (dec::kRing - 1))) = ld4w(d.data[hh] + a, vecIn);
           }
+          ringPrefetch(d, hh, lane, vecIn);
         }
-        d.x = x0[c][s];
       }
+      d.x = x0[s];
     }
 
-    DStream* chains[K * S];
-    lp<const u32x2> lutC[K * S];
-    bool allValid[K * S];
+    DStream* chains[S];
+    bool allValid[S];
 #pragma unroll
-    for (int c = 0; c < K; ++c)
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        chains[c * S + s] = &st[c][s];
-        lutC[c * S + s] = lut[s];
-        allValid[c * S + s] = true;
-      }
+    for (int s = 0; s < S; ++s) {
+      chains[s] = &st[s];
+      allValid[s] = true;
+    }
 
     // kVec: 16 B aligned input and output (once per wave): full segments
     // then load and join unconditionally.
@@ -612,52 +587,46 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
       constexpr bool kVec = decltype(vecTag)::value;
       // raw float bytes, double-buffered: a full segment's bytes are loaded
       // before the previous segment's steps, a whole segment ahead of use
-      auto loadRaw = [&](int32_t g, bool fullSeg, uint32_t (&rv)[K][R]) {
+      auto loadRaw = [&](int32_t g, bool fullSeg, uint32_t (&rv)[R]) {
         const uint32_t segW0 = uint32_t(g) * dec::kSegWords;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-          const uint32_t uw = lane >= 32 ? uwH[c][1] : uwH[c][0];
-          const uint32_t bk = blk0 + 2 * c + (lane >> 5);
-          if (FT != 0 && kVec && (fullSeg || segW0 + off + dec::kChunk <= uw) &&
-              wholeInRange(bk * kBlockSize + segW0 + off))
-            Join<FT>::load(rv[c], raw, n, bk * kBlockSize + segW0 + off);
-        }
+        const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
+        const uint32_t bk = blk0 + (lane >> 5);
+        if (FT != 0 && kVec && (fullSeg || segW0 + off + dec::kChunk <= uw) &&
+            wholeInRange(bk * kBlockSize + segW0 + off))
+          Join<FT>::load(rv, raw, n, bk * kBlockSize + segW0 + off);
       };
-      auto join = [&](int32_t g, bool fullSeg, const uint32_t (&rv)[K][R]) {
+      auto join = [&](int32_t g, bool fullSeg, const uint32_t (&rv)[R]) {
         const uint32_t segW0 = uint32_t(g) * dec::kSegWords;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-          const uint32_t uw = lane >= 32 ? uwH[c][1] : uwH[c][0];
-          const uint32_t bk = blk0 + 2 * c + (lane >> 5);
-          if (!fullSeg && segW0 + off >= uw) continue;
-          const uint32_t cnt = fullSeg ? dec::kChunk : min(dec::kChunk, uw - segW0 - off);
-          const uint32_t i0 = bk * kBlockSize + segW0 + off;
-          // range form: words [k0, k1) of the chunk lie in the range
-          uint32_t k0 = 0, k1 = cnt;
-          if constexpr (RNG) {
-            k0 = i0 < rlo ? min(cnt, rlo - i0) : 0u;
-            k1 = rhi > i0 ? min(cnt, rhi - i0) : 0u;
-            if (k0 >= k1) continue;
-          }
-          lp<const uint16_t> q0 = segLane[c][0] - l + off;
-          lp<const uint16_t> q1 = segLane[c][S - 1] - l + off;
-          if (kVec && cnt == dec::kChunk && wholeInRange(i0)) {
-            uint32_t sv[4], sv1[4];
-            const u32x4 a0 = *(lp<const u32x4>)q0;
-            sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
-            if constexpr (S == 2) {
-              const u32x4 b0 = *(lp<const u32x4>)q1;
-              sv1[0] = b0.x; sv1[1] = b0.y; sv1[2] = b0.z; sv1[3] = b0.w;
-            } else {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) sv1[k] = 0;
-            }
-            Join<FT>::template vec<NT>(outB, i0, sv, sv1, rv[c]);
+        const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
+        const uint32_t bk = blk0 + (lane >> 5);
+        if (!fullSeg && segW0 + off >= uw) return;
+        const uint32_t cnt = fullSeg ? dec::kChunk : min(dec::kChunk, uw - segW0 - off);
+        const uint32_t i0 = bk * kBlockSize + segW0 + off;
+        // range form: words [k0, k1) of the chunk lie in the range
+        uint32_t k0 = 0, k1 = cnt;
+        if constexpr (RNG) {
+          k0 = i0 < rlo ? min(cnt, rlo - i0) : 0u;
+          k1 = rhi > i0 ? min(cnt, rhi - i0) : 0u;
+          if (k0 >= k1) return;
+        }
+        lp<const uint16_t> q0 = segLane[0] - l + off;
+        lp<const uint16_t> q1 = segLane[S - 1] - l + off;
+        if (kVec && cnt == dec::kChunk && wholeInRange(i0)) {
+          uint32_t sv[4], sv1[4];
+          const u32x4 a0 = *(lp<const u32x4>)q0;
+          sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
+          if constexpr (S == 2) {
+            const u32x4 b0 = *(lp<const u32x4>)q1;
+            sv1[0] = b0.x; sv1[1] = b0.y; sv1[2] = b0.z; sv1[3] = b0.w;
           } else {
-            gp<WordT> o = (gp<WordT>)outB;
-            for (uint32_t k = k0; k < k1; ++k)
-              o[i0 + k] = Join<FT>::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sv1[k] = 0;
           }
+          Join<FT>::template vec<NT>(outB, i0, sv, sv1, rv);
+        } else {
+          gp<WordT> o = (gp<WordT>)outB;
+          for (uint32_t k = k0; k < k1; ++k)
+            o[i0 + k] = Join<FT>::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
         }
       };
 
@@ -673,27 +642,20 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 #pragma unroll
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
 #pragma unroll
-          for (int c = 0; c < K; ++c)
-#pragma unroll
-            for (int s = 0; s < S; ++s) ringEnsure(st[c][s], lane, kVec);
+          for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, kVec);
 #pragma unroll
           for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
             const int tr = grp * int(dec::kUnroll) + u;
             const uint32_t t = uint32_t(tBot + tr);
-            bool vld[K * S];
+            const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
+            bool vld[S];
 #pragma unroll
-            for (int c = 0; c < K; ++c) {
-              const uint32_t uw = lane >= 32 ? uwH[c][1] : uwH[c][0];
+            for (int s = 0; s < S; ++s) vld[s] = t * 32 + l < uw;
+            uint32_t e0[S];
+            decStepAll<true, S>(chains, vld, lut, mask, pb, hv, e0);
 #pragma unroll
-              for (int s = 0; s < S; ++s) vld[c * S + s] = t * 32 + l < uw;
-            }
-            uint32_t e0[K * S];
-            decStepAll<true, K * S>(chains, vld, lutC, mask, pb, hv, e0);
-#pragma unroll
-            for (int c = 0; c < K; ++c)
-#pragma unroll
-              for (int s = 0; s < S; ++s)
-                if (vld[c * S + s]) segLane[c][s][tr * 32] = uint16_t(e0[c * S + s] >> 16);
+            for (int s = 0; s < S; ++s)
+              if (vld[s]) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
           }
         }
         __builtin_amdgcn_wave_barrier();
@@ -702,25 +664,21 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         if (g > gMin) loadRaw(g - 1, uint32_t(g - 1) < nFull, rvA);
       }
       // full segments: unrolled, unmasked
-      auto fullSeg = [&](int32_t g, const uint32_t (&cur)[K][R], uint32_t (&nxt)[K][R]) {
+      auto fullSeg = [&](int32_t g, const uint32_t (&cur)[R], uint32_t (&nxt)[R]) {
         if constexpr (BAL)
           setPrioRemaining((chunksPerWG - 1 - pass) * uint32_t(nSeg) + uint32_t(g), chunksPerWG * uint32_t(nSeg));
         if (g > 0) loadRaw(g - 1, true, nxt);
 #pragma unroll
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
 #pragma unroll
-          for (int c = 0; c < K; ++c)
-#pragma unroll
-            for (int s = 0; s < S; ++s) ringEnsure(st[c][s], lane, kVec);
+          for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, kVec);
 #pragma unroll
           for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
             const int tr = grp * int(dec::kUnroll) + u;  // step within segment
-            uint32_t e0[K * S];
-            decStepAll<false, K * S>(chains, allValid, lutC, mask, pb, hv, e0);
+            uint32_t e0[S];
+            decStepAll<false, S>(chains, allValid, lut, mask, pb, hv, e0);
 #pragma unroll
-            for (int c = 0; c < K; ++c)
-#pragma unroll
-              for (int s = 0; s < S; ++s) segLane[c][s][tr * 32] = uint16_t(e0[c * S + s] >> 16);
+            for (int s = 0; s < S; ++s) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
           }
         }
         __builtin_amdgcn_wave_barrier();

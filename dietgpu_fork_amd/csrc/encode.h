@@ -549,20 +549,19 @@ constexpr uint32_t kFlush = 256;   // words per flush (64 lanes x 8 B)
 constexpr uint32_t kUnroll = 4;    // steps between flush checks
 }  // namespace enc
 
-// KK: block pairs per wave (0 = the default, 1; see decode.h DecCfg: c2
-// encode 111 -> 97 us against 2 pairs per wave).
-template <int FT, int KK = 0>
+// One block pair per wave (see decode.h DecCfg; two interleaved pairs per
+// wave measured slower: c2 encode 97 -> 111 us).
+template <int FT>
 struct EncCfg {
   using WordT = typename FloatTraits<FT>::WordT;
   static constexpr int S = FloatTraits<FT>::kSegs;
-  static constexpr int K = KK ? KK : 1;
-  static constexpr int kBlocksPerWave = 2 * K;
+  static constexpr int kBlocksPerWave = 2;
   static constexpr int kBlocksPerWG = enc::kWaves * kBlocksPerWave;
   // 16-byte input vectors per lane per block per segment (32 lanes x V x 16 B
   // = 512 words)
   static constexpr int V = int(enc::kSegWords * sizeof(WordT) / (32 * 16));
   static constexpr uint32_t kWordsPerVec = 16 / sizeof(WordT);
-  static constexpr uint32_t kHalfStreams = enc::kWaves * K * S * 2;
+  static constexpr uint32_t kHalfStreams = enc::kWaves * S * 2;
 };
 
 // One ANS stream of one block pair.  All but x are wave-uniform.
@@ -1003,19 +1002,18 @@ __device__ __forceinline__ void writeHeadTotal(gp<uint8_t> base, gp<uint8_t> o, 
 // (kFused): writes the whole archive (states straight to it, words via the
 // slots, see EncTail).  fp64: writes per block slot states, slot words and
 // cw[] (word count) for k_coalesce.
-template <int FT, int KK, bool kPro = false>
+template <int FT, bool kPro = false>
 __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDesc out,
                                                           uint32_t batchOffset,
                                                           uint32_t numInBatch, uint32_t MB,
                                                           const uint4* __restrict__ table,
                                                           uint8_t* __restrict__ slots,
                                                           uint32_t* __restrict__ cw, EncTail tail) {
-  using Cfg = EncCfg<FT, KK>;
+  using Cfg = EncCfg<FT>;
   using WordT = typename Cfg::WordT;
-  constexpr int S = Cfg::S, K = Cfg::K, V = Cfg::V;
+  constexpr int S = Cfg::S, V = Cfg::V;
   constexpr bool kFused = S == 1;
   constexpr uint32_t R = kFused ? enc::kRingFused : enc::kRing;
-  static_assert(!kFused || K == 1, "fused copy addresses block k's ring at k * R");
   __shared__ __attribute__((aligned(16))) uint32_t tblS[S][kNumSymbols * 4];
   __shared__ __attribute__((aligned(16))) uint8_t symS[Cfg::kHalfStreams][enc::kSegWords];
   __shared__ __attribute__((aligned(16))) uint16_t ringS[Cfg::kHalfStreams / 2][2 * R];
@@ -1042,9 +1040,8 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
   // kPro also the pdf rows k_coalesce reads)
   if (first >= nBlocks && ((!kFused && !kPro) || wx != 0)) return;
   gp<uint8_t> base = startOf(out, b);
-  gp<uint8_t> o = base + (FT == 0 ? 0u : 32u + floatRawBytes(FT, n));  // ANS archive
-  gp<uint8_t> states = o + kANSHeaderBytes + kPdfBytes;
-  gp<uint2> bwords = (gp<uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks);
+  gp<uint8_t> o = ansArchiveOf<FT>(base, n);
+  const AnsSections arc(o, nBlocks);
   if constexpr (kPro) {
     proNormalize<S>(G(tail.rows), tail.rowsPer, numInBatch, b, n, tail.pb, (lp<u32x4>)&ringS[0][0], tblS, pdfS);
     __syncthreads();
@@ -1071,169 +1068,114 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
   gp<uint8_t> raw = FT == 0 ? gp<uint8_t>(nullptr) : startOf(out, b) + 32;
   const bool vecIn = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
 
-  uint32_t uwH[K][2];  // wave-uniform
-  uint32_t blk[K], uw[K];
-  EStream st[K][S];
-  lp<uint8_t> symLane[K][S];
+  // the wave's pair: blocks blk0 (lanes 0-31) and blk0 + 1 (lanes 32-63)
+  uint32_t uwH[2];  // wave-uniform
 #pragma unroll
-  for (int c = 0; c < K; ++c) {
+  for (int hh = 0; hh < 2; ++hh) uwH[hh] = blockSymbols(blk0 + hh, nBlocks, n);
+  const uint32_t blk = blk0 + h;
+  const uint32_t uw = h ? uwH[1] : uwH[0];
+  EStream st[S];
+  lp<uint8_t> symLane[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    EStream& p = st[s];
+    const uint32_t hs = w * S + s;
+    p.x = kStartState;
+    p.ring = (lp<uint16_t>)&ringS[hs][0];
+    p.ringLane = p.ring + (hv & R);
+    symLane[s] = (lp<uint8_t>)&symS[2 * hs][0] + (hv & enc::kSegWords) + l;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      const uint32_t bk = blk0 + 2 * c + hh;
-      uwH[c][hh] = bk < nBlocks ? min(kBlockSize, n - bk * kBlockSize) : 0u;
-    }
-    blk[c] = blk0 + 2 * c + h;
-    uw[c] = h ? uwH[c][1] : uwH[c][0];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      EStream& p = st[c][s];
-      const uint32_t hs = (w * K + c) * S + s;
-      p.x = kStartState;
-      p.ring = (lp<uint16_t>)&ringS[hs][0];
-      p.ringLane = p.ring + (hv & R);
-      symLane[c][s] = (lp<uint8_t>)&symS[2 * hs][0] + (hv & enc::kSegWords) + l;
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const uint32_t bk = blk0 + 2 * c + hh;
-        const uint32_t sb = bk < nBlocks ? bk : blk0;
-        p.nout[hh] = 0;
-        p.flushed[hh] = 0;
-        p.out[hh] = (gp<uint16_t>)(G(slots) + ((uint64_t(s) * numInBatch + b) * MB + sb) * kSlotBytes +
-                                   kStateBytesPerBlock);
-      }
+      const uint32_t bk = blk0 + hh;
+      const uint32_t sb = bk < nBlocks ? bk : blk0;
+      p.nout[hh] = 0;
+      p.flushed[hh] = 0;
+      p.out[hh] = (gp<uint16_t>)(G(slots) + ((uint64_t(s) * numInBatch + b) * MB + sb) * kSlotBytes +
+                                 kStateBytesPerBlock);
     }
   }
-  uint32_t T = 0;
-#pragma unroll
-  for (int c = 0; c < K; ++c) T = max(T, max(divUp(uwH[c][0], 32), divUp(uwH[c][1], 32)));
+  const uint32_t T = max(divUp(uwH[0], 32), divUp(uwH[1], 32));
   const uint32_t nSeg = divUp(T, enc::kSegSteps);
 
   lp<const u32x4> tbl[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) tbl[s] = (lp<const u32x4>)&tblS[s][0];
 
-  // segments [0, nFull) are full for every block of the wave
-  uint32_t nFull = ~0u;
-#pragma unroll
-  for (int c = 0; c < K; ++c)
-    nFull = min(nFull, min(uwH[c][0], uwH[c][1]) / enc::kSegWords);
+  // segments [0, nFull) are full for both blocks of the pair
+  const uint32_t nFull = min(uwH[0], uwH[1]) / enc::kSegWords;
 
   // kVec: 16 B aligned input (chosen once per wave).  With it, full
   // segments split unconditionally, so the prefetch registers are always
   // consumed before they are reloaded (no vmcnt(0) drain of the stores).
   auto run = [&](auto vecTag) {
     constexpr bool kVec = decltype(vecTag)::value;
-    uint4 pv[K][V];  // input vectors, one segment ahead
+    uint4 pv[V];  // input vectors, one segment ahead
     auto loadSeg = [&](uint32_t g) {
 #pragma unroll
-      for (int c = 0; c < K; ++c) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          const uint32_t j0 = g * enc::kSegWords + (k * 32 + l) * Cfg::kWordsPerVec;
-          if (kVec && (g < nFull || j0 + Cfg::kWordsPerVec <= uw[c]))
-            pv[c][k] = ld16(src + blk[c] * kBlockSize + j0);
-        }
+      for (int k = 0; k < V; ++k) {
+        const uint32_t j0 = g * enc::kSegWords + (k * 32 + l) * Cfg::kWordsPerVec;
+        if (kVec && (g < nFull || j0 + Cfg::kWordsPerVec <= uw)) pv[k] = ld16(src + blk * kBlockSize + j0);
       }
     };
     // split segment g: symbols -> LDS, raw -> archive
     auto split = [&](uint32_t g, bool fullSeg) {
       const uint32_t segW0 = g * enc::kSegWords;
+      if (!fullSeg && uw <= segW0) return;
+      const uint32_t segCnt = fullSeg ? enc::kSegWords : min(enc::kSegWords, uw - segW0);
 #pragma unroll
-      for (int c = 0; c < K; ++c) {
-        if (!fullSeg && uw[c] <= segW0) continue;
-        const uint32_t segCnt = fullSeg ? enc::kSegWords : min(enc::kSegWords, uw[c] - segW0);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          const uint32_t off = (k * 32 + l) * Cfg::kWordsPerVec;  // word offset in segment
-          lp<uint8_t> s0 = symLane[c][0] - l + off;
-          lp<uint8_t> s1 = symLane[c][S - 1] - l + off;
-          const uint32_t i0 = blk[c] * kBlockSize + segW0 + off;
-          if (kVec && (fullSeg || off + Cfg::kWordsPerVec <= segCnt)) {
-            splitVec<FT>(pv[c][k], i0, n, raw, s0, s1);
-          } else {
-            for (uint32_t q = 0; q < Cfg::kWordsPerVec && off + q < segCnt; ++q)
-              splitOne<FT>(src[i0 + q], i0 + q, n, raw, s0 + q, s1 + q);
-          }
+      for (int k = 0; k < V; ++k) {
+        const uint32_t off = (k * 32 + l) * Cfg::kWordsPerVec;  // word offset in segment
+        lp<uint8_t> s0 = symLane[0] - l + off;
+        lp<uint8_t> s1 = symLane[S - 1] - l + off;
+        const uint32_t i0 = blk * kBlockSize + segW0 + off;
+        if (kVec && (fullSeg || off + Cfg::kWordsPerVec <= segCnt)) {
+          splitVec<FT>(pv[k], i0, n, raw, s0, s1);
+        } else {
+          for (uint32_t q = 0; q < Cfg::kWordsPerVec && off + q < segCnt; ++q)
+            splitOne<FT>(src[i0 + q], i0 + q, n, raw, s0 + q, s1 + q);
         }
       }
     };
 
-    if (nSeg > 0) loadSeg(0);
-    for (uint32_t g = 0; g < nFull; ++g) {
-      split(g, true);
+    // Segment g: split it, flush what the rings hold beyond a flush unit,
+    // issue the next segment's loads, then kSegSteps encode steps in groups
+    // of kUnroll (the ring checked once per group).  kMask: a partial segment
+    // (element tail / odd block counts): masked steps, unrolled like the full
+    // ones; steps past a block's end are no-ops of the masked step.
+    auto segment = [&](uint32_t g, auto maskTag) __attribute__((always_inline)) {
+      constexpr bool kMask = decltype(maskTag)::value;
+      split(g, !kMask);
 #pragma unroll
-      for (int c = 0; c < K; ++c)
-#pragma unroll
-        for (int s = 0; s < S; ++s) ringFlush<int(R - 256), R>(st[c][s], lane);
+      for (int s = 0; s < S; ++s) ringFlush<int(R - 256), R>(st[s], lane);
       if (g + 1 < nSeg) loadSeg(g + 1);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int grp = 0; grp < int(enc::kSegSteps / enc::kUnroll); ++grp) {
 #pragma unroll
-        for (int c = 0; c < K; ++c)
-#pragma unroll
-          for (int s = 0; s < S; ++s) ringFlush<int(R - 128), R>(st[c][s], lane);
+        for (int s = 0; s < S; ++s) ringFlush<int(R - 128), R>(st[s], lane);
         // the group's symbols and table entries first: their LDS reads
         // cannot be hoisted over the ring stores of earlier steps
-        u32x4 E[enc::kUnroll][K][S];
-#pragma unroll
-        for (int u = 0; u < int(enc::kUnroll); ++u)
-#pragma unroll
-          for (int c = 0; c < K; ++c)
-#pragma unroll
-            for (int s = 0; s < S; ++s)
-              E[u][c][s] = tbl[s][symLane[c][s][(grp * int(enc::kUnroll) + u) * 32]];
-#pragma unroll
-        for (int u = 0; u < int(enc::kUnroll); ++u)
-#pragma unroll
-          for (int c = 0; c < K; ++c)
-#pragma unroll
-            for (int s = 0; s < S; ++s) encStep<false, R>(st[c][s], true, E[u][c][s], hv);
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    // partial segments (element tail / odd block counts): masked steps,
-    // unrolled like the full segments (groups of kUnroll steps, the ring
-    // checked once per group, table reads ahead); steps past a block's end
-    // are no-ops of the masked step
-    for (uint32_t g = nFull; g < nSeg; ++g) {
-      split(g, false);
-#pragma unroll
-      for (int c = 0; c < K; ++c)
-#pragma unroll
-        for (int s = 0; s < S; ++s) ringFlush<int(R - 256), R>(st[c][s], lane);
-      if (g + 1 < nSeg) loadSeg(g + 1);
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int grp = 0; grp < int(enc::kSegSteps / enc::kUnroll); ++grp) {
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-#pragma unroll
-          for (int s = 0; s < S; ++s) ringFlush<int(R - 128), R>(st[c][s], lane);
-        u32x4 E[enc::kUnroll][K][S];
-        bool vd[enc::kUnroll][K];
+        u32x4 E[enc::kUnroll][S];
+        bool vd[enc::kUnroll];
 #pragma unroll
         for (int u = 0; u < int(enc::kUnroll); ++u) {
           const uint32_t tr = uint32_t(grp * int(enc::kUnroll) + u);
-          const uint32_t t = g * enc::kSegSteps + tr;
+          vd[u] = !kMask || (g * enc::kSegSteps + tr) * 32 + l < uw;
 #pragma unroll
-          for (int c = 0; c < K; ++c) {
-            vd[u][c] = t * 32 + l < uw[c];
-#pragma unroll
-            for (int s = 0; s < S; ++s)
-              E[u][c][s] = tbl[s][vd[u][c] ? uint32_t(symLane[c][s][tr * 32]) : 0u];
-          }
+          for (int s = 0; s < S; ++s) E[u][s] = tbl[s][vd[u] ? uint32_t(symLane[s][tr * 32]) : 0u];
         }
 #pragma unroll
         for (int u = 0; u < int(enc::kUnroll); ++u)
 #pragma unroll
-          for (int c = 0; c < K; ++c)
-#pragma unroll
-            for (int s = 0; s < S; ++s) encStep<true, R>(st[c][s], vd[u][c], E[u][c][s], hv);
-        __builtin_amdgcn_sched_barrier(0);
+          for (int s = 0; s < S; ++s) encStep<kMask, R>(st[s], vd[u], E[u][s], hv);
+        if constexpr (kMask) __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_wave_barrier();
-    }
+    };
+
+    if (nSeg > 0) loadSeg(0);
+    for (uint32_t g = 0; g < nFull; ++g) segment(g, std::false_type{});
+    for (uint32_t g = nFull; g < nSeg; ++g) segment(g, std::true_type{});
   };
   if (vecIn)
     run(std::true_type{});
@@ -1241,26 +1183,23 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
     run(std::false_type{});
 
 #pragma unroll
-  for (int c = 0; c < K; ++c) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      EStream& p = st[c][s];
-      if constexpr (!kFused) ringFlushAll(p, lane);  // fused: the rest stays in LDS
-      if (uw[c]) {
-        const uint32_t words = uint32_t(h ? p.nout[1] : p.nout[0]);
-        if constexpr (kFused) {
-          ((gp<uint32_t>)(states + uint64_t(kStateBytesPerBlock) * blk[c]))[l] = p.x;
-          if (l == 0) {
-            cwE[blk[c] - first] = words;
-            flE[blk[c] - first] = uint32_t(h ? p.flushed[1] : p.flushed[0]);
-          }
-        } else {
-          gp<uint8_t> slot = G(slots) + ((uint64_t(s) * numInBatch + b) * MB + blk[c]) * kSlotBytes;
-          ((gp<uint32_t>)slot)[l] = p.x;
-          if (l == 0) {
-            G(cw)[(uint64_t(s) * numInBatch + b) * MB + blk[c]] = words;
-            cwSeg[kFused ? 0 : s][blk[c] - first] = words;
-          }
+  for (int s = 0; s < S; ++s) {
+    EStream& p = st[s];
+    if constexpr (!kFused) ringFlushAll(p, lane);  // fused: the rest stays in LDS
+    if (uw) {
+      const uint32_t words = uint32_t(h ? p.nout[1] : p.nout[0]);
+      if constexpr (kFused) {
+        ((gp<uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * blk))[l] = p.x;
+        if (l == 0) {
+          cwE[blk - first] = words;
+          flE[blk - first] = uint32_t(h ? p.flushed[1] : p.flushed[0]);
+        }
+      } else {
+        gp<uint8_t> slot = G(slots) + ((uint64_t(s) * numInBatch + b) * MB + blk) * kSlotBytes;
+        ((gp<uint32_t>)slot)[l] = p.x;
+        if (l == 0) {
+          G(cw)[(uint64_t(s) * numInBatch + b) * MB + blk] = words;
+          cwSeg[kFused ? 0 : s][blk - first] = words;
         }
       }
     }
@@ -1302,7 +1241,7 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
           if (tail.outSize) G(tail.outSize)[b] = 0u;
           __hip_atomic_fetch_add(G(tail.err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-          writeHeadTotal<FT>(base, o, n, nBlocks, excl + agg, bwords, tail, b);
+          writeHeadTotal<FT>(base, o, n, nBlocks, excl + agg, arc.bwords, tail, b);
         }
       }
     }
@@ -1313,10 +1252,10 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
     if (tid < nk) {
       const uint32_t k = first + tid;
       const uint32_t uwk = min(kBlockSize, n - k * kBlockSize);
-      st8(bwords + k, make_uint2((uwk << 16) | cwE[tid], preE[tid]));
+      st8(arc.bwords + k, make_uint2((uwk << 16) | cwE[tid], preE[tid]));
     }
     copyPayload<R>(preE, cwE, nk, G(slots) + (uint64_t(b) * MB + first) * kSlotBytes + kStateBytesPerBlock,
-                   (gp<uint8_t>)(bwords + roundUp(nBlocks, 2)), &ringS[0][0], flE);
+                   (gp<uint8_t>)arc.words, &ringS[0][0], flE);
   }
 }
 
@@ -1396,18 +1335,15 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
     }
   }
 
-  gp<uint8_t> o = startOf(out, b);
+  gp<uint8_t> o = ansArchiveOf<FT>(startOf(out, b), n);
   uint32_t total0Words = 0;
   if constexpr (FT != 0) {
-    o += 32 + floatRawBytes(FT, n);
     if (kSegs == 2 && (seg == 1 || blockIdx.x == 0)) {
       total0Words = fromFlags ? segTotal[0] : sumRoundedWords(cw0, nBlocks, red);
       if (seg == 1) o += roundUp64(ansOverhead(nBlocks) + 2ull * total0Words, 16);
     }
   }
-  gp<uint8_t> states = o + kANSHeaderBytes + kPdfBytes;
-  gp<uint2> bwords = (gp<uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks);
-  gp<uint8_t> data = (gp<uint8_t>)(bwords + roundUp(nBlocks, 2));
+  const AnsSections arc(o, nBlocks);
 
   // exclusive scan over [base, last): base is this range's first block, or
   // (flags) the first block of its encode workgroup, whose prefix the flag
@@ -1437,7 +1373,7 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
       hdr[5] = ansCk ? G(ck)[b] : 0u;
       hdr[6] = 0;
       hdr[7] = 0;
-      if (nBlocks & 1) st8(bwords + nBlocks, make_uint2(0, 0));
+      if (nBlocks & 1) st8(arc.bwords + nBlocks, make_uint2(0, 0));
       if constexpr (FT == 0) {
         if (outSize) G(outSize)[b] = uint32_t(ansBytes);
       } else if (seg == 0) {
@@ -1481,16 +1417,16 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
   for (uint32_t k = first + (tid >> 6); k < last; k += kWaves) {
     gp<const uint8_t> slot = G(slots) + ((uint64_t(seg) * numInBatch + b) * MB + k) * kSlotBytes;
     if (lane < 32)
-      ((gp<uint32_t>)(states + uint64_t(kStateBytesPerBlock) * k))[lane] = ((gp<const uint32_t>)slot)[lane];
+      ((gp<uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * k))[lane] = ((gp<const uint32_t>)slot)[lane];
     if (lane == 32) {
       const uint32_t uwk = (k + 1 < nBlocks || n % kBlockSize == 0) ? kBlockSize : n % kBlockSize;
-      st8(bwords + k, make_uint2((uwk << 16) | cwS[k], pre[k - first]));
+      st8(arc.bwords + k, make_uint2((uwk << 16) | cwS[k], pre[k - first]));
     }
   }
   __syncthreads();
   const uint32_t nk = last > first ? last - first : 0;
   copyPayload(pre, cwL, nk, G(slots) + ((uint64_t(seg) * numInBatch + b) * MB + first) * kSlotBytes +
-                                kStateBytesPerBlock, data);
+                                kStateBytesPerBlock, (gp<uint8_t>)arc.words);
 }
 
 // ---------------------------------------------------------------------------

@@ -347,13 +347,11 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
                        __HIP_MEMORY_SCOPE_AGENT);
   };
   auto pairSize = [&](const PItem& it, int hh) __attribute__((always_inline)) -> uint32_t {
-    const uint32_t bk = it.x * pc::kBlocksPerItem + 2 * w + hh;
-    return bk < it.nBlocks ? min(kBlockSize, it.n - bk * kBlockSize) : 0u;
+    return blockSymbols(it.x * pc::kBlocksPerItem + 2 * w + hh, it.nBlocks, it.n);
   };
   // this lane's block size of an item (h ? pairSize(it, 1) : pairSize(it, 0))
   auto laneSize = [&](const PItem& it) __attribute__((always_inline)) -> uint32_t {
-    const uint32_t bk = it.x * pc::kBlocksPerItem + 2 * w + halfNow();
-    return bk < it.nBlocks ? min(kBlockSize, it.n - bk * kBlockSize) : 0u;
+    return blockSymbols(it.x * pc::kBlocksPerItem + 2 * w + halfNow(), it.nBlocks, it.n);
   };
   auto srcOf = [&](const PItem& it) __attribute__((always_inline)) -> gp<const WordT> {
     const uint32_t hh = halfNow();
@@ -470,7 +468,10 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       p.out[hh] = (gp<uint16_t>)(slotBase + (2 * w + hh) * kSlotDataBytes);
     }
   };
-  auto encSegFull = [&](uint32_t g) __attribute__((always_inline)) {
+  // the 16 steps of segment g; kMask: steps at or past the block's end (uw)
+  // are no-ops of the masked step
+  auto encSegSteps = [&](uint32_t g, uint32_t uw, auto maskTag) __attribute__((always_inline)) {
+    constexpr bool kMask = decltype(maskTag)::value;
 #pragma unroll
     for (uint32_t t0 = g * pc::kSegSteps; t0 < (g + 1) * pc::kSegSteps; t0 += enc::kUnroll) {
       ringFlush<int(pc::kSpill), pc::kRing>(p, lane);
@@ -481,27 +482,10 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
         Ev[u] = tbl[(symR[t / 4] >> (8 * (t & 3))) & 0xffu];
       }
 #pragma unroll
-      for (uint32_t u = 0; u < enc::kUnroll; ++u) encStep<false, pc::kRing>(p, true, Ev[u], hv);
+      for (uint32_t u = 0; u < enc::kUnroll; ++u)
+        encStep<kMask, pc::kRing>(p, !kMask || (t0 + u) * 32 + l < uw, Ev[u], hv);
       // keep the scheduler from hoisting later groups' table reads over the
       // ring stores (registers, not latency, bound this loop)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  auto encSegMasked = [&](uint32_t g, uint32_t uw) __attribute__((always_inline)) {
-#pragma unroll
-    for (uint32_t t0 = g * pc::kSegSteps; t0 < (g + 1) * pc::kSegSteps; t0 += enc::kUnroll) {
-      ringFlush<int(pc::kSpill), pc::kRing>(p, lane);
-      u32x4 Ev[enc::kUnroll];
-#pragma unroll
-      for (uint32_t u = 0; u < enc::kUnroll; ++u) {
-        const uint32_t t = t0 + u;
-        Ev[u] = tbl[(symR[t / 4] >> (8 * (t & 3))) & 0xffu];
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < enc::kUnroll; ++u) {
-        const uint32_t t = t0 + u;
-        encStep<true, pc::kRing>(p, t * 32 + l < uw, Ev[u], hv);
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -597,9 +581,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t first = it.x * pc::kBlocksPerItem;
     const uint32_t nk = first < it.nBlocks ? min(pc::kBlocksPerItem, it.nBlocks - first) : 0u;
     gp<uint8_t> base = startOf(OUT(), it.b);
-    gp<uint8_t> o = base + (FT == 0 ? 0u : 32u + floatRawBytes(FT, it.n));  // ANS archive
-    gp<uint8_t> states = o + kANSHeaderBytes + kPdfBytes;
-    gp<uint2> bwords = (gp<uint2>)(states + uint64_t(kStateBytesPerBlock) * it.nBlocks);
+    gp<uint8_t> o = ansArchiveOf<FT>(base, it.n);
     const uint32_t r = lane < nk ? roundUp(cwE[lane], 8) : 0u;
     const uint32_t inc = waveInclusiveScan(r);
     const uint32_t agg = readfirst(__shfl(inc, 63));
@@ -615,7 +597,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
         } else {
           EncTail t{nullptr, nullptr, A().outSize, nullptr, 0, A().pb, A().useChecksum};
           t.sparseN = A().sparseN;
-          writeHeadTotal<FT>(base, o, it.n, it.nBlocks, excl + agg, bwords, t, it.b);
+          writeHeadTotal<FT>(base, o, it.n, it.nBlocks, excl + agg, AnsSections(o, it.nBlocks).bwords, t, it.b);
         }
       }
     }
@@ -629,7 +611,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     (void)tid;
     (void)lane;
     gp<uint8_t> base = startOf(OUT(), it.b);
-    gp<uint8_t> o = base + (FT == 0 ? 0u : 32u + floatRawBytes(FT, it.n));  // ANS archive
+    gp<uint8_t> o = ansArchiveOf<FT>(base, it.n);
     if (lane == 0) {
       const bool ansCk = FT == 0 && A().useChecksum;
       if (FT != 0) ckv = A().ckIn ? G(A().ckIn)[it.b] : 0u;
@@ -681,22 +663,20 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t t = tid - 64;
     const uint32_t first = it.x * pc::kBlocksPerItem;
     const uint32_t nk = first < it.nBlocks ? min(pc::kBlocksPerItem, it.nBlocks - first) : 0u;
-    gp<uint8_t> o = startOf(OUT(), it.b) + (FT == 0 ? 0u : 32u + floatRawBytes(FT, it.n));  // ANS archive
-    gp<uint8_t> states = o + kANSHeaderBytes + kPdfBytes;
-    gp<uint2> bwords = (gp<uint2>)(states + uint64_t(kStateBytesPerBlock) * it.nBlocks);
+    const AnsSections arc(ansArchiveOf<FT>(startOf(OUT(), it.b), it.n), it.nBlocks);
     // a poisoned element's archive is abandoned (outSize 0): its payload
     // range is not known, so nothing more is written
     if (nk == 0 || poisonS) return;
     if (t < nk) {
       const uint32_t k = first + t;
       const uint32_t uwk = min(kBlockSize, it.n - k * kBlockSize);
-      st8(bwords + k, make_uint2((uwk << 16) | cwE[t], preE[t]));
+      st8(arc.bwords + k, make_uint2((uwk << 16) | cwE[t], preE[t]));
     }
     // payload: 16 B vectors over the item's contiguous archive range; the
     // source is the block's ring, or its slot for words spilled before the end
     // (per-wave block lists with wave-uniform block parameters measured +1
     // us)
-    gp<uint4> dst = (gp<uint4>)((gp<uint8_t>)(bwords + roundUp(it.nBlocks, 2)) + 2ull * preE[0]);
+    gp<uint4> dst = (gp<uint4>)(arc.words + preE[0]);
     const uint32_t nv = (preE[nk - 1] + roundUp(cwE[nk - 1], 8) - preE[0]) / 8;
     for (uint32_t v = t; v < nv; v += kPT) {
       const uint32_t wd = preE[0] + 8 * v;
@@ -727,10 +707,9 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t hh = halfNow();
     const uint32_t uw = laneSize(it);
     if (uw) {
-      gp<uint8_t> o = startOf(OUT(), it.b) + (FT == 0 ? 0u : 32u + floatRawBytes(FT, it.n));
-      gp<uint8_t> states = o + kANSHeaderBytes + kPdfBytes;
+      const AnsSections arc(ansArchiveOf<FT>(startOf(OUT(), it.b), it.n), it.nBlocks);
       const uint32_t blk = it.x * pc::kBlocksPerItem + 2 * w + hh;
-      ((gp<uint32_t>)(states + uint64_t(kStateBytesPerBlock) * blk))[l] = p.x;
+      ((gp<uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * blk))[l] = p.x;
     }
     if (l == 0) {
       cwE[2 * w + hh] = uw ? uint32_t(hh ? p.nout[1] : p.nout[0]) : 0u;
@@ -785,8 +764,8 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       if (hasE) encInit();
       auto encSeg = [&](uint32_t g) __attribute__((always_inline)) {
         if (encOn) {
-          if (fastE) encSegFull(g);
-          else encSegMasked(g, uwEnc);
+          if (fastE) encSegSteps(g, uwEnc, std::false_type{});
+          else encSegSteps(g, uwEnc, std::true_type{});
         }
       };
       if (loadOn) {

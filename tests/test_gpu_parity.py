@@ -142,6 +142,59 @@ def test_float_pointer_parity(C, ws, ft, pb):
         np.testing.assert_array_equal(to_np_words(o, ft), w)
 
 
+# Sizes at the edges of the kernels' index arithmetic: the decoder's 256-word
+# segment, the encoder's 512-word segment, a lone whole block in a wave's
+# pair, and the 8-block workgroup.
+EDGE_SIZES = [4096 + 255, 4096 + 256, 4096 + 257, 4096 + 511, 4096 + 512, 3 * 4096,
+              8 * 4096 - 1, 8 * 4096, 8 * 4096 + 1]
+
+
+@pytest.mark.parametrize("ft,path", [(0, "three-kernel"), (2, "three-kernel"), (4, "three-kernel"),
+                                     (0, "single-pass"), (2, "single-pass")])
+def test_segment_and_workgroup_edges(C, ws, ft, path):
+    """Bytes, bf16 and fp64 (two segments) at EDGE_SIZES, one batch per
+    format, through k_encode (three-kernel) and the single-pass compressor:
+    archives byte-equal to the oracle's, the roundtrip bit-exact, and (bf16)
+    the last 300 words of each archive by range decode."""
+    pb = 10
+    if ft == 0:
+        words = [exp_bytes(n, lam=[1, 10, 100, 1000][i % 4], seed=40 + i) for i, n in enumerate(EDGE_SIZES)]
+        ts = [torch.from_numpy(w).to(DEV) for w in words]
+        refs = [O.ans_encode(w, pb, False) for w in words]
+    else:
+        words = [float_words(ft, n, seed=50 + i) for i, n in enumerate(EDGE_SIZES)]
+        ts = [to_dev_words(w, ft) for w in words]
+        refs = [O.float_compress(w, ft, pb) for w in words]
+    with C.compress_path(path):
+        if ft == 0:
+            out, sizes = C.ans_encode_pointer(ts, prob_bits=pb, ws=ws)
+        else:
+            out, sizes = C.float_compress_pointer(ts, ft=ft, prob_bits=pb, ws=ws)
+    sizes_h = sizes.cpu().tolist()
+    host = out.cpu().numpy()
+    for i, ref in enumerate(refs):
+        assert sizes_h[i] == ref.size, (EDGE_SIZES[i], sizes_h[i], ref.size)
+        np.testing.assert_array_equal(host[i, : ref.size], ref, err_msg=f"n = {EDGE_SIZES[i]}")
+    arch = [out[i, : sizes_h[i]].clone() for i in range(len(ts))]
+    outs = [torch.empty_like(t) for t in ts]
+    if ft == 0:
+        ok, sz = C.ans_decode_pointer(arch, outs, prob_bits=pb, ws=ws)
+    else:
+        ok, sz = C.float_decompress_pointer(arch, outs, ft=ft, prob_bits=pb, ws=ws)
+    assert ok.cpu().tolist() == [1] * len(ts)
+    assert sz.cpu().tolist() == EDGE_SIZES
+    for w, o in zip(words, outs):
+        np.testing.assert_array_equal(o.cpu().numpy().view(w.dtype), w)
+    if ft == 2:
+        firsts = [n - 300 for n in EDGE_SIZES]
+        tails, ok, sz = C.float_decompress_range(arch, firsts, [300] * len(ts), dtype=torch.bfloat16,
+                                                 prob_bits=pb, ws=ws)
+        assert ok.cpu().tolist() == [1] * len(ts)
+        assert sz.cpu().tolist() == [300] * len(ts)
+        for w, t in zip(words, tails):
+            np.testing.assert_array_equal(to_np_words(t.view(torch.int16), ft), w[-300:])
+
+
 @pytest.mark.parametrize("ft", [1, 2, 3, 4])
 def test_float_checksum(C, ws, ft):
     words = [float_words(ft, n, seed=20 + i) for i, n in enumerate([1, 5000, 70000])]

@@ -22,8 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def family(name):
-    """'void dietgpu::k_decode<2, 0>(...)' -> 'k_decode<2,0>': one entry per
-    template instance, so the bf16 launches are not averaged with the byte
+    """'void dietgpu::k_decode<2, true, false, false>(...)' ->
+    'k_decode<2,true,false,false>': one entry per template instance, so the bf16 launches are not averaged with the byte
     (c3) or fp64 launches of the bench's secondary configs."""
     m = re.search(r"dietgpu::(?:\(anonymous namespace\)::)?(k_\w+)(<[^>(]*>)?", name)
     if not m:
