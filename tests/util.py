@@ -31,3 +31,181 @@ def sparsify(words, frac_zero=0.9, seed=5):
     w = words.copy()
     w[rng.random(w.size) < frac_zero] = 0
     return w
+
+
+# --------------------------------------------------------------------------
+# Adversarial content: blocks at the maximum rate beside nearly silent ones,
+# and histograms that drive every branch of the table normalisation.
+# --------------------------------------------------------------------------
+
+BLOCK = 4096
+
+# The standard rate-extreme element: both halves of a wave's block pair rare
+# (0, 1 and 20, 21), only the low half (6), only the high half (9), a rare
+# block in another 8-block workgroup (40) and a rare partial tail block with
+# no partner (64).
+STD_BLOCKS, STD_TAIL = 64, 1000
+STD_RARE = [0, 1, 6, 9, 20, 21, 40, 64]
+# A second layout for the second symbol stream of fp64, so that the two
+# streams of one wave run dry at different steps.
+STD_RARE_C1 = [1, 7, 8, 40]
+SMALL_BLOCKS, SMALL_RARE = 5, [2]
+
+
+def _block_slices(n_blocks, blocks, tail):
+    n = n_blocks * BLOCK + tail
+    for b in blocks:
+        assert 0 <= b < n_blocks or (b == n_blocks and tail > 0), b
+        yield slice(b * BLOCK, min((b + 1) * BLOCK, n))
+
+
+def rate_extreme_bytes(n_blocks, rare_blocks, tail, filler=0, max_pb=11):
+    """n_blocks * 4096 + tail bytes of `filler`, except that every listed block
+    (index n_blocks: the tail block) holds 1 + (k mod 255), k one counter that
+    runs on through the rare blocks.  Every rare symbol occurs fewer than
+    2 N / 2^max_pb times (asserted), so it quantises to pdf 1 at every
+    prob-bits up to max_pb, and keeps it unless the pdfs sum to less than
+    2^pb (the 5-block element at pb 11).  With every rare pdf 1 a full rare
+    block encodes to 4096 * pb / 16 words, the maximum, all 32 lanes emitting
+    on the same steps, and a filler block to almost none."""
+    n = n_blocks * BLOCK + tail
+    out = np.full(n, filler, dtype=np.uint8)
+    k = 0
+    for sl in _block_slices(n_blocks, rare_blocks, tail):
+        m = sl.stop - sl.start
+        out[sl] = 1 + (k + np.arange(m)) % 255
+        k += m
+    counts = np.bincount(out, minlength=256)
+    counts[filler] = 0
+    assert counts.max() * (1 << max_pb) < 2 * n, (int(counts.max()), n)
+    return out
+
+
+def rate_mirror_bytes(n_blocks, const_blocks, tail, const=7, seed=11):
+    """The mirror image of rate_extreme_bytes: uniformly random bytes (about
+    2048 words per block, the lanes out of step) except the listed blocks,
+    which hold one constant."""
+    rng = np.random.default_rng(seed)
+    out = rng.integers(0, 256, n_blocks * BLOCK + tail, dtype=np.uint8)
+    for sl in _block_slices(n_blocks, const_blocks, tail):
+        out[sl] = const
+    return out
+
+
+def std_extreme_bytes(rare=None):
+    return rate_extreme_bytes(STD_BLOCKS, STD_RARE if rare is None else rare, STD_TAIL)
+
+
+def small_extreme_bytes():
+    return rate_extreme_bytes(SMALL_BLOCKS, SMALL_RARE, 0)
+
+
+def std_mirror_bytes():
+    return rate_mirror_bytes(STD_BLOCKS, STD_RARE, STD_TAIL)
+
+
+def words_from_symbols(ft, c0, c1=None, seed=0, nonzero=False):
+    """Float words whose ANS symbol streams (pyref.float_split) are exactly
+    the bytes c0 (and, fp64, c1); every other bit is random.  fp16: the high
+    byte; bf16: bits 14..7; fp32: bits 30..23; fp64: c0 = bits 62..55, c1 =
+    bits 54..47.  nonzero: bit 0 (never a symbol bit) is set in every word."""
+    rng = np.random.default_rng(seed)
+    c0 = np.asarray(c0, dtype=np.uint8)
+    n = c0.size
+    assert (c1 is not None) == (ft == 4)
+    if ft in (1, 2):
+        r = rng.integers(0, 1 << 16, n, dtype=np.uint16)
+        c = c0.astype(np.uint16)
+        w = (c << 8) | (r & 0x00FF) if ft == 1 else (r & 0x807F) | (c << 7)
+    elif ft == 3:
+        r = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+        w = (r & np.uint32(0x807FFFFF)) | (c0.astype(np.uint32) << 23)
+    else:
+        c1 = np.asarray(c1, dtype=np.uint8)
+        assert c1.size == n
+        r = rng.integers(0, 1 << 63, n, dtype=np.uint64) << np.uint64(1) | rng.integers(0, 2, n, dtype=np.uint64)
+        keep = np.uint64((1 << 63) | ((1 << 47) - 1))
+        w = (r & keep) | (c0.astype(np.uint64) << np.uint64(55)) | (c1.astype(np.uint64) << np.uint64(47))
+    if nonzero:
+        w = w | w.dtype.type(1)
+    return w
+
+
+LARGE_FAMILIES = ("large_round_up", "large_above_2p24")
+
+
+def hard_histograms(seed=0):
+    """Named 256-entry count vectors (uint32) that drive the branches of the
+    table normalisation the stationary inputs never reach.  The two
+    LARGE_FAMILIES have totals of 32 MiB; every other total is below 200 KB."""
+    rng = np.random.default_rng(seed)
+    fam = {}
+
+    def vec(d):
+        h = np.zeros(256, dtype=np.uint32)
+        for s, c in d.items():
+            h[s] = c
+        return h
+
+    # many count-1 symbols + a few mid counts + one dominant count: the excess
+    # (one per singleton) exceeds the number of entries above 1, so there are
+    # many decrement rounds, and the mid entries reach 1 and leave the group
+    # (g shrinks from round to round)
+    h = np.zeros(256, dtype=np.uint32)
+    h[rng.permutation(256)[:200]] = 1
+    free = np.flatnonzero(h == 0)
+    for s, c in zip(free[:6], (60, 90, 150, 150, 240, 400)):
+        h[s] = c
+    h[free[6]] = 60000
+    fam["singletons_mid_dominant"] = h
+
+    # 40 equal mid counts + singletons + a dominant count: the last round
+    # decrements only part of the group of equal pdfs (the symbol id decides)
+    h = np.zeros(256, dtype=np.uint32)
+    perm = rng.permutation(256)
+    h[perm[:40]] = 700
+    h[perm[40:140]] = 1
+    h[perm[140]] = 72000
+    fam["tie_group_cut"] = h
+    # two tie groups of different pdfs
+    h = np.zeros(256, dtype=np.uint32)
+    perm = rng.permutation(256)
+    h[perm[:40]] = 500
+    h[perm[40:60]] = 1100
+    h[perm[60:190]] = 1
+    h[perm[190]] = 50000
+    fam["two_tie_groups"] = h
+
+    # 2 .. 256 symbols with counts 1 .. 3
+    for nsym in (2, 3, 17, 100, 255, 256):
+        h = np.zeros(256, dtype=np.uint32)
+        h[rng.permutation(256)[:nsym]] = rng.integers(1, 4, nsym)
+        fam[f"tiny_counts_{nsym}"] = h
+
+    # diff > 0 (equal counts whose quotient truncates), and the bumped ids
+    # 0 .. diff - 1 do not occur in the input
+    fam["bump_absent_ids"] = vec({s: 1000 for s in range(200, 211)})
+    fam["bump_absent_ids_3"] = vec({100: 3333, 180: 3333, 255: 3333})
+
+    fam["two_symbols"] = vec({10: 1, 200: 99999})
+    fam["lone_255"] = vec({255: 5000})
+    fam["squares"] = (np.arange(256, dtype=np.uint32) * 7 % 23) ** 2
+
+    # the float32 quotient rounds up across an integer at a small total: at
+    # pb 10, 1024 * fl(35016 / 40063) = 895 where the exact floor is 894.  The
+    # pdfs then sum to 1024 and nothing is bumped; with the exact floor
+    # symbol 0, which does not occur, would get pdf 1.
+    fam["small_round_up"] = vec({5: 35016, 9: 5047})
+
+    # totals above 2^24: float32(count) rounds, and at pb 10 the float32
+    # quotient of the first rounds up across an integer (1000, exactly 999)
+    fam["large_round_up"] = vec({0: 32774999, 1: 786601})
+    fam["large_above_2p24"] = vec({0: (1 << 24) + 1, 1: (1 << 24) + 3, 2: 5, 255: 1})
+    assert set(LARGE_FAMILIES) <= set(fam)
+    return fam
+
+
+def bytes_from_histogram(h, seed=0):
+    """A seeded permutation of h[s] copies of every symbol s."""
+    rng = np.random.default_rng(seed)
+    return rng.permutation(np.repeat(np.arange(256, dtype=np.uint8), np.asarray(h, dtype=np.int64)))
