@@ -809,10 +809,7 @@ void ansGetCompressedInfo(StackDeviceMemory& res, const void** in, uint32_t numI
 // u32 range is refused instead of wrapping.
 uint32_t getMaxFloatCompressedSize(FloatType ft, uint32_t size) {
   DG_CHECK(ft != FloatType::kUndefined && uint32_t(ft) <= 4, "bad float type");
-  const uint64_t n8 = roundUp64(size, 8), n16 = roundUp64(size, 16);
-  const uint64_t raw = ft == FloatType::kFloat32 ? 2 * n8 + n16
-                       : ft == FloatType::kFloat64 ? 4 * roundUp64(size, 4) + 2 * n8 : n16;
-  uint64_t base = 32ull + getMaxCompressedSize(size) + raw;
+  uint64_t base = uint64_t(kFloatHeaderBytes) + getMaxCompressedSize(size) + floatRawBytes(int(ft), uint64_t(size));
   if (ft == FloatType::kFloat64) base += getMaxCompressedSize(size);
   DG_CHECK(base <= uint64_t(UINT32_MAX), "input too large: " << size << " float words");
   return uint32_t(base);

@@ -1,8 +1,8 @@
 // Shared constants, host error handling and gfx950 wave helpers for the
-// MI355X-native rANS / float codec.  Constants restate the reference's wire
-// format (ans/GpuANSUtils.cuh:33-60, float/GpuFloatUtils.cuh:15-19) so archives
-// are interchangeable; everything else is designed for CDNA4 (wave64, LDS,
-// 8 XCDs).
+// MI355X-native rANS / float codec.  The coder's constants restate the
+// reference's (ans/GpuANSUtils.cuh:33-60) so archives are interchangeable
+// (their byte layout: archive.h); everything else is designed for CDNA4
+// (wave64, LDS, 8 XCDs).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@
 namespace dietgpu {
 
 // ---------------------------------------------------------------------------
-// wire-format constants (ans/GpuANSUtils.cuh:33-60)
+// coder constants (ans/GpuANSUtils.cuh:33-60)
 // ---------------------------------------------------------------------------
 constexpr uint32_t kNumSymbols = 256;
 constexpr uint32_t kBlockSize = 4096;         // uncompressed bytes per ANS block
@@ -23,12 +23,7 @@ constexpr int kStateBits = 31;                // state kept < 2^31
 constexpr int kEncodedBits = 16;              // u16 renormalisation words
 constexpr uint32_t kStartState = 1u << (kStateBits - kEncodedBits);
 constexpr uint32_t kMinState = 1u << (kStateBits - kEncodedBits);
-constexpr uint32_t kANSMagicVersion = 0xd00d0001u;
-constexpr uint32_t kFloatMagicVersion = 0xf00f0001u;
 constexpr uint32_t kLanesPerBlock = 32;       // interleaved states per block
-constexpr uint32_t kANSHeaderBytes = 32;
-constexpr uint32_t kPdfBytes = 2 * kNumSymbols;
-constexpr uint32_t kStateBytesPerBlock = 4 * kLanesPerBlock;
 
 // Scratch slot per encoded block.  The reference sizes it at
 // getRawCompBlockMaxSize(4096) = 5120 B, which an adversarial 11-bit block can
@@ -43,38 +38,6 @@ __host__ __device__ constexpr inline uint32_t roundUp(uint32_t a, uint32_t b) {
 }
 __host__ __device__ constexpr inline uint64_t roundUp64(uint64_t a, uint64_t b) {
   return (a + b - 1) / b * b;
-}
-
-// Symbols of block bk of an n-symbol element; 0 for a block at or past `end`
-// (the element's block count, or the end of the blocks a caller works on).
-__host__ __device__ inline uint32_t blockSymbols(uint32_t bk, uint32_t end, uint32_t n) {
-  const uint32_t left = n - bk * kBlockSize;
-  return bk < end ? (left < kBlockSize ? left : kBlockSize) : 0u;
-}
-
-// ANSCoalescedHeader::getCompressedOverhead (ans/GpuANSUtils.cuh:68-86); the
-// sections it sums are laid out by AnsSections (device.h)
-__host__ __device__ inline uint64_t ansOverhead(uint32_t numBlocks) {
-  return kANSHeaderBytes + kPdfBytes + uint64_t(kStateBytesPerBlock) * numBlocks +
-      8ull * roundUp(numBlocks, 2);
-}
-
-// Float raw-section size, FloatTypeInfo<FT>::getUncompDataSize
-// (float/GpuFloatUtils.cuh:200-391).  ft: 1 fp16, 2 bf16, 3 fp32, 4 fp64.
-__host__ __device__ inline uint32_t floatRawBytes(int ft, uint32_t n) {
-  switch (ft) {
-    case 1:
-    case 2:
-      return roundUp(n, 16);
-    case 3:
-      return 2 * roundUp(n, 8) + roundUp(n, 16);
-    default:
-      return 4 * roundUp(n, 4) + 2 * roundUp(n, 8);
-  }
-}
-
-__host__ __device__ inline uint32_t floatWordBytes(int ft) {
-  return ft <= 2 ? 2 : (ft == 3 ? 4 : 8);
 }
 
 // ---------------------------------------------------------------------------

@@ -31,7 +31,7 @@
 
 #include <type_traits>
 
-#include "device.h"
+#include "archive.h"
 
 namespace dietgpu {
 
@@ -207,11 +207,11 @@ struct Join {
       r[0] = a.x; r[1] = a.y;
     } else if constexpr (FT == 3) {
       const uint4 a = ld16(raw + 2 * i0);
-      const uint2 h = ld8(raw + 2 * roundUp(n, 8) + i0);
+      const uint2 h = ld8(raw + floatPlane2Offset(FT, n) + i0);
       r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w; r[4] = h.x; r[5] = h.y;
     } else if constexpr (FT == 4) {
       const uint4 a = ld16(raw + 4 * i0), b = ld16(raw + 4 * i0 + 16);
-      const uint4 h = ld16(raw + 4 * roundUp(n, 4) + 2 * i0);
+      const uint4 h = ld16(raw + floatPlane2Offset(FT, n) + 2 * i0);
       r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
       r[4] = b.x; r[5] = b.y; r[6] = b.z; r[7] = b.w;
       r[8] = h.x; r[9] = h.y; r[10] = h.z; r[11] = h.w;
@@ -230,11 +230,11 @@ struct Join {
       return WordT((s0 << 7) | (r >> 1) | ((r & 1u) << 15));
     } else if constexpr (FT == 3) {
       const uint32_t lo = ((gp<const uint16_t>)raw)[i];
-      const uint32_t hb = raw[2 * roundUp(n, 8) + i];
+      const uint32_t hb = raw[floatPlane2Offset(FT, n) + i];
       return rotr32((s0 << 24) | (hb << 16) | lo, 1);
     } else {
       const uint64_t lo = ((gp<const uint32_t>)raw)[i];
-      const uint64_t hb = ((gp<const uint16_t>)(raw + 4 * roundUp(n, 4)))[i];
+      const uint64_t hb = ((gp<const uint16_t>)(raw + floatPlane2Offset(FT, n)))[i];
       const uint64_t v = (uint64_t(s0) << 56) | (uint64_t(s1) << 48) | (hb << 32) | lo;
       return (v >> 1) | (v << 63);
     }
@@ -399,18 +399,19 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   uint32_t n;
   bool ok;
   if constexpr (FT == 0) {
-    n = fh[2];
-    ok = fh[0] == kANSMagicVersion;
+    n = fh[kAnsSize];
+    ok = fh[kAnsMagic] == kANSMagicVersion;
   } else {
-    n = fh[1];
-    ok = fh[0] == kFloatMagicVersion && (fh[2] & 0xfu) == uint32_t(FT);
+    n = fh[kFloatSize];
+    ok = fh[kFloatMagic] == kFloatMagicVersion && (fh[kFloatType] & kTypeMask) == uint32_t(FT);
   }
   arch[0] = ansArchiveOf<FT>(base, n);
-  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[4];
+  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[kFloatSecondAns];
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
-    ok = ok && ah[0] == kANSMagicVersion && (ah[4] & 0xfu) == uint32_t(pb) && ah[2] == n;
+    ok = ok && ah[kAnsMagic] == kANSMagicVersion && (ah[kAnsPrecision] & kTypeMask) == uint32_t(pb) &&
+         ah[kAnsSize] == n;
   }
   // range form: words [rlo, rhi) of the element, blocks [blkFirst, blkEnd)
   uint32_t rlo = 0, rhi = 0;
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   auto wholeInRange = [&](uint32_t i0) __attribute__((always_inline)) {
     return !RNG || (i0 >= rlo && i0 + dec::kChunk <= rhi);
   };
-  gp<const uint8_t> raw = base + 32;
+  gp<const uint8_t> raw = rawSectionOf(base);
   const uint32_t mask = (1u << pb) - 1;
   lp<const u32x2> lut[S];
 #pragma unroll

@@ -27,29 +27,6 @@ __device__ __forceinline__ gp<uint8_t> startOf(const BatchDesc& d, uint32_t b) {
   return G(d.start(b));
 }
 
-// The ANS archive inside element `base` of n words: the element itself for
-// raw bytes; for floats it follows the 32 B float header and the raw section
-// (fp64's second archive follows the first, float header word 4).
-template <int FT, typename B>
-__device__ __forceinline__ gp<B> ansArchiveOf(gp<B> base, uint32_t n) {
-  return base + (FT == 0 ? 0u : 32u + floatRawBytes(FT, n));
-}
-
-// The sections of the ANS archive at o that follow its header and pdf table
-// (ANSCoalescedHeader, ans/GpuANSUtils.cuh:68-86; ansOverhead, common.h, is
-// their size up to `words`).  Every kernel that writes an archive and the
-// decoder take their addresses from here.  (The decoder only reads through
-// them.)
-struct AnsSections {
-  gp<uint8_t> states;  // [nBlocks][32] u32: the blocks' final states
-  gp<uint2> bwords;    // [roundUp(nBlocks, 2)] {symbols << 16 | words, word offset}
-  gp<uint16_t> words;  // the blocks' compressed words, each padded to 8
-  __device__ __forceinline__ AnsSections(gp<const uint8_t> o, uint32_t nBlocks)
-      : states((gp<uint8_t>)o + kANSHeaderBytes + kPdfBytes),
-        bwords((gp<uint2>)(states + uint64_t(kStateBytesPerBlock) * nBlocks)),
-        words((gp<uint16_t>)(bwords + roundUp(nBlocks, 2))) {}
-};
-
 // 8 / 16-byte global accesses through native vector types (HIP's uint2 /
 // uint4 classes cannot bind address_space(1) references)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

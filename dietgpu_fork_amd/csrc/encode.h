@@ -16,7 +16,7 @@
 
 #include <type_traits>
 
-#include "device.h"
+#include "archive.h"
 #include "sync_arena.h"
 
 namespace dietgpu {
@@ -112,8 +112,8 @@ __device__ __forceinline__ void normalizeWave(uint32_t (&c)[4], uint32_t (&cdf)[
 // quotient x - 1 (x >= 16 there: renormalised states of a pdf-1 symbol are
 // >= 2^15 or >= 2^(31-pb) >> 16), and the one missing (2^pb - 1) goes into
 // z: x' = x 2^pb + cdf as the reference computes (ans/GpuANSEncode.cuh:63-89).
-// Computed at compile time for every pdf 1 <= q <= 2^11 (a 64-bit division
-// per symbol is ~100 VALU instructions).
+// The exact definition, a 64-bit division (~100 VALU instructions per
+// symbol): the host and the test hook use it, the kernels encMagicReg.
 __host__ __device__ constexpr uint32_t encMagic(uint32_t q, uint32_t* shift) {
   if (q <= 1) {
     *shift = 0;
@@ -122,18 +122,7 @@ __host__ __device__ constexpr uint32_t encMagic(uint32_t q, uint32_t* shift) {
   uint32_t l = 0;
   while ((1u << l) < q) ++l;
   *shift = l - 1;
-  return uint32_t(((1ull << (31 + l)) + q - 1) / q);
-}
-struct MagicTable {
-  uint32_t m[(1u << 11) + 1];
-  constexpr MagicTable() : m() {
-    for (uint32_t q = 1; q <= (1u << 11); ++q) {
-      uint32_t sh = 0;
-      m[q] = encMagic(q, &sh);
-    }
-  }
-};
-__device__ constexpr MagicTable kMagic{};
+  return uint32_t(((1ull << (31 + l)) + q - 1) / q);}
 
 __device__ __forceinline__ uint4 encEntryPack(uint32_t q, uint32_t cdf, uint32_t magic, uint32_t shift,
                                               int pb) {
@@ -141,20 +130,9 @@ __device__ __forceinline__ uint4 encEntryPack(uint32_t q, uint32_t cdf, uint32_t
   return make_uint4(q << (kStateBits - pb), magic, z, ((1u << pb) - q) | (shift << 24));
 }
 
-__device__ __forceinline__ uint4 encTableEntry(uint32_t q, uint32_t cdf, int pb) {
-  uint32_t shift = 0, magic = 0;
-  if (q > 1) {
-    shift = 31 - __clz(q - 1);  // ceil(log2 q) - 1
-    magic = kMagic.m[q];
-  } else if (q == 1) {
-    magic = 0xffffffffu;
-  }
-  return encEntryPack(q, cdf, magic, shift, pb);
-}
-
-// The magic of pdf q >= 2 computed in registers (no dependent global load of
-// kMagic on a latency-bound path): ceil(2^(32+shift) / q) from v_rcp_f64 and
-// two Newton steps (any seed better than 2^-8 relative then lands within one
+// The magic of pdf q >= 2 computed in registers (no dependent global load
+// from a table of magics on a latency-bound path):
+// ceil(2^(32+shift) / q) from v_rcp_f64 and two Newton steps (any seed better than 2^-8 relative then lands within one
 // of the quotient: it is below 2^32), and an exact fix-up -- the remainder
 // 2^(32+shift) - m q is an integer below 2^13 in magnitude, so one fma yields
 // it exactly.  About a quarter of the IEEE double division it replaced
@@ -188,7 +166,7 @@ __device__ __forceinline__ uint32_t encMagicReg(uint32_t q, uint32_t shift) {
 __device__ __forceinline__ uint4 encTableEntryReg(uint32_t q, uint32_t cdf, int pb) {
   uint32_t shift = 0, magic = 0;
   if (q > 1) {
-    shift = 31 - __clz(q - 1);
+    shift = 31 - __clz(q - 1);  // ceil(log2 q) - 1
     magic = encMagicReg(q, shift);
   } else if (q == 1) {
     magic = 0xffffffffu;
@@ -199,7 +177,7 @@ __device__ __forceinline__ uint4 encTableEntryReg(uint32_t q, uint32_t cdf, int 
 // ---------------------------------------------------------------------------
 // Normalisation of one (element, segment): sums the partial histograms,
 // normalises (normalizeWave) and stores the encode table rows
-// (encTableEntry) and the u16 pdf.  Run by k_normalize, or -- one launch
+// (encTableEntryReg) and the u16 pdf.  Run by k_normalize, or -- one launch
 // fewer -- by the last workgroup to finish an element in the kernel that
 // writes its final partial rows (k_hist or k_histReduce: NormArgs::arrive,
 // the classic last-block reduction: every workgroup counts itself in after
@@ -692,7 +670,7 @@ __device__ __forceinline__ void splitVec(const uint4& v, uint32_t i0, uint32_t n
     if (store) {
       st8(raw + 2 * i0, make_uint2(__builtin_amdgcn_perm(r[1], r[0], 0x05040100u),
                                    __builtin_amdgcn_perm(r[3], r[2], 0x05040100u)));
-      *(gp<uint32_t>)(raw + 2 * roundUp(n, 8) + i0) =
+      *(gp<uint32_t>)(raw + floatPlane2Offset(FT, n) + i0) =
           (__builtin_amdgcn_perm(r[1], r[0], 0x06020602u) & 0xffffu) |
           (__builtin_amdgcn_perm(r[3], r[2], 0x06020602u) << 16);
     }
@@ -701,7 +679,7 @@ __device__ __forceinline__ void splitVec(const uint4& v, uint32_t i0, uint32_t n
     *(lp<uint16_t>)sym0 = uint16_t((r0 >> 56) | ((r1 >> 56) << 8));
     *(lp<uint16_t>)sym1 = uint16_t(((r0 >> 48) & 0xffu) | (((r1 >> 48) & 0xffu) << 8));
     st8(raw + 4 * i0, make_uint2(uint32_t(r0), uint32_t(r1)));
-    *(gp<uint32_t>)(raw + 4 * roundUp(n, 4) + 2 * i0) =
+    *(gp<uint32_t>)(raw + floatPlane2Offset(FT, n) + 2 * i0) =
         uint32_t((r0 >> 32) & 0xffffu) | (uint32_t((r1 >> 32) & 0xffffu) << 16);
   }
 }
@@ -722,13 +700,13 @@ __device__ __forceinline__ void splitOne(typename FloatTraits<FT>::WordT w, uint
     const uint32_t v = rotl32(w, 1);
     *sym0 = uint8_t(v >> 24);
     ((gp<uint16_t>)raw)[i] = uint16_t(v);
-    raw[2 * roundUp(n, 8) + i] = uint8_t(v >> 16);
+    raw[floatPlane2Offset(FT, n) + i] = uint8_t(v >> 16);
   } else {
     const uint64_t v = rotl64(w, 1);
     *sym0 = uint8_t(v >> 56);
     *sym1 = uint8_t(v >> 48);
     ((gp<uint32_t>)raw)[i] = uint32_t(v);
-    ((gp<uint16_t>)(raw + 4 * roundUp(n, 4)))[i] = uint16_t(v >> 32);
+    ((gp<uint16_t>)(raw + floatPlane2Offset(FT, n)))[i] = uint16_t(v >> 32);
   }
 }
 
@@ -815,7 +793,7 @@ struct EncTail {
   uint32_t spinCap = 1u << 24;  // look-back polls before the element is poisoned
   uint32_t* err = nullptr;      // device error word (poisoned elements)
   // sparse archives: element sizes whose header + bitmap precede this dense
-  // archive (sparseOverhead), added to outSize; null otherwise
+  // archive (sparsePrefixBytes), added to outSize; null otherwise
   const uint32_t* sparseN = nullptr;
   uint32_t skew = 0;  // test hook: emulated out-of-order start (skewDelay, device.h)
   uint32_t epoch = 0;  // this call's epoch: the flags are epoch-tagged (sync arena), never zeroed
@@ -878,12 +856,6 @@ __device__ __forceinline__ void proNormalize(gp<const uint32_t> rows, uint32_t P
   }
 }
 
-// bytes of a sparse archive before its dense part: 16 B header, bitmap
-// padded to 16 (float/GpuSparseFloatCompress.cuh)
-__device__ __forceinline__ uint64_t sparseOverhead(const uint32_t* sparseN, uint32_t b) {
-  return sparseN ? 16ull + roundUp64((uint64_t(sparseN[b]) + 7) / 8, 16) : 0ull;
-}
-
 constexpr uint64_t kFlagAgg = 1ull << 62;
 constexpr uint64_t kFlagPrefix = 2ull << 62;
 constexpr uint64_t kFlagPoisonE = 1ull << 61;
@@ -937,65 +909,6 @@ __device__ __forceinline__ uint32_t lookBackPoison(gp<uint64_t> f, uint32_t x, u
     __hip_atomic_store(f + x, kFlagPrefix | (poison ? kFlagPoisonE : 0ull) | tag | uint64_t(excl + agg),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return excl;
-}
-
-// Header fields known before encoding (all but the word totals): ANS header
-// words 0-2 and 4-7, the pdf table, float header words 0-3 and 5-7, and the
-// raw section's rounding tails.  Whole workgroup.
-template <int FT>
-__device__ __forceinline__ void writeHeadFixed(gp<uint8_t> base, gp<uint8_t> o, uint32_t n, uint32_t nBlocks,
-                               const EncTail& t, uint32_t b, uint16_t pdfOfTid) {
-  const uint32_t tid = threadIdx.x;
-  const bool ansCk = FT == 0 && t.useChecksum;
-  if (tid == 0) {
-    gp<uint32_t> hdr = (gp<uint32_t>)o;
-    hdr[0] = kANSMagicVersion;
-    hdr[1] = nBlocks;
-    hdr[2] = n;
-    hdr[4] = uint32_t(t.pb) | (ansCk ? 0x10u : 0u);
-    hdr[5] = ansCk ? G(t.ck)[b] : 0u;
-    hdr[6] = 0;
-    hdr[7] = 0;
-    if constexpr (FT != 0) {
-      gp<uint32_t> fh = (gp<uint32_t>)base;
-      fh[0] = kFloatMagicVersion;
-      fh[1] = n;
-      fh[2] = uint32_t(FT) | (t.useChecksum ? 0x10u : 0u);
-      fh[3] = t.useChecksum ? G(t.ck)[b] : 0u;
-      fh[5] = 0;
-      fh[6] = 0;
-      fh[7] = 0;
-    }
-  }
-  ((gp<uint16_t>)(o + kANSHeaderBytes))[tid] = pdfOfTid;
-  if constexpr (FT != 0) {
-    if (tid < 16) {
-      gp<uint8_t> raw = base + 32;
-      if constexpr (FT == 1 || FT == 2) {
-        if (n + tid < roundUp(n, 16)) raw[n + tid] = 0;
-      } else {
-        static_assert(FT == 3, "single-segment float formats only");
-        if (n + tid < roundUp(n, 8)) ((gp<uint16_t>)raw)[n + tid] = 0;
-        if (n + tid < roundUp(n, 16)) raw[2 * roundUp(n, 8) + n + tid] = 0;
-      }
-    }
-  }
-}
-
-// The fields that need the element's word total (last workgroup, one lane).
-template <int FT>
-__device__ __forceinline__ void writeHeadTotal(gp<uint8_t> base, gp<uint8_t> o, uint32_t n, uint32_t nBlocks,
-                               uint32_t totalWords, gp<uint2> bwords, const EncTail& t, uint32_t b) {
-  ((gp<uint32_t>)o)[3] = totalWords;
-  if (nBlocks & 1) st8(bwords + nBlocks, make_uint2(0, 0));
-  const uint64_t ansBytes = ansOverhead(nBlocks) + 2ull * totalWords;
-  uint64_t sz = ansBytes;
-  if constexpr (FT != 0) {
-    ((gp<uint32_t>)base)[4] = uint32_t(roundUp64(ansBytes, 16));  // GpuFloatHeader2
-    sz += 32ull + floatRawBytes(FT, n);
-  }
-  sz += sparseOverhead(t.sparseN, b);
-  if (t.outSize) G(t.outSize)[b] = uint32_t(sz);
 }
 
 // grid (max(1, ceil(MB / kBlocksPerWG)), batch).  Single-segment formats
@@ -1065,7 +978,7 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
   asm volatile("" : "+v"(hv));  // keep `hv & x` a v_and
 
   gp<const WordT> src = (gp<const WordT>)startOf(in, b);
-  gp<uint8_t> raw = FT == 0 ? gp<uint8_t>(nullptr) : startOf(out, b) + 32;
+  gp<uint8_t> raw = FT == 0 ? gp<uint8_t>(nullptr) : rawSectionOf(startOf(out, b));
   const bool vecIn = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
 
   // the wave's pair: blocks blk0 (lanes 0-31) and blk0 + 1 (lanes 32-63)
@@ -1236,23 +1149,21 @@ __global__ __launch_bounds__(enc::kThreads) void k_encode(BatchDesc in, BatchDes
       bool pz = false;
       const uint32_t excl = lookBackPoison(G(tail.flags) + uint64_t(b) * tail.nW, wx, agg, tail.epoch, tail.spinCap, pz);
       if (lane < nk) preE[lane] = excl + inc - r;
-      if (lane == 0 && (first + Cfg::kBlocksPerWG >= nBlocks)) {
-        if (pz) {
-          if (tail.outSize) G(tail.outSize)[b] = 0u;
-          __hip_atomic_fetch_add(G(tail.err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          writeHeadTotal<FT>(base, o, n, nBlocks, excl + agg, arc.bwords, tail, b);
-        }
-      }
+      if (lane == 0 && (first + Cfg::kBlocksPerWG >= nBlocks))
+        closeElement<FT>(base, n, nBlocks, pz, excl + agg, 0, tail.outSize, tail.sparseN, b, tail.err);
     }
-    if (wx == 0)
-      writeHeadFixed<FT>(base, o, n, nBlocks, tail, b,
-                         kPro ? pdfS[0][tid] : G(tail.pdf)[uint64_t(b) * kNumSymbols + tid]);
+    if (wx == 0) {
+      // what is known before encoding: the header(s) but for the word total,
+      // the pdf table and the raw section's rounding tails
+      if (tid == 0)
+        writeHeaders<FT>(base, o, n, nBlocks, tail.pb, tail.useChecksum, tail.useChecksum ? G(tail.ck)[b] : 0u);
+      ((gp<uint16_t>)(o + kANSHeaderBytes))[tid] = kPro ? pdfS[0][tid] : G(tail.pdf)[uint64_t(b) * kNumSymbols + tid];
+      zeroRawTails<FT>(base, n, tid);
+    }
     __syncthreads();
     if (tid < nk) {
       const uint32_t k = first + tid;
-      const uint32_t uwk = min(kBlockSize, n - k * kBlockSize);
-      st8(arc.bwords + k, make_uint2((uwk << 16) | cwE[tid], preE[tid]));
+      st8(arc.bwords + k, blockWordsEntry(n, k, cwE[tid], preE[tid]));
     }
     copyPayload<R>(preE, cwE, nk, G(slots) + (uint64_t(b) * MB + first) * kSlotBytes + kStateBytesPerBlock,
                    (gp<uint8_t>)arc.words, &ringS[0][0], flE);
@@ -1327,21 +1238,15 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
     base = e * cp.encBlocks;
     if (e > 0) flagBefore = flagOf(seg, e - 1);
     if (bad) {  // an encoder look-back gave up: the element is abandoned
-      if (blockIdx.x == 0 && seg == 0 && tid == 0) {
-        if (outSize) G(outSize)[b] = 0u;
-        __hip_atomic_fetch_add(G(cp.err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (blockIdx.x == 0 && seg == 0 && tid == 0)
+        closeElement<FT>(startOf(out, b), n, nBlocks, true, 0, 0, outSize, sparseN, b, cp.err);
       return;
     }
   }
 
   gp<uint8_t> o = ansArchiveOf<FT>(startOf(out, b), n);
-  uint32_t total0Words = 0;
-  if constexpr (FT != 0) {
-    if (kSegs == 2 && (seg == 1 || blockIdx.x == 0)) {
-      total0Words = fromFlags ? segTotal[0] : sumRoundedWords(cw0, nBlocks, red);
-      if (seg == 1) o += roundUp64(ansOverhead(nBlocks) + 2ull * total0Words, 16);
-    }
+  if constexpr (kSegs == 2) {
+    if (seg == 1) o += secondAnsOffset(nBlocks, fromFlags ? segTotal[0] : sumRoundedWords(cw0, nBlocks, red));
   }
   const AnsSections arc(o, nBlocks);
 
@@ -1357,57 +1262,22 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
   __syncthreads();
 
   if (blockIdx.x == 0) {
-    const uint32_t totalWords = fromFlags ? segTotal[seg] : sumRoundedWords(cwS, nBlocks, red);
-    uint32_t total1Words = 0;
-    if (kSegs == 2 && seg == 0)
-      total1Words = fromFlags ? segTotal[1] : sumRoundedWords(cwS + uint64_t(numInBatch) * MB, nBlocks, red);
-    const uint64_t ansBytes = ansOverhead(nBlocks) + 2ull * totalWords;
-    if (tid == 0) {
-      gp<uint32_t> hdr = (gp<uint32_t>)o;
-      const bool ansCk = FT == 0 && useChecksum;
-      hdr[0] = kANSMagicVersion;
-      hdr[1] = nBlocks;
-      hdr[2] = n;
-      hdr[3] = totalWords;
-      hdr[4] = uint32_t(pb) | (ansCk ? 0x10u : 0u);
-      hdr[5] = ansCk ? G(ck)[b] : 0u;
-      hdr[6] = 0;
-      hdr[7] = 0;
-      if (nBlocks & 1) st8(arc.bwords + nBlocks, make_uint2(0, 0));
-      if constexpr (FT == 0) {
-        if (outSize) G(outSize)[b] = uint32_t(ansBytes);
-      } else if (seg == 0) {
-        gp<uint32_t> fh = (gp<uint32_t>)startOf(out, b);
-        fh[0] = kFloatMagicVersion;
-        fh[1] = n;
-        fh[2] = uint32_t(FT) | (useChecksum ? 0x10u : 0u);
-        fh[3] = useChecksum ? G(ck)[b] : 0u;
-        fh[4] = uint32_t(roundUp64(ansBytes, 16));  // GpuFloatHeader2
-        fh[5] = 0;
-        fh[6] = 0;
-        fh[7] = 0;
-        uint64_t sz = 32ull + floatRawBytes(FT, n) + ansBytes;
-        if (kSegs == 2) sz += ansOverhead(nBlocks) + 2ull * total1Words;
-        sz += sparseOverhead(sparseN, b);
-        if (outSize) G(outSize)[b] = uint32_t(sz);
+    // segment 0: the element's header(s), raw tails, and every segment's
+    // word total with the element's size; segment 1: its own ANS header
+    if (seg == 0) {
+      uint32_t total[2] = {0, 0};
+#pragma unroll
+      for (int s = 0; s < kSegs; ++s)
+        total[s] = fromFlags ? segTotal[s] : sumRoundedWords(cw0 + uint64_t(s) * numInBatch * MB, nBlocks, red);
+      if (tid == 0) {
+        writeHeaders<FT>(startOf(out, b), o, n, nBlocks, pb, useChecksum, useChecksum ? G(ck)[b] : 0u);
+        closeElement<FT>(startOf(out, b), n, nBlocks, false, total[0], total[1], outSize, sparseN, b, cp.err);
       }
+      zeroRawTails<FT>(startOf(out, b), n, tid);
+    } else if (tid == 0) {
+      writeAnsHeader(o, nBlocks, n, pb, false, 0u);
     }
     ((gp<uint16_t>)(o + kANSHeaderBytes))[tid] = G(pdf)[(uint64_t(seg) * numInBatch + b) * kNumSymbols + tid];
-    // zero the raw section's rounding tails (reference: uninitialised)
-    if constexpr (FT != 0) {
-      if (seg == 0 && tid < 16) {
-        gp<uint8_t> raw = startOf(out, b) + 32;
-        if constexpr (FT == 1 || FT == 2) {
-          if (n + tid < roundUp(n, 16)) raw[n + tid] = 0;
-        } else if constexpr (FT == 3) {
-          if (n + tid < roundUp(n, 8)) ((gp<uint16_t>)raw)[n + tid] = 0;
-          if (n + tid < roundUp(n, 16)) raw[2 * roundUp(n, 8) + n + tid] = 0;
-        } else {
-          if (n + tid < roundUp(n, 4)) ((gp<uint32_t>)raw)[n + tid] = 0;
-          if (n + tid < roundUp(n, 8)) ((gp<uint16_t>)(raw + 4 * roundUp(n, 4)))[n + tid] = 0;
-        }
-      }
-    }
   }
 
   // per block: states (32 lanes) and the blockWords entry
@@ -1418,10 +1288,7 @@ __global__ __launch_bounds__(kThreads) void k_coalesce(
     gp<const uint8_t> slot = G(slots) + ((uint64_t(seg) * numInBatch + b) * MB + k) * kSlotBytes;
     if (lane < 32)
       ((gp<uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * k))[lane] = ((gp<const uint32_t>)slot)[lane];
-    if (lane == 32) {
-      const uint32_t uwk = (k + 1 < nBlocks || n % kBlockSize == 0) ? kBlockSize : n % kBlockSize;
-      st8(arc.bwords + k, make_uint2((uwk << 16) | cwS[k], pre[k - first]));
-    }
+    if (lane == 32) st8(arc.bwords + k, blockWordsEntry(n, k, cwS[k], pre[k - first]));
   }
   __syncthreads();
   const uint32_t nk = last > first ? last - first : 0;
@@ -1464,14 +1331,15 @@ static __global__ void k_info(BatchDesc in, uint32_t numInBatch, bool isFloat,
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= numInBatch) return;
   gp<const uint32_t> h = (gp<const uint32_t>)startOf(in, b);
-  const bool ok = h[0] == (isFloat ? kFloatMagicVersion : kANSMagicVersion);
+  static_assert(kFloatMagic == kAnsMagic, "one magic word");
+  const bool ok = h[kAnsMagic] == (isFloat ? kFloatMagicVersion : kANSMagicVersion);
   if (isFloat) {
-    if (sizes) G(sizes)[b] = ok ? h[1] : 0u;
-    if (types) G(types)[b] = ok ? (h[2] & 0xfu) : 0u;
-    if (checksums) G(checksums)[b] = h[3];
+    if (sizes) G(sizes)[b] = ok ? h[kFloatSize] : 0u;
+    if (types) G(types)[b] = ok ? (h[kFloatType] & kTypeMask) : 0u;
+    if (checksums) G(checksums)[b] = h[kFloatChecksum];
   } else {
-    if (sizes) G(sizes)[b] = ok ? h[2] : 0u;
-    if (checksums) G(checksums)[b] = h[5];
+    if (sizes) G(sizes)[b] = ok ? h[kAnsSize] : 0u;
+    if (checksums) G(checksums)[b] = h[kAnsChecksum];
   }
 }
 

@@ -580,8 +580,6 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     (void)lane;
     const uint32_t first = it.x * pc::kBlocksPerItem;
     const uint32_t nk = first < it.nBlocks ? min(pc::kBlocksPerItem, it.nBlocks - first) : 0u;
-    gp<uint8_t> base = startOf(OUT(), it.b);
-    gp<uint8_t> o = ansArchiveOf<FT>(base, it.n);
     const uint32_t r = lane < nk ? roundUp(cwE[lane], 8) : 0u;
     const uint32_t inc = waveInclusiveScan(r);
     const uint32_t agg = readfirst(__shfl(inc, 63));
@@ -590,16 +588,9 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     if (lane < nk) preE[lane] = excl + inc - r;
     if (lane == 0) {
       poisonS = pz ? 1u : 0u;
-      if (it.x == it.team - 1) {
-        if (pz) {
-          if (A().outSize) G(A().outSize)[it.b] = 0u;
-          __hip_atomic_fetch_add(G(A().err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          EncTail t{nullptr, nullptr, A().outSize, nullptr, 0, A().pb, A().useChecksum};
-          t.sparseN = A().sparseN;
-          writeHeadTotal<FT>(base, o, it.n, it.nBlocks, excl + agg, AnsSections(o, it.nBlocks).bwords, t, it.b);
-        }
-      }
+      if (it.x == it.team - 1)
+        closeElement<FT>(startOf(OUT(), it.b), it.n, it.nBlocks, pz, excl + agg, 0, A().outSize, A().sparseN, it.b,
+                         A().err);
     }
   };
 
@@ -612,26 +603,28 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     (void)lane;
     gp<uint8_t> base = startOf(OUT(), it.b);
     gp<uint8_t> o = ansArchiveOf<FT>(base, it.n);
+    // (writeHeaders' stores, archive.h, spelled out: through the shared
+    // function, whatever its call shape, the register allocator spills
+    // differently in the bf16 / fp32 instances)
     if (lane == 0) {
       const bool ansCk = FT == 0 && A().useChecksum;
       if (FT != 0) ckv = A().ckIn ? G(A().ckIn)[it.b] : 0u;
-      gp<uint32_t> hdr = (gp<uint32_t>)o;
-      hdr[0] = kANSMagicVersion;
-      hdr[1] = it.nBlocks;
-      hdr[2] = it.n;
-      hdr[4] = uint32_t(A().pb) | (ansCk ? 0x10u : 0u);
-      hdr[5] = ansCk ? ckv : 0u;
-      hdr[6] = 0;
-      hdr[7] = 0;
+      gp<uint32_t> ah = (gp<uint32_t>)o;
+      ah[kAnsMagic] = kANSMagicVersion;
+      ah[kAnsBlocks] = it.nBlocks;
+      ah[kAnsSize] = it.n;
+      ah[kAnsPrecision] = uint32_t(A().pb) | (ansCk ? kChecksumFlag : 0u);
+      ah[kAnsChecksum] = ansCk ? ckv : 0u;
+#pragma unroll
+      for (uint32_t w = kAnsZeros; w < kANSHeaderBytes / 4; ++w) ah[w] = 0;
       if constexpr (FT != 0) {
         gp<uint32_t> fh = (gp<uint32_t>)base;
-        fh[0] = kFloatMagicVersion;
-        fh[1] = it.n;
-        fh[2] = uint32_t(FT) | (A().useChecksum ? 0x10u : 0u);
-        fh[3] = A().useChecksum ? ckv : 0u;
-        fh[5] = 0;
-        fh[6] = 0;
-        fh[7] = 0;
+        fh[kFloatMagic] = kFloatMagicVersion;
+        fh[kFloatSize] = it.n;
+        fh[kFloatType] = uint32_t(FT) | (A().useChecksum ? kChecksumFlag : 0u);
+        fh[kFloatChecksum] = A().useChecksum ? ckv : 0u;
+#pragma unroll
+        for (uint32_t w = kFloatZeros; w < kFloatHeaderBytes / 4; ++w) fh[w] = 0;
       }
     }
     // pdf: 4 symbols per lane, one 8 B store
@@ -639,18 +632,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       const u32x2 pd = *(lp<const u32x2>)&pdfS[4 * lane];
       *(gp<u32x2>)((gp<uint8_t>)(o + kANSHeaderBytes) + 8 * lane) = pd;
     }
-    if constexpr (FT != 0) {
-      gp<uint8_t> raw = base + 32;
-      const uint32_t n = it.n;
-      if (lane < 16) {
-        if constexpr (FT == 1 || FT == 2) {
-          if (n + lane < roundUp(n, 16)) raw[n + lane] = 0;
-        } else {
-          if (n + lane < roundUp(n, 8)) ((gp<uint16_t>)raw)[n + lane] = 0;
-          if (n + lane < roundUp(n, 16)) raw[2 * roundUp(n, 8) + n + lane] = 0;
-        }
-      }
-    }
+    zeroRawTails<FT>(base, it.n, lane);
   };
 
   // ---- placement of E by waves 1-3 (t = tid - 64 of 192), after the
@@ -669,8 +651,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     if (nk == 0 || poisonS) return;
     if (t < nk) {
       const uint32_t k = first + t;
-      const uint32_t uwk = min(kBlockSize, it.n - k * kBlockSize);
-      st8(arc.bwords + k, make_uint2((uwk << 16) | cwE[t], preE[t]));
+      st8(arc.bwords + k, blockWordsEntry(it.n, k, cwE[t], preE[t]));
     }
     // payload: 16 B vectors over the item's contiguous archive range; the
     // source is the block's ring, or its slot for words spilled before the end
@@ -760,7 +741,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       const bool fullL = uwL1 == kBlockSize;
       const uint32_t uwL = halfNow() ? uwL1 : uwL0;
       const gp<const WordT> srcL = srcOf(L);
-      gp<uint8_t> rawL = FT == 0 ? gp<uint8_t>(nullptr) : startOf(OUT(), L.b) + 32;
+      gp<uint8_t> rawL = FT == 0 ? gp<uint8_t>(nullptr) : rawSectionOf(startOf(OUT(), L.b));
       if (hasE) encInit();
       auto encSeg = [&](uint32_t g) __attribute__((always_inline)) {
         if (encOn) {

@@ -121,7 +121,7 @@ __device__ __forceinline__ void sparseCountTile(const BatchDesc& in, gp<uint8_t>
     // the wave's kSteps bitmap words in one store; then zero the 16-byte
     // padding after the element's last bitmap word
     const uint32_t i0 = t0 + w * (kTileWords / kWaves) + 64 * lane;
-    gp<uint64_t> dst = (gp<uint64_t>)(o + 16 + i0 / 8);
+    gp<uint64_t> dst = (gp<uint64_t>)(o + kSparseHeaderBytes + i0 / 8);
     if (lane < kSteps && i0 < n) {
       dst[0] = bmLane;
       if (i0 + 64 >= n && i0 / 8 + 8 < bmPad) dst[1] = 0;
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
   const uint32_t tile = blockIdx.x;
   const uint32_t tid = threadIdx.x;
   gp<uint8_t> o = startOf(outD, b);
-  if (tile == 0 && tid == 0) st16(o, make_uint4(n, 0, 0, 0));
+  if (tile == 0 && tid == 0) writeSparseHeader(o, n);
   const uint32_t t0 = tile * kTileWords;
   if (t0 >= n) {
     if (tid == 0) tileCounts[uint64_t(b) * tilesPerElem + tile] = 0;
@@ -327,16 +327,16 @@ __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_
   __shared__ uint32_t red[kWaves];
   const uint32_t b = batchOffset + blockIdx.y;
   gp<const uint8_t> a = (gp<const uint8_t>)in.start(b);
-  const uint32_t n = ((gp<const uint32_t>)a)[0];
+  const uint32_t n = ((gp<const uint32_t>)a)[kSparseSize];
   const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
   if (c == 0) {
-    densePtrs[b] = reinterpret_cast<uint64_t>(in.start(b) + 16 + roundUp((n + 7) / 8, 16));
+    densePtrs[b] = reinterpret_cast<uint64_t>(in.start(b) + sparsePrefixBytes(n));
     sizes[b] = n;
   }
   uint32_t cnt = 0;
   const uint32_t i0 = c * kChunkWords;
   if (c < chunksPerElem && i0 < n) {
-    gp<const uint64_t> bm = (gp<const uint64_t>)(a + 16) + uint64_t(c) * (kChunkWords / 64);
+    gp<const uint64_t> bm = (gp<const uint64_t>)(a + kSparseHeaderBytes) + uint64_t(c) * (kChunkWords / 64);
     uint64_t v[kChunkWords / 64];
 #pragma unroll
     for (uint32_t k = 0; k < kChunkWords / 64; ++k) v[k] = i0 + 64 * k < n ? bm[k] : 0ull;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   const uint32_t c = blockIdx.x * kWaves + w;
   const uint32_t i0 = c * kChunkWords;
   if (!ok || c >= chunksPerElem || i0 >= n) return;
-  gp<const uint8_t> bm = (gp<const uint8_t>)in.start(b) + 16;
+  gp<const uint8_t> bm = (gp<const uint8_t>)in.start(b) + kSparseHeaderBytes;
   uint64_t mv = 0;
   if (lane < kRows && i0 + 64 * lane < n) {
     mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
@@ -571,7 +571,7 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
 }  // namespace
 
 uint32_t getMaxSparseFloatCompressedSize(FloatType ft, uint32_t size) {
-  const uint64_t v = 16ull + roundUp64((uint64_t(size) + 7) / 8, 16) + getMaxFloatCompressedSize(ft, size);
+  const uint64_t v = sparsePrefixBytes(size) + getMaxFloatCompressedSize(ft, size);
   DG_CHECK(v <= uint64_t(UINT32_MAX), "input too large: " << size << " float words");
   return uint32_t(v);
 }
@@ -593,7 +593,7 @@ void floatCompressSparse(StackDeviceMemory& res, const FloatCompressConfig& conf
   for (uint32_t i = 0; i < numInBatch; ++i) {
     DG_CHECK(op[i] % 16 == 0, "out[i] must be 16-byte aligned");
     DG_CHECK(ip[i] % ws == 0, "input not word aligned");
-    dp[i] = op[i] + 16 + roundUp((sz.sizes[i] + 7) / 8, 16);
+    dp[i] = op[i] + sparsePrefixBytes(sz.sizes[i]);
   }
   const auto t = uploadTables(res, stream, {&ip, &op, &dp}, sz.sizes, true);
   const DeviceDescs dd(res, stream, &t, numInBatch);

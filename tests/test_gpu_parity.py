@@ -195,6 +195,70 @@ def test_segment_and_workgroup_edges(C, ws, ft, path):
             np.testing.assert_array_equal(to_np_words(t.view(torch.int16), ft), w[-300:])
 
 
+# 1, 2 and 3 blocks (both parities of the block-words pad entry); n mod 16 =
+# 1, 9, 7, so every plane of every float type's raw section has a rounding tail.
+HEADER_SIZES = [1, 4096 + 9, 2 * 4096 + 7]
+FLOAT_DTYPE = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
+
+
+@pytest.mark.parametrize("checksum", [False, True])
+@pytest.mark.parametrize("ft,path", [(ft, "three-kernel") for ft in range(5)] +
+                                    [(ft, "single-pass") for ft in range(4)])
+def test_headers_and_tails_into_dirty_buffers(C, ws, ft, path, checksum):
+    """Every (route, format, checksum) writes each header word, the raw
+    section's rounding tails, the block-words pad entry and the size itself:
+    the archive and its size land in buffers pre-filled with 0xA5 / -1 and
+    must equal the oracle's byte for byte, decode bit-exactly, and have been
+    written by the route asked for (one element per call in a row whose
+    stride is a multiple of 16 bytes: the single-pass route takes nothing
+    else)."""
+    pb = 10
+
+    def one_row(x):  # [1, n] view of a fresh row padded to 16 words
+        row = torch.zeros([1, (x.numel() + 15) // 16 * 16], dtype=x.dtype, device=DEV)
+        row[0, : x.numel()] = x
+        return row[:, : x.numel()]
+
+    C.profile_filter(None)
+    C.profile(True)
+    try:
+        for i, n in enumerate(HEADER_SIZES):
+            if ft == 0:
+                w = exp_bytes(n, lam=[1, 10, 100][i], seed=60 + i)
+                t = one_row(torch.from_numpy(w).to(DEV))
+                ref = O.ans_encode(w, pb, checksum)
+                cols = C.max_compressed_size(n)
+            else:
+                w = float_words(ft, n, seed=70 + i)
+                t = one_row(to_dev_words(w, ft))
+                ref = O.float_compress(w, ft, pb, checksum)
+                cols = C.max_float_compressed_size(ft, n)
+            out = torch.full([1, cols], 0xA5, dtype=torch.uint8, device=DEV)
+            sizes = torch.full([1], -1, dtype=torch.int32, device=DEV)
+            C.profile_reset()
+            with C.compress_path(path):
+                if ft == 0:
+                    C.ans_encode_stride(t, prob_bits=pb, checksum=checksum, ws=ws, out=out, sizes=sizes)
+                else:
+                    C.float_compress_stride(t, ft=ft, prob_bits=pb, checksum=checksum, ws=ws, out=out, sizes=sizes)
+            if path == "single-pass":
+                assert C.profile_query("compress")[1] == 1, n
+            else:
+                assert C.profile_query("encode")[1] >= 1, n
+                assert C.profile_query("compress")[1] == 0, n
+            assert int(sizes[0]) == ref.size, (n, int(sizes[0]), ref.size)
+            np.testing.assert_array_equal(out[0, : ref.size].cpu().numpy(), ref, err_msg=f"n = {n}")
+            if ft == 0:
+                dec, ok, sz = C.ans_decode_stride(out, n, prob_bits=pb, checksum=checksum, ws=ws)
+            else:
+                dec, ok, sz = C.float_decompress_stride(out, n, FLOAT_DTYPE[ft], prob_bits=pb, checksum=checksum,
+                                                        ws=ws)
+            assert ok.cpu().tolist() == [1] and sz.cpu().tolist() == [n]
+            np.testing.assert_array_equal(dec[0].view(t.dtype).cpu().numpy().view(w.dtype), w)
+    finally:
+        C.profile(False)
+
+
 @pytest.mark.parametrize("ft", [1, 2, 3, 4])
 def test_float_checksum(C, ws, ft):
     words = [float_words(ft, n, seed=20 + i) for i, n in enumerate([1, 5000, 70000])]

@@ -20,6 +20,31 @@
 
 using namespace dietgpu;
 
+// The table form measured here (the product computes the magic in registers,
+// encTableEntryReg): encMagic of every pdf 1 <= q <= 2^11 at compile time, in
+// global memory.
+struct MagicTable {
+  uint32_t m[(1u << 11) + 1];
+  constexpr MagicTable() : m() {
+    for (uint32_t q = 1; q <= (1u << 11); ++q) {
+      uint32_t sh = 0;
+      m[q] = encMagic(q, &sh);
+    }
+  }
+};
+__device__ constexpr MagicTable kMagic{};
+
+__device__ __forceinline__ uint4 encTableEntry(uint32_t q, uint32_t cdf, int pb) {
+  uint32_t shift = 0, magic = 0;
+  if (q > 1) {
+    shift = 31 - __clz(q - 1);  // ceil(log2 q) - 1
+    magic = kMagic.m[q];
+  } else if (q == 1) {
+    magic = 0xffffffffu;
+  }
+  return encEntryPack(q, cdf, magic, shift, pb);
+}
+
 __device__ __forceinline__ uint32_t magicRcp(uint32_t q, uint32_t shift) {
   const uint64_t num = 1ull << (32 + shift);
   uint64_t m = uint64_t(double(num) * __builtin_amdgcn_rcp(double(q)));
