@@ -75,7 +75,7 @@ def main():
         ref = np.frombuffer(bytes(pyref.float_compress(2, w, pb, checksum=True, word_bytes=w.view(np.uint8))), dtype=np.uint8)
         assert np.array_equal(arch, ref), f"oracle/pyref disagree: bf16 pb{pb}"
         fx[f"f2_pb{pb}_ck1"] = arch
-    # sparse (oracle only: pyref has no sparse path; decode round trip checked)
+    # sparse
     for ft in (2, 3):
         for tag, zero_n2 in (("z", True), ("nz", False)):
             rng = np.random.default_rng(50 + ft)
@@ -83,6 +83,8 @@ def main():
             w[rng.random(w.size) < 0.9] = 0
             w[-2] = 0 if zero_n2 else (w[-2] | 1)
             arch = O.sparse_compress(w, ft, 10, False)
+            ref = pyref.sparse_compress(ft, w, 10)
+            assert np.array_equal(arch, ref), f"oracle/pyref disagree: sparse ft{ft} {tag}"
             st, dec = O.sparse_decompress(arch, ft, 10)
             assert st == 0 and np.array_equal(dec, w)
             fx[f"s{ft}_{tag}_in"] = w

@@ -194,3 +194,135 @@ def float_compress(ft, words, pb=10, checksum=False, word_bytes=None):
         out += bytes(round_up(len(a1), 16) - len(a1))
         out += ans_encode(np.frombuffer(c1, np.uint8), pb).tobytes()
     return np.frombuffer(out, dtype=np.uint8)
+
+
+# --------------------------------------------------------------------------
+# Sparse float codec.  Restated from the reference's kernels, not from
+# oracle/dietgpu_oracle.c: float/GpuSparseFloatCompress.cuh :32-58
+# (generate_bitmap), :64-113 (bitmap_bytes_to_bits), :119-185
+# (fill_comp_input), :237-247 (addBitmapToOutSizes), :360-367 (the exclusive
+# scan); float/GpuSparseFloatDecompress.cuh :26-62 (bitmap_bits_to_bytes),
+# :73-145 (fill_in_nonzeros).  Like the reference it keeps a 0/1 flag array
+# and an explicit u32 exclusive scan of it.
+# --------------------------------------------------------------------------
+
+_NP_WORD = {1: np.uint16, 2: np.uint16, 3: np.uint32, 4: np.uint64}
+
+
+def _exclusive_scan_u32(flags):
+    # thrust::exclusive_scan(.., 0) into uint32_t (:360-367)
+    idx = np.zeros(flags.size, dtype=np.uint32)
+    if flags.size > 1:
+        np.cumsum(flags[:-1], dtype=np.uint32, out=idx[1:])
+    return idx
+
+
+def sparse_list(ft, words, gap_fill=0):
+    """fill_comp_input (:119-185): the nonzero list handed to the dense codec.
+    gap_fill: the value of the slot the reference never writes (list[idx[n-2]]
+    when x[n-2] == 0; uninitialised memory there)."""
+    W = _NP_WORD[ft]
+    x = np.ascontiguousarray(words, dtype=W)
+    n = x.size
+    flag = (x != 0).astype(np.uint8)  # generate_bitmap :56, bitwise: -0.0 is nonzero
+    if n <= 1:
+        # the reference reads idx[-1] here; as the oracle defines it, the list
+        # is the word itself when it is nonzero, and empty otherwise
+        return x[flag == 1].copy()
+    idx = _exclusive_scan_u32(flag)
+    count = int(idx[n - 2]) + int(flag[n - 1]) + 1  # :183
+    lst = np.full(count, gap_fill, dtype=W)
+    body = np.flatnonzero(flag[: n - 1] == 1)  # :162-168, i < n-1
+    lst[idx[body]] = x[body]
+    if flag[n - 1] == 1:
+        lst[int(idx[n - 2]) + 1] = x[n - 1]  # :177-179
+    return lst
+
+
+def sparse_compress(ft, words, pb=10, checksum=False, gap_fill=0, pad_fill=0, pad_bits=False):
+    """Sparse archive: 16 B header {n, 0, 0, 0}, the bitmap MSB-first
+    (bitmap_bytes_to_bits :108-110) padded to 16 B, the dense archive of the
+    nonzero list.  gap_fill, pad_fill, pad_bits: the content of what the
+    reference leaves uninitialised -- the n-2 quirk's list slot, the bitmap's
+    padding bytes and (pad_bits) the bits of its last byte past n, filled from
+    pad_fill too.  The defaults are what this project's compressor writes."""
+    W = _NP_WORD[ft]
+    x = np.ascontiguousarray(words, dtype=W)
+    n = x.size
+    flag = (x != 0).astype(np.uint8)
+    nbytes = (n + 7) // 8
+    padded = np.zeros(8 * nbytes, dtype=np.uint8)  # "zero-padded at the end" :66-68
+    padded[:n] = flag
+    bitmap = np.zeros(round_up(nbytes, 16), dtype=np.uint8)
+    g = padded.reshape(nbytes, 8).astype(np.uint32)
+    for j in range(8):
+        bitmap[:nbytes] |= (g[:, j] << (7 - j)).astype(np.uint8)  # v.x[j] << (7 - j)
+    bitmap[nbytes:] = pad_fill
+    if pad_bits and n % 8:
+        bitmap[nbytes - 1] |= pad_fill & ((1 << (8 - n % 8)) - 1)
+    lst = sparse_list(ft, x, gap_fill)
+    dense = float_compress(ft, lst, pb, checksum=checksum, word_bytes=lst.view(np.uint8))
+    out = struct.pack("<4I", n, 0, 0, 0) + bitmap.tobytes() + dense.tobytes()
+    return np.frombuffer(out, dtype=np.uint8)
+
+
+def float_join(ft, c0, c1, raw, n):
+    """The inverse of float_split."""
+    W = _NP_WORD[ft]
+    out = np.zeros(n, dtype=W)
+    for i in range(n):
+        if ft == 1:
+            w = (c0[i] << 8) | raw[i]
+        elif ft == 2:
+            # c0 = bits 14..7 of w; raw = bits 6..0, then the sign
+            w = (c0[i] << 7) | (raw[i] >> 1) | ((raw[i] & 1) << 15)
+        elif ft == 3:
+            lo, = struct.unpack_from("<H", raw, 2 * i)
+            hi = raw[2 * round_up(n, 8) + i]
+            v = (c0[i] << 24) | (hi << 16) | lo
+            w = ((v >> 1) | (v << 31)) & 0xFFFFFFFF
+        else:
+            lo, = struct.unpack_from("<I", raw, 4 * i)
+            hi, = struct.unpack_from("<H", raw, 4 * round_up(n, 4) + 2 * i)
+            v = (c0[i] << 56) | (c1[i] << 48) | (hi << 32) | lo
+            w = ((v >> 1) | (v << 63)) & 0xFFFFFFFFFFFFFFFF
+        out[i] = w
+    return out
+
+
+def float_decompress(ft, arch, pb=10):
+    a = bytes(np.asarray(arch, dtype=np.uint8))
+    magic, n, opts, _, ans_off = struct.unpack_from("<5I", a, 0)
+    assert magic == 0xF00F0001 and opts & 0xF == ft
+    rawsz = {1: round_up(n, 16), 2: round_up(n, 16), 3: 2 * round_up(n, 8) + round_up(n, 16),
+             4: 4 * round_up(n, 4) + 2 * round_up(n, 8)}[ft]
+    raw = a[32: 32 + rawsz]
+    body = np.frombuffer(a, dtype=np.uint8)[32 + rawsz:]
+    c0 = ans_decode(body, pb)
+    c1 = ans_decode(body[ans_off:], pb) if ft == 4 else None
+    return float_join(ft, bytes(c0), bytes(c1) if ft == 4 else None, raw, n)
+
+
+def sparse_decompress(ft, arch, pb=10):
+    """bitmap_bits_to_bytes (:26-62) and fill_in_nonzeros (:73-145)."""
+    a = np.asarray(arch, dtype=np.uint8)
+    n = int(a[:4].view(np.uint32)[0])
+    nbytes = (n + 7) // 8
+    bits = a[16: 16 + nbytes]
+    flag = np.zeros(8 * nbytes, dtype=np.uint8)
+    for j in range(8):
+        flag[j::8] = (bits & (1 << (7 - j))) >> (7 - j)  # :59
+    lst = float_decompress(ft, a[16 + round_up(nbytes, 16):], pb)
+    out = np.zeros(n, dtype=_NP_WORD[ft])
+    if n == 0:
+        return out
+    if n == 1:  # idx[-1] in the reference; see sparse_list
+        if flag[0]:
+            out[0] = lst[0]
+        return out
+    idx = _exclusive_scan_u32(flag[:n])
+    body = np.flatnonzero(flag[: n - 1] == 1)
+    out[body] = lst[idx[body]]
+    if flag[n - 1] == 1:
+        out[n - 1] = lst[int(idx[n - 2]) + 1]  # :139-140
+    return out

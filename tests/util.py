@@ -209,3 +209,136 @@ def bytes_from_histogram(h, seed=0):
     """A seeded permutation of h[s] copies of every symbol s."""
     rng = np.random.default_rng(seed)
     return rng.permutation(np.repeat(np.arange(256, dtype=np.uint8), np.asarray(h, dtype=np.int64)))
+
+
+# --------------------------------------------------------------------------
+# Sparse codec: sizes on every edge of its index arithmetic (64-word ballot
+# steps, 1024-word chunks, 4096-word tiles, 262,144-word scan workgroups), the
+# four zero / nonzero combinations of the last two words (the reference's n-2
+# quirk), special bit patterns, and one element past 65 scan workgroups.
+# --------------------------------------------------------------------------
+
+SPARSE_SMALL_B = (256, 1024, 2048, 4096, 8192)
+SPARSE_LARGE_B = 262144  # one k_sparseChunks workgroup: 256 chunks of 1024 words
+SPARSE_BLOCK_EDGE = (4095, 4096, 4097, 4098, 8191, 8192, 8193)
+# (x[n-2] != 0, x[n-1] != 0)
+SPARSE_TAILS = ((False, False), (False, True), (True, False), (True, True))
+SPARSE_FILLS = ("zero", "half", "dense")
+
+
+def sparse_edge_sizes():
+    """(small sizes, large sizes)."""
+    small = list(range(201)) + [B + d for B in SPARSE_SMALL_B for d in range(-2, 3)]
+    large = [SPARSE_LARGE_B + d for d in range(-2, 3)]
+    return small, large
+
+
+def _sparse_fill(ft, n, fill, seed):
+    if fill == "zero":
+        return np.zeros(n, dtype=NP_WORD[ft])
+    w = float_words(ft, n, seed=seed)
+    if fill == "half":
+        return sparsify(w, 0.5, seed=seed + 1)
+    w[w == 0] = 1  # (fp16 rounds small draws to zero)
+    return w
+
+
+def sparse_edge_elements(ft):
+    """[(group, name, words)]: group "small" or "large".  Every size of
+    sparse_edge_sizes() with each of the four SPARSE_TAILS (for n == 1 the two
+    values of x[0]); a forced nonzero word is w | 1.  The other words cycle
+    with n through SPARSE_FILLS.  Then elements without zeros and all-zero
+    elements at SPARSE_BLOCK_EDGE: the list's length falls on the dense
+    codec's 4096-symbol block edge, and an all-zero element's list is the n-2
+    slot alone."""
+    out = []
+    small, large = sparse_edge_sizes()
+    for group, sizes in (("small", small), ("large", large)):
+        for n in sizes:
+            fill = SPARSE_FILLS[n % 3]
+            base = _sparse_fill(ft, n, fill, seed=7 * n + ft)
+            tails = SPARSE_TAILS if n >= 2 else SPARSE_TAILS[:2][:n + 1]
+            for t2, t1 in tails:
+                w = base.copy()
+                if n >= 2:
+                    w[n - 2] = (w[n - 2] | 1) if t2 else 0
+                if n >= 1:
+                    w[n - 1] = (w[n - 1] | 1) if t1 else 0
+                out.append((group, f"n{n}_{fill}_t{int(t2)}{int(t1)}", w))
+    for n in SPARSE_BLOCK_EDGE:
+        for fill in ("dense", "zero"):
+            out.append(("small", f"n{n}_all_{fill}", _sparse_fill(ft, n, fill, seed=11 * n + ft)))
+    return out
+
+
+def sparse_special_patterns(ft):
+    """name -> word: the bit patterns sparse_special_words() mixes in.  Only
+    +0.0 is a zero of the sparse codec (generate_bitmap tests the word)."""
+    bits = 8 * np.dtype(NP_WORD[ft]).itemsize
+    exp_bits, man_bits = {1: (5, 10), 2: (8, 7), 3: (8, 23), 4: (11, 52)}[ft]
+    sign = 1 << (bits - 1)
+    inf = ((1 << exp_bits) - 1) << man_bits
+    p = {
+        "pos_zero": 0,
+        "neg_zero": sign,
+        "min_denormal": 1,
+        "neg_min_denormal": sign | 1,
+        "pos_inf": inf,
+        "neg_inf": sign | inf,
+        "quiet_nan": inf | (1 << (man_bits - 1)),
+        "signalling_nan": inf | 1,
+        "neg_nan_all_ones": (1 << bits) - 1,
+    }
+    if ft == 4:
+        p["low_half_zero"] = 0x3FF0000000000000  # 1.0
+        p["low_half_zero_denormal"] = 0x0000000100000000
+        p["high_half_zero"] = 0x00000000FFFFFFFF
+        p["high_half_zero_top_bit"] = 0x0000000080000000
+    return {k: NP_WORD[ft](v) for k, v in p.items()}
+
+
+SPARSE_SPECIAL_N = 4321  # two tiles, five chunks, an odd tail
+
+
+def sparse_special_words(ft):
+    """name -> words, three variants of one element of SPARSE_SPECIAL_N words:
+    N(0,1) words, 40 % of them +0.0, then 30 % of the positions overwritten
+    with the patterns of sparse_special_patterns() in equal shares (each at
+    least once).  "base" ends in two random nonzero words, "negzero_n2" has -0.0 at
+    n-2 (no gap slot: -0.0 is nonzero) and "negzero_n1" has +0.0 at n-2 and
+    -0.0 at n-1 (the gap slot, then a -0.0 in the list)."""
+    n = SPARSE_SPECIAL_N
+    rng = np.random.default_rng(900 + ft)
+    pats = sparse_special_patterns(ft)
+    w = sparsify(float_words(ft, n, seed=910 + ft), 0.4, seed=920 + ft)
+    vals = np.array(list(pats.values()), dtype=NP_WORD[ft])
+    pick = rng.random(n) < 0.3
+    w[pick] = vals[rng.integers(0, len(vals), int(pick.sum()))]
+    pos = rng.permutation(n - 2)[: len(vals)]  # every pattern at least once
+    w[pos] = vals
+    neg0 = pats["neg_zero"]
+    base = w.copy()
+    base[n - 2:] |= NP_WORD[ft](1)
+    n2 = w.copy()
+    n2[n - 2], n2[n - 1] = neg0, w[n - 1] | NP_WORD[ft](1)
+    n1 = w.copy()
+    n1[n - 2], n1[n - 1] = 0, neg0
+    return {"base": base, "negzero_n2": n2, "negzero_n1": n1}
+
+
+SPARSE_FAR_N = 66 * SPARSE_LARGE_B + 1102
+
+
+def sparse_far_element():
+    """bf16, SPARSE_FAR_N words, about 1 % nonzero at seeded positions,
+    x[n-2] == 0 != x[n-1].  Its chunks from word 65 * 262,144 on belong to scan
+    workgroups above 64, whose list offsets k_sparseExpand sums in a second
+    round of its blockTot loop."""
+    n = SPARSE_FAR_N
+    rng = np.random.default_rng(66)
+    k = n // 100
+    w = np.zeros(n, dtype=np.uint16)
+    w[rng.integers(0, n, k)] = float_words(2, k, seed=67) | np.uint16(1)
+    w[n - 2] = 0
+    w[n - 1] = 0x3F81
+    return w
