@@ -231,6 +231,7 @@ bool compressPersistent(const CompressCall& c) {
   a.team = team;
   a.nb = nb;
   a.grid = grid;
+  a.teams = teams;  // (the kernel divides by nothing but `team`, once per workgroup)
   a.epoch = lease.epoch;
   a.spinCap = spinCap();
   a.fallbackTicks = barrierBudgetTicks();

@@ -126,6 +126,7 @@ struct PCompArgs {
   uint32_t team;         // items per element
   uint32_t nb;
   uint32_t grid;         // workgroups = items per round (a whole number of teams)
+  uint32_t teams;        // grid / team
   uint64_t* ctr;         // [2] element dequeue counters, this call's at epoch & 1 (sync arena)
   uint64_t* elog;        // [teams][maxR] element of each team's round, epoch << 32 | element (sync arena)
   uint32_t maxR;         // rounds a team may take
@@ -137,33 +138,32 @@ struct PCompArgs {
   bool useChecksum;
 };
 
-// One item: element b, member x of a team of `team` items starting at item tb.
+// One item: member x of the team of element b (items tb .. tb + team - 1; the
+// workgroup's member index never changes, so x is the same for all its items).
+// An item is decoded ONCE, by one wave, when its element becomes known (at
+// the kernel's start for round 0, at the end of the previous hand-off window
+// otherwise), into a record in LDS that every later use reads: no use repeats
+// the descriptor loads, the table look-ups or a division.
 struct PItem {
-  uint32_t i;  // item index, or >= items: none
-  uint32_t b, x, team, tb, n, nBlocks;
+  uint32_t i;  // item index, or kNoItem
+  uint32_t b, x, n, nBlocks;
+  uint64_t in, out;    // the element's input and archive addresses
+  uint32_t uw0, uw1;   // symbols of the reading wave's two blocks
 };
-
-__device__ __forceinline__ PItem itemOf(uint32_t i, const PCompArgs& a, const BatchDesc& in) {
-  PItem it;
-  it.i = i;
-  it.b = it.x = it.team = it.tb = it.n = it.nBlocks = 0;
-  if (i >= a.items) return it;
-  it.b = i / a.team;
-  it.team = a.team;
-  it.tb = it.b * a.team;
-  it.x = i - it.tb;
-  it.n = in.size(it.b);
-  it.nBlocks = divUp(it.n, kBlockSize);
-  return it;
-}
+constexpr uint32_t kNoItem = ~0u;
+// record words: i, b, n, nBlocks, in (2), out (2), the item's 8 block sizes
+constexpr uint32_t kItemWords = 16;
 
 // Kernel-argument layout of k_pcompress (explicit arguments in order, each at
-// its natural alignment).  The kernel re-reads its arguments from the kernarg
-// segment where it needs them, through a pointer the compiler cannot see
-// through: otherwise it keeps both descriptors and the argument block (~50
-// SGPRs) live across the pipelined loop and spills SGPRs to scratch inside
-// the encode steps, where every reload's vmcnt wait drains the prefetched
-// input loads.
+// its natural alignment).  The kernel reads its arguments from the kernarg
+// segment through a pointer the compiler cannot see through: otherwise it
+// keeps both descriptors and the argument block (~50 SGPRs) live across the
+// pipelined loop and spills SGPRs to scratch inside the encode steps, where
+// every reload's vmcnt wait drains the prefetched input loads.  Each hand-off
+// window defines such a pointer once, after its first barrier, and reads the
+// argument block through it once (the fields it uses: one batch of scalar
+// loads, one wait); the segment phase reads no argument at all (its item
+// records and the workgroup's team coordinates are in LDS).
 constexpr size_t kArgIn = sizeof(InlineTable);
 constexpr size_t kArgOut = (kArgIn + sizeof(BatchDesc) + alignof(BatchDesc) - 1) / alignof(BatchDesc) * alignof(BatchDesc);
 constexpr size_t kArgA = (kArgOut + sizeof(BatchDesc) + alignof(PCompArgs) - 1) / alignof(PCompArgs) * alignof(PCompArgs);
@@ -180,16 +180,31 @@ __device__ __forceinline__ void staticFor(F&& f) {
   staticForImpl(f, std::make_integer_sequence<uint32_t, N>{});
 }
 
-template <typename T>
-__device__ __forceinline__ T kernArg(size_t off) {
+// The kernarg segment through a pointer of unknown origin: loads through it
+// can move neither above this call nor be merged with another call's.
+__device__ __forceinline__ const DG_CONST uint8_t* kernArgBase() {
 #if defined(__HIP_DEVICE_COMPILE__)
   const DG_CONST uint8_t* k = (const DG_CONST uint8_t*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));  // opaque: a fresh scalar load at every use
+  asm volatile("" : "+s"(k));
+  return k;
+#else
+  return nullptr;
+#endif
+}
+// (by value: only the fields a caller uses are loaded)
+template <typename T>
+__device__ __forceinline__ T kernArgAt(const DG_CONST uint8_t* k, size_t off) {
+#if defined(__HIP_DEVICE_COMPILE__)
   return *(const DG_CONST T*)(k + off);
 #else
+  (void)k;
   (void)off;
   return T();
 #endif
+}
+template <typename T>
+__device__ __forceinline__ T kernArg(size_t off) {  // a fresh scalar load at every use
+  return kernArgAt<T>(kernArgBase(), off);
 }
 
 __device__ __forceinline__ uint64_t realtime() {
@@ -213,9 +228,6 @@ __device__ __forceinline__ uint64_t realtime() {
 template <int FT, bool kCk, bool kXcd>
 __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_pcompress(
     const InlineTable, BatchDesc, BatchDesc, PCompArgs) {
-  auto IN = [] { return kernArg<BatchDesc>(kArgIn); };
-  auto OUT = [] { return kernArg<BatchDesc>(kArgOut); };
-  auto A = [] { return kernArg<PCompArgs>(kArgA); };
   using WordT = typename FloatTraits<FT>::WordT;
   static_assert(FloatTraits<FT>::kSegs == 1, "single-segment formats only");
   constexpr uint32_t kWPV = 16 / sizeof(WordT);                      // words per 16 B vector
@@ -236,6 +248,12 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   __shared__ __attribute__((aligned(16))) uint32_t flE[pc::kBlocksPerItem];
   __shared__ __attribute__((aligned(16))) uint32_t preE[pc::kBlocksPerItem];
   __shared__ uint32_t poisonS, sigS, fbS;
+  // item records, rotating: round r's item lives in record r % 3 (L in
+  // iteration r, E in iteration r + 1, while the window of iteration r
+  // decodes round r + 1's); and the workgroup's team T, member X and
+  // dispatch slot, computed once
+  __shared__ __attribute__((aligned(16))) uint32_t itemS[3][kItemWords];
+  __shared__ __attribute__((aligned(16))) uint32_t wgS[4];
 
   const uint32_t tid = threadIdx.x;
   // the lane's half (0: lanes 0-31, 1: lanes 32-63), recomputed at each use
@@ -266,7 +284,8 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   const uint32_t sel1 = (qr & 2) ? 0x03020706u : 0x05040100u;
   const uint32_t sel2 = (qr & 1) ? 0x03070105u : 0x06020400u;
   lp<const u32x4> tbl = (lp<const u32x4>)&tblS[0];
-  gp<uint8_t> slotBase = G(A().slots) + uint64_t(blockIdx.x) * pc::kBlocksPerItem * kSlotDataBytes;
+  gp<uint8_t> slotBase =
+      G(kernArg<PCompArgs>(kArgA).slots) + uint64_t(blockIdx.x) * pc::kBlocksPerItem * kSlotDataBytes;
 
   for (uint32_t i = tid; i < pc::kHistWords / 4; i += pc::kThreads)
     *(lp<u32x4>)&hist[4 * i] = u32x4{0, 0, 0, 0};
@@ -289,33 +308,68 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   // take more elements (the SIMD arbiter favours the earlier-dispatched
   // workgroups of a CU: with a static deal their teams finished rounds of
   // work ahead of the last ones).
-  auto teamX = [&](uint32_t& T, uint32_t& X) __attribute__((always_inline)) {
-    const PCompArgs ka = A();
+  // (the kernel's only division: once, at its start, into wgS)
+  auto teamX = [&](uint32_t team, uint32_t& T, uint32_t& X) __attribute__((always_inline)) {
     if constexpr (kXcd) {  // w = xcd + 8 (group * team + x), team T = group * 8 + xcd
       const uint32_t xcd = blockIdx.x & 7u, q = blockIdx.x >> 3;
-      const uint32_t grp = q / ka.team;
-      X = q - grp * ka.team;
+      const uint32_t grp = q / team;
+      X = q - grp * team;
       T = grp * 8 + xcd;
     } else {
-      T = blockIdx.x / ka.team;
-      X = blockIdx.x - T * ka.team;
+      T = blockIdx.x / team;
+      X = blockIdx.x - T * team;
     }
   };
-  // item of element e (>= nb: none) for this member
-  auto itemOfElem = [&](uint32_t e) __attribute__((always_inline)) -> uint32_t {
-    uint32_t T, X;
-    teamX(T, X);
-    const PCompArgs ka = A();
-    return e < ka.nb ? e * ka.team + X : ka.items;
+  // Decode member X's item of element e (>= nb: none) into record s: the
+  // descriptors' loads and table look-ups happen here and nowhere else.  One
+  // wave, e wave-uniform; the next workgroup barrier hands the record over.
+  auto decodeItem = [&](const DG_CONST uint8_t* kw, const PCompArgs& ka, uint32_t e, uint32_t X, uint32_t s)
+                        __attribute__((always_inline)) {
+    uint32_t i = kNoItem, n = 0, nBlocks = 0;
+    uint64_t in = 0, out = 0;
+    if (e < ka.nb) {
+      const BatchDesc din = kernArgAt<BatchDesc>(kw, kArgIn), dout = kernArgAt<BatchDesc>(kw, kArgOut);
+      i = e * ka.team + X;
+      n = din.size(e);
+      nBlocks = divUp(n, kBlockSize);
+      in = uint64_t(reinterpret_cast<uintptr_t>(startOf(din, e)));
+      out = uint64_t(reinterpret_cast<uintptr_t>(startOf(dout, e)));
+    }
+    const uint32_t lane = laneNow();
+    if (lane < pc::kBlocksPerItem) itemS[s][8 + lane] = blockSymbols(X * pc::kBlocksPerItem + lane, nBlocks, n);
+    if (lane == 0) {
+      *(lp<u32x4>)&itemS[s][0] = u32x4{i, e, n, nBlocks};
+      *(lp<u32x4>)&itemS[s][4] = u32x4{uint32_t(in), uint32_t(in >> 32), uint32_t(out), uint32_t(out >> 32)};
+    }
+  };
+  static_assert(kItemWords == 8 + pc::kBlocksPerItem, "record layout");
+  // record s as this wave reads it (uniform values in SGPRs; a caller's
+  // unused fields cost nothing)
+  auto itemAt = [&](uint32_t s, uint32_t X) __attribute__((always_inline)) -> PItem {
+    const u32x4 q0 = *(lp<const u32x4>)&itemS[s][0], q1 = *(lp<const u32x4>)&itemS[s][4];
+    const u32x2 q2 = *(lp<const u32x2>)&itemS[s][8 + 2 * w];
+    PItem it;
+    it.i = readfirst(q0.x);
+    it.b = readfirst(q0.y);
+    it.x = X;
+    it.n = readfirst(q0.z);
+    it.nBlocks = readfirst(q0.w);
+    it.in = uint64_t(readfirst(q1.x)) | (uint64_t(readfirst(q1.y)) << 32);
+    it.out = uint64_t(readfirst(q1.z)) | (uint64_t(readfirst(q1.w)) << 32);
+    it.uw0 = readfirst(q2.x);
+    it.uw1 = readfirst(q2.y);
+    return it;
+  };
+  auto inOf = [](const PItem& it) __attribute__((always_inline)) -> gp<const uint8_t> {
+    return (gp<const uint8_t>)uintptr_t(it.in);
+  };
+  auto outOf = [](const PItem& it) __attribute__((always_inline)) -> gp<uint8_t> {
+    return (gp<uint8_t>)uintptr_t(it.out);
   };
   // element of this team's round r (r >= 2: from the log, written by member
   // 0 a round earlier; a lower workgroup index, so the wait always ends)
-  auto elemOfRound = [&](uint32_t r) __attribute__((always_inline)) -> uint32_t {
-    uint32_t T, X;
-    teamX(T, X);
-    const PCompArgs ka = A();
-    const uint32_t teams = ka.grid / ka.team;
-    if (r < 2) return min(r * teams + T, ka.nb);
+  auto elemOfRound = [&](const PCompArgs& ka, uint32_t T, uint32_t r) __attribute__((always_inline)) -> uint32_t {
+    if (r < 2) return min(r * ka.teams + T, ka.nb);
     if (r >= ka.maxR) return ka.nb;
     gp<const uint64_t> slot = G(ka.elog) + uint64_t(T) * ka.maxR + r;
     uint64_t v = 0;
@@ -331,12 +385,9 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     return ka.nb;
   };
   // member 0: take the element of round r (>= 2) and log it
-  auto dequeueRound = [&](uint32_t r) __attribute__((always_inline)) {
-    uint32_t T, X;
-    teamX(T, X);
-    const PCompArgs ka = A();
-    if (X != 0 || r >= ka.maxR) return;
-    const uint32_t teams = ka.grid / ka.team;
+  auto dequeueRound = [&](const PCompArgs& ka, uint32_t T, uint32_t r) __attribute__((always_inline)) {
+    if (r >= ka.maxR) return;
+    const uint32_t teams = ka.teams;
     const uint64_t tag = uint64_t(ka.epoch) << 32;
     // one returning add on this call's counter (zeroed by the previous call
     // on this stream, see below): a compare-and-swap loop under 64
@@ -346,17 +397,14 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     __hip_atomic_store(G(ka.elog) + uint64_t(T) * ka.maxR + r, tag | min(e, ka.nb), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   };
-  auto pairSize = [&](const PItem& it, int hh) __attribute__((always_inline)) -> uint32_t {
-    return blockSymbols(it.x * pc::kBlocksPerItem + 2 * w + hh, it.nBlocks, it.n);
-  };
-  // this lane's block size of an item (h ? pairSize(it, 1) : pairSize(it, 0))
+  // this lane's block size of an item
   auto laneSize = [&](const PItem& it) __attribute__((always_inline)) -> uint32_t {
-    return blockSymbols(it.x * pc::kBlocksPerItem + 2 * w + halfNow(), it.nBlocks, it.n);
+    return halfNow() ? it.uw1 : it.uw0;
   };
+  // this wave's block pair of an item (wave-uniform: the lane's half is added
+  // at each load, so no per-lane address is held across the segment loop)
   auto srcOf = [&](const PItem& it) __attribute__((always_inline)) -> gp<const WordT> {
-    const uint32_t hh = halfNow();
-    return (gp<const WordT>)startOf(IN(), it.b) +
-           uint64_t(it.x * pc::kBlocksPerItem + 2 * w + hh) * kBlockSize;
+    return (gp<const WordT>)inOf(it) + uint64_t(it.x * pc::kBlocksPerItem + 2 * w) * kBlockSize;
   };
 
   // 16 B streaming loads of segment g of this lane's block into load slot
@@ -378,7 +426,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       const uint32_t j0 = g * pc::kSegWords + (k * 32 + ll) * kWPV;
-      pv[g % D][k] = ld16nt(j0 < uw ? src + j0 : dummy);
+      pv[g % D][k] = ld16nt(j0 < uw ? src + (halfNow() * kBlockSize + j0) : dummy);
     }
   };
 
@@ -500,7 +548,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   // otherwise sc1 (write-through) stores, since members on other XCDs read
   // from memory.  The words live in the persistent epoch-tagged sync arena,
   // never in scratch a stale value could come from.
-  auto publishHist = [&](const PItem& it) __attribute__((always_inline)) {
+  auto publishHist = [&](const PItem& it, const PCompArgs& ka) __attribute__((always_inline)) {
     const uint32_t tid = tidNow(), lane = laneNow();
     (void)tid;
     (void)lane;
@@ -510,14 +558,14 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       cnt += hist[tid * pc::kHistStride + k];
       hist[tid * pc::kHistStride + k] = 0;
     }
-    const uint32_t tag = A().epoch << 16;
+    const uint32_t tag = ka.epoch << 16;
     if constexpr (kXcd)
-      __hip_atomic_store(G(A().part) + uint64_t(it.i) * kNumSymbols + tid, tag | cnt, __ATOMIC_RELAXED,
+      __hip_atomic_store(G(ka.part) + uint64_t(it.i) * kNumSymbols + tid, tag | cnt, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_WORKGROUP);
     else
-      stSc1(G(A().part) + uint64_t(it.i) * kNumSymbols + tid, tag | cnt);
+      stSc1(G(ka.part) + uint64_t(it.i) * kNumSymbols + tid, tag | cnt);
     if constexpr (kCk) {
-      if (tid == 0) stSc1(G(A().partCk) + it.i, tag | (ckS[0] ^ ckS[1] ^ ckS[2] ^ ckS[3]));
+      if (tid == 0) stSc1(G(ka.partCk) + it.i, tag | (ckS[0] ^ ckS[1] ^ ckS[2] ^ ckS[3]));
     }
   };
 
@@ -527,7 +575,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   // LDS is zero on entry and on exit (no other wave touches it meanwhile).
   auto countElementWave = [&](const PItem& it, uint32_t (&c)[4], uint32_t& ckOut) __attribute__((always_inline)) {
     const uint32_t lane = laneNow();
-    const gp<const WordT> src = (gp<const WordT>)startOf(IN(), it.b);
+    const gp<const WordT> src = (gp<const WordT>)inOf(it);
     const uint32_t nv = divUp(it.n, kWPV);
     lp<uint32_t> col = (lp<uint32_t>)&hist[lane % pc::kHistCols];
     uint32_t x = 0;
@@ -559,7 +607,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   };
 
   // ---- E's aggregate (its words, rounded to 8 per block) -> its look-back flag ----
-  auto publishAgg = [&](const PItem& it) __attribute__((always_inline)) {
+  auto publishAgg = [&](const PItem& it, const PCompArgs& ka) __attribute__((always_inline)) {
     const uint32_t tid = tidNow(), lane = laneNow();
     (void)tid;
     (void)lane;
@@ -568,13 +616,13 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t r = lane < nk ? roundUp(cwE[lane], 8) : 0u;
     const uint32_t agg = readfirst(__shfl(waveInclusiveScan(r), 63));
     if (lane == 0)
-      __hip_atomic_store(G(A().flags) + it.tb + it.x,
-                         (it.x == 0 ? kFlagPrefix : kFlagAgg) | (uint64_t(A().epoch) << 32) | agg,
+      __hip_atomic_store(G(ka.flags) + it.b * ka.team + it.x,
+                         (it.x == 0 ? kFlagPrefix : kFlagAgg) | (uint64_t(ka.epoch) << 32) | agg,
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
 
   // ---- wave 0: E's look-back -> preE, the last member's header total ----
-  auto lookBackE = [&](const PItem& it) __attribute__((always_inline)) {
+  auto lookBackE = [&](const PItem& it, const PCompArgs& ka) __attribute__((always_inline)) {
     const uint32_t tid = tidNow(), lane = laneNow();
     (void)tid;
     (void)lane;
@@ -584,36 +632,35 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t inc = waveInclusiveScan(r);
     const uint32_t agg = readfirst(__shfl(inc, 63));
     bool pz = false;
-    const uint32_t excl = lookBackPoison(G(A().flags) + it.tb, it.x, agg, A().epoch, A().spinCap, pz, false);
+    const uint32_t excl = lookBackPoison(G(ka.flags) + it.b * ka.team, it.x, agg, ka.epoch, ka.spinCap, pz, false);
     if (lane < nk) preE[lane] = excl + inc - r;
     if (lane == 0) {
       poisonS = pz ? 1u : 0u;
-      if (it.x == it.team - 1)
-        closeElement<FT>(startOf(OUT(), it.b), it.n, it.nBlocks, pz, excl + agg, 0, A().outSize, A().sparseN, it.b,
-                         A().err);
+      if (it.x == ka.team - 1)
+        closeElement<FT>(outOf(it), it.n, it.nBlocks, pz, excl + agg, 0, ka.outSize, ka.sparseN, it.b, ka.err);
     }
   };
 
   // ---- wave 0, after L's normalisation: L's header fields known before
   // encoding (all but the word totals), its pdf table and the raw section's
   // rounding tails, by the team's first member ----
-  auto writeHeadFixedL = [&](const PItem& it, uint32_t ckv) __attribute__((always_inline)) {
+  auto writeHeadFixedL = [&](const PItem& it, const PCompArgs& ka, uint32_t ckv) __attribute__((always_inline)) {
     const uint32_t tid = tidNow(), lane = laneNow();
     (void)tid;
     (void)lane;
-    gp<uint8_t> base = startOf(OUT(), it.b);
+    gp<uint8_t> base = outOf(it);
     gp<uint8_t> o = ansArchiveOf<FT>(base, it.n);
     // (writeHeaders' stores, archive.h, spelled out: through the shared
     // function, whatever its call shape, the register allocator spills
     // differently in the bf16 / fp32 instances)
     if (lane == 0) {
-      const bool ansCk = FT == 0 && A().useChecksum;
-      if (FT != 0) ckv = A().ckIn ? G(A().ckIn)[it.b] : 0u;
+      const bool ansCk = FT == 0 && ka.useChecksum;
+      if (FT != 0) ckv = ka.ckIn ? G(ka.ckIn)[it.b] : 0u;
       gp<uint32_t> ah = (gp<uint32_t>)o;
       ah[kAnsMagic] = kANSMagicVersion;
       ah[kAnsBlocks] = it.nBlocks;
       ah[kAnsSize] = it.n;
-      ah[kAnsPrecision] = uint32_t(A().pb) | (ansCk ? kChecksumFlag : 0u);
+      ah[kAnsPrecision] = uint32_t(ka.pb) | (ansCk ? kChecksumFlag : 0u);
       ah[kAnsChecksum] = ansCk ? ckv : 0u;
 #pragma unroll
       for (uint32_t w = kAnsZeros; w < kANSHeaderBytes / 4; ++w) ah[w] = 0;
@@ -621,8 +668,8 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
         gp<uint32_t> fh = (gp<uint32_t>)base;
         fh[kFloatMagic] = kFloatMagicVersion;
         fh[kFloatSize] = it.n;
-        fh[kFloatType] = uint32_t(FT) | (A().useChecksum ? kChecksumFlag : 0u);
-        fh[kFloatChecksum] = A().useChecksum ? ckv : 0u;
+        fh[kFloatType] = uint32_t(FT) | (ka.useChecksum ? kChecksumFlag : 0u);
+        fh[kFloatChecksum] = ka.useChecksum ? ckv : 0u;
 #pragma unroll
         for (uint32_t w = kFloatZeros; w < kFloatHeaderBytes / 4; ++w) fh[w] = 0;
       }
@@ -645,7 +692,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t t = tid - 64;
     const uint32_t first = it.x * pc::kBlocksPerItem;
     const uint32_t nk = first < it.nBlocks ? min(pc::kBlocksPerItem, it.nBlocks - first) : 0u;
-    const AnsSections arc(ansArchiveOf<FT>(startOf(OUT(), it.b), it.n), it.nBlocks);
+    const AnsSections arc(ansArchiveOf<FT>(outOf(it), it.n), it.nBlocks);
     // a poisoned element's archive is abandoned (outSize 0): its payload
     // range is not known, so nothing more is written
     if (nk == 0 || poisonS) return;
@@ -688,7 +735,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     const uint32_t hh = halfNow();
     const uint32_t uw = laneSize(it);
     if (uw) {
-      const AnsSections arc(ansArchiveOf<FT>(startOf(OUT(), it.b), it.n), it.nBlocks);
+      const AnsSections arc(ansArchiveOf<FT>(outOf(it), it.n), it.nBlocks);
       const uint32_t blk = it.x * pc::kBlocksPerItem + 2 * w + hh;
       ((gp<uint32_t>)(arc.states + uint64_t(kStateBytesPerBlock) * blk))[l] = p.x;
     }
@@ -702,18 +749,32 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
   const gp<const WordT> dummy = (gp<const WordT>)slotBase;
 
   // ================= the pipeline =================
-  // Only item indices live across iterations; everything else is recomputed
-  // (scalar work) where it is needed.
-  // the next call on this stream (epoch + 1) counts from zero: calls on one
-  // stream run one after another, so nothing reads that counter now
-  if (blockIdx.x == 0 && tid == 0)
-    __hip_atomic_store(G(A().ctr) + ((A().epoch + 1) & 1u), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();  // histogram zeroed
+  // Only the round lives across iterations (the record indices follow from
+  // it: carried in a register of their own they cost the fp32 instance eight
+  // more spilled dwords); the items are in their LDS records, the arguments
+  // are read per window.
+  if (w == 0) {
+    const DG_CONST uint8_t* kw = kernArgBase();
+    const PCompArgs ka = kernArgAt<PCompArgs>(kw, kArgA);
+    // the next call on this stream (epoch + 1) counts from zero: calls on one
+    // stream run one after another, so nothing reads that counter now
+    if (blockIdx.x == 0 && tid == 0)
+      __hip_atomic_store(G(ka.ctr) + ((ka.epoch + 1) & 1u), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t T, X;
+    teamX(ka.team, T, X);
+    // (the dispatch slot enters the segment-phase priority mod 3 only)
+    if (tid == 0) *(lp<u32x4>)&wgS[0] = u32x4{T, X, (blockIdx.x / ka.slotSpan) % 3u, 0u};
+    decodeItem(kw, ka, elemOfRound(ka, T, 0), X, 0);  // round 0's item: L of iteration 0
+    decodeItem(kw, ka, ka.nb, X, 2);                  // ... which has no E
+  }
+  __syncthreads();  // histogram zeroed, records written
   uint32_t round = 0;
-  uint32_t iE = A().items, iL = itemOfElem(elemOfRound(0));
-  if (iL >= A().items) return;
+  if (readfirst(itemS[0][0]) == kNoItem) return;
   while (true) {
-    const bool hasE = iE < A().items, hasL = iL < A().items;
+    const uint32_t sL = readfirst(round % 3u), sE = readfirst((round + 2u) % 3u);  // (by a constant: no division)
+    const uint32_t X = readfirst(wgS[1]);
+    const PItem E = itemAt(sE, X), L = itemAt(sL, X);
+    const bool hasE = E.i != kNoItem, hasL = L.i != kNoItem;
     if (!hasE && !hasL) break;
     // Segment-phase wave priority rotates over the CU's dispatch slots
     // round by round.  At equal priority the SIMD arbiter favours the older
@@ -722,15 +783,14 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     // launch); rotating gives each slot each level in turn.  (The hand-off
     // window runs above all of them.)
     {
-      const uint32_t pr = (blockIdx.x / A().slotSpan + round) % 3u;
-      if (pr == 0) __builtin_amdgcn_s_setprio(0);
-      else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+      const uint32_t pr = readfirst(wgS[2]) + sL;  // (slot + round) % 3
+      if (pr == 0 || pr == 3) __builtin_amdgcn_s_setprio(0);
+      else if (pr == 1 || pr == 4) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(2);
     }
     {
-      const PItem E = itemOf(iE, A(), IN()), L = itemOf(iL, A(), IN());
-      const uint32_t uwE0 = pairSize(E, 0), uwE1 = pairSize(E, 1);
-      const uint32_t uwL0 = pairSize(L, 0), uwL1 = pairSize(L, 1);
+      const uint32_t uwE0 = E.uw0, uwE1 = E.uw1;
+      const uint32_t uwL0 = L.uw0, uwL1 = L.uw1;
       // encode: the full-step variant when both blocks of the pair are whole
       // (uwE0 >= uwE1)
       const bool encOn = hasE && uwE0 != 0;
@@ -741,7 +801,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       const bool fullL = uwL1 == kBlockSize;
       const uint32_t uwL = halfNow() ? uwL1 : uwL0;
       const gp<const WordT> srcL = srcOf(L);
-      gp<uint8_t> rawL = FT == 0 ? gp<uint8_t>(nullptr) : rawSectionOf(startOf(OUT(), L.b));
+      gp<uint8_t> rawL = FT == 0 ? gp<uint8_t>(nullptr) : rawSectionOf(outOf(L));
       if (hasE) encInit();
       auto encSeg = [&](uint32_t g) __attribute__((always_inline)) {
         if (encOn) {
@@ -785,8 +845,17 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     }
     // E's word counts and L's histogram counts are in
     __syncthreads();
-    if (hasL) publishHist(itemOf(iL, A(), IN()));
-    if (hasE && w == 0) publishAgg(itemOf(iE, A(), IN()));
+    // The window's view of the arguments: read here once (the pointer is
+    // born here, so no load moves above the segment phase or stays live
+    // across it), then passed to every step below; the items and the team
+    // coordinates come back from LDS.
+    const DG_CONST uint8_t* kw = kernArgBase();
+    const PCompArgs ka = kernArgAt<PCompArgs>(kw, kArgA);
+    const uint32_t T = readfirst(wgS[0]);
+    const uint32_t sN = readfirst((round + 1u) % 3u);
+    const PItem Ew = itemAt(readfirst((round + 2u) % 3u), X), Lw = itemAt(readfirst(round % 3u), X);
+    if (hasL) publishHist(Lw, ka);
+    if (hasE && w == 0) publishAgg(Ew, ka);
     // L's team partials: wave w gathers members w, w + 4, ... (16 B = four
     // bins per lane: a lane holds bins 4l .. 4l + 3, the layout the one-wave
     // normalisation takes); the first four of each wave's members are loaded
@@ -797,34 +866,31 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     uint32_t ckv = 0;
     if (hasL) {
       const uint32_t lane = laneNow();
-      const PItem L = itemOf(iL, A(), IN());
-      const BufRsrc hb = bufOf(G(A().part) + uint64_t(L.tb) * kNumSymbols);
+      const BufRsrc hb = bufOf(G(ka.part) + uint64_t(Lw.b * ka.team) * kNumSymbols);
 #pragma unroll
       for (uint32_t m = 0; m < kFirst; ++m) {
         const uint32_t k = w + pc::kWaves * m;
-        pa[m] = k < L.team ? ldSc1x4(hb, (k * 64 + lane) * 16) : u32x4{0, 0, 0, 0};
+        pa[m] = k < ka.team ? ldSc1x4(hb, (k * 64 + lane) * 16) : u32x4{0, 0, 0, 0};
       }
       if constexpr (kCk) {
-        if (w == 0) ckv = lane < L.team ? ldSc1(G(A().partCk) + L.tb + lane) : 0u;
+        if (w == 0) ckv = lane < ka.team ? ldSc1(G(ka.partCk) + Lw.b * ka.team + lane) : 0u;
       }
     }
     // (member 0, wave 0) this team's element of round + 2, taken now, if
     // round + 1 has one
     if (hasL && w == 0 && lane == 0) {
-      uint32_t T, X;
-      teamX(T, X);
-      if (X == 0 && elemOfRound(round + 1) < A().nb) dequeueRound(round + 2);
+      if (X == 0 && elemOfRound(ka, T, round + 1) < ka.nb) dequeueRound(ka, T, round + 2);
     }
     // the next round's element: its log entry (written a round ago) read
-    // now, by lane 0 of each wave, in flight over the rest of the window
+    // now, by lane 0 of the wave that decodes the next item, in flight over
+    // the rest of the window
+    constexpr uint32_t kDecodeWave = pc::kWaves - 1;
     uint64_t nextRaw = 0;
-    if (hasL && lane == 0 && round + 1 >= 2 && round + 1 < A().maxR) {
-      uint32_t T, X;
-      teamX(T, X);
-      nextRaw = __hip_atomic_load(G(A().elog) + uint64_t(T) * A().maxR + round + 1, __ATOMIC_RELAXED,
+    if (hasL && w == kDecodeWave && lane == 0 && round + 1 >= 2 && round + 1 < ka.maxR) {
+      nextRaw = __hip_atomic_load(G(ka.elog) + uint64_t(T) * ka.maxR + round + 1, __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (hasE && w == 0) lookBackE(itemOf(iE, A(), IN()));
+    if (hasE && w == 0) lookBackE(Ew, ka);
     // spilled words of E are read back by other waves in place(): a wave
     // that spilled waits for its slot stores
     if (hasE && (p.flushed[0] | p.flushed[1])) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -833,9 +899,9 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
     // 4 KB); wave 0 adds them and normalises L while waves 1-3 place E
     if (hasL) {
       const uint32_t lane = laneNow();
-      const PItem L = itemOf(iL, A(), IN());
-      const uint32_t ep = A().epoch;
-      const BufRsrc hb = bufOf(G(A().part) + uint64_t(L.tb) * kNumSymbols);
+      const PItem& L = Lw;
+      const uint32_t ep = ka.epoch;
+      const BufRsrc hb = bufOf(G(ka.part) + uint64_t(L.b * ka.team) * kNumSymbols);
       auto tagged = [&](const u32x4& v) __attribute__((always_inline)) -> bool {
         return (v.x >> 16) == ep && (v.y >> 16) == ep && (v.z >> 16) == ep && (v.w >> 16) == ep;
       };
@@ -850,11 +916,11 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
 #pragma unroll
       for (uint32_t m = 0; m < kPer; ++m) {
         const uint32_t k = w + pc::kWaves * m;
-        if (k >= L.team) continue;
+        if (k >= ka.team) continue;
         if (m < kFirst && tagged(pa[m])) take(pa[m]);
         else miss |= 1u << m;
       }
-      bool ckMissing = kCk && w == 0 && lane < L.team;
+      bool ckMissing = kCk && w == 0 && lane < ka.team;
       uint32_t ckAcc = 0;
       if (ckMissing && (ckv >> 16) == ep) {
         ckAcc = ckv & 0xffu;
@@ -866,7 +932,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
       bool giveUp = false;
       const uint64_t t0 = realtime();
       for (uint32_t spins = 0; ballot(miss != 0 || ckMissing) != 0; ++spins) {
-        if (spins >= A().spinCap || realtime() - t0 >= A().fallbackTicks) {
+        if (spins >= ka.spinCap || realtime() - t0 >= ka.fallbackTicks) {
           giveUp = true;
           break;
         }
@@ -882,7 +948,7 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
           }
         }
         if (ckMissing) {
-          ckv = ldSc1(G(A().partCk) + L.tb + lane);
+          ckv = ldSc1(G(ka.partCk) + L.b * ka.team + lane);
           if ((ckv >> 16) == ep) {
             ckAcc = ckv & 0xffu;
             ckMissing = false;
@@ -915,41 +981,42 @@ __global__ __launch_bounds__(pc::kThreads) __attribute__((amdgpu_waves_per_eu(4,
           // counted per call (dietgpu_barrier_fallback_count): a nonzero
           // count on an uncontended chip means a hand-off that never lands
           if (lane == 0)
-            __hip_atomic_fetch_add(G(A().err) + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(G(ka.err) + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           countElementWave(L, c, ckL);
         }
         uint32_t cdf[4];
         if (L.n != 0) {
-          normalizeWave(c, cdf, L.n, A().pb);
+          normalizeWave(c, cdf, L.n, ka.pb);
         } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) c[j] = cdf[j] = 0;
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const uint4 e = encTableEntryReg(c[j], cdf[j], A().pb);
+          const uint4 e = encTableEntryReg(c[j], cdf[j], ka.pb);
           *(lp<u32x4>)&tblS[4 * (4 * lane + j)] = u32x4{e.x, e.y, e.z, e.w};
         }
         *(lp<u32x2>)&pdfS[4 * lane] = u32x2{c[0] | (c[1] << 16), c[2] | (c[3] << 16)};
         if (L.x == 0) {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          writeHeadFixedL(L, ckL);
+          writeHeadFixedL(L, ka, ckL);
         }
       }
     }
-    if (hasE && w != 0) place(itemOf(iE, A(), IN()));
-    // the next round's element (logged a round ago): lane 0 of each wave
-    uint32_t iN = A().items;
-    if (hasL) {
-      uint32_t e = 0;
-      if (lane == 0) {
-        e = uint32_t(nextRaw >> 32) == A().epoch ? min(uint32_t(nextRaw), A().nb) : elemOfRound(round + 1);
+    if (hasE && w != 0) place(Ew);
+    // the next round's element (logged a round ago) and its item, decoded
+    // into the record neither E nor L uses, by one wave whose placement is
+    // done (wave 0 is still normalising); the barrier below hands it over
+    if (w == kDecodeWave) {
+      uint32_t e = ka.nb;  // no L: no next item either
+      if (hasL) {
+        if (lane == 0)
+          e = uint32_t(nextRaw >> 32) == ka.epoch ? min(uint32_t(nextRaw), ka.nb) : elemOfRound(ka, T, round + 1);
+        e = readfirst(e);
       }
-      iN = itemOfElem(readfirst(e));
+      decodeItem(kw, ka, e, X, sN);
     }
     __syncthreads();
-    iE = iL;
-    iL = iN;
     ++round;
   }
 }

@@ -45,9 +45,13 @@ if _os.environ.get("STAMP4"):
     names = {0: "top", 1: "segs", 2: "pubH", 10: "deq", 3: "gath", 4: "sig", 5: "norm", 6: "lb", 7: "plc0", 8: "plc1", 9: "syncC"}
     order = [0, 1, 2, 10, 3, 4, 5, 6, 7, 8, 9]
 else:
-    names = {0: "top", 1: "segs", 2: "syncA", 8: "pubH", 3: "split", 4: "wait", 5: "syncB", 10: "parts", 6: "place",
-             7: "norm", 9: "syncC"}
-    order = [0, 1, 2, 8, 3, 4, 5, 10, 6, 7, 9]
+    names = {0: "top", 11: "ld0", 1: "segs", 2: "syncA", 8: "pubH", 3: "split", 4: "wait", 5: "syncB", 10: "parts",
+             6: "place", 12: "dec", 7: "norm", 9: "syncC"}
+    order = [0, 11, 1, 2, 8, 3, 4, 5, 10, 6, 12, 7, 9]
+# wave 0's window steps, as medians of per-workgroup differences: publish,
+# aggregate + gather issue + dequeue, look-back, sum + normalise, header +
+# next item; and the iteration head (start to the first input load)
+STEPS = ((0, 11), (2, 8), (8, 3), (3, 4), (10, 7), (7, 9))
 for it in range(8):
     m = used[:, it]
     if not m.any():
@@ -63,3 +67,11 @@ for it in range(8):
             if v.size:
                 cells.append(f"{names[k]}={np.median(v):.2f}")
         print(f"   w{wv}: " + " ".join(cells))
+    if not _os.environ.get("STAMP4"):
+        cells = []
+        for a, b in STEPS:
+            d = us[m, it, 0, b] - us[m, it, 0, a]
+            d = d[~np.isnan(d)]
+            if d.size:
+                cells.append(f"{names[a]}->{names[b]}={np.median(d):.2f}")
+        print("   w0 steps: " + " ".join(cells))

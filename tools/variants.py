@@ -62,15 +62,19 @@ STAMP3 = [
     (P, "namespace pc {", "__device__ unsigned long long g_stamp[4096 * 8 * 4 * 16];\n#define STAMP(ph) do { if (lane == 0 && itc < 8) { unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); asm volatile(\"\" : \"+v\"(t_)); ((volatile unsigned long long*)g_stamp)[((blockIdx.x * 8 + itc) * 4 + w) * 16 + (ph)] = t_; } } while (0)\nnamespace pc {"),
     (P, "  uint32_t round = 0;\n", "  uint32_t round = 0;\n  uint32_t itc = 0;\n"),
     (P, "    // Segment-phase wave priority rotates", "    STAMP(0);\n    // Segment-phase wave priority rotates"),
+    # the iteration head is over: the round's first input loads issue next
+    (P, "#pragma unroll\n        for (uint32_t g = 0; g < uint32_t(D); ++g) load(dummy, srcL, uwL, g);", "        STAMP(11);\n#pragma unroll\n        for (uint32_t g = 0; g < uint32_t(D); ++g) load(dummy, srcL, uwL, g);"),
     (P, "    __builtin_amdgcn_s_setprio(3);\n", "    STAMP(1);\n    __builtin_amdgcn_s_setprio(3);\n"),
     (P, "    // E's word counts and L's histogram counts are in\n    __syncthreads();\n", "    // E's word counts and L's histogram counts are in\n    __syncthreads();\n    STAMP(2);\n"),
-    (P, "    if (hasL) publishHist(itemOf(iL, A(), IN()));", "    if (hasL) publishHist(itemOf(iL, A(), IN()));\n    STAMP(8);"),
-    (P, "    if (hasE && w == 0) lookBackE(itemOf(iE, A(), IN()));", "    STAMP(3);\n    if (hasE && w == 0) lookBackE(itemOf(iE, A(), IN()));\n    STAMP(4);"),
-    (P, "      const uint32_t ep = A().epoch;", "      STAMP(5);\n      const uint32_t ep = A().epoch;"),
-    (P, "    if (hasE && w != 0) place(itemOf(iE, A(), IN()));", "    if (hasE && w != 0) place(itemOf(iE, A(), IN()));\n    STAMP(6);"),
+    (P, "    if (hasL) publishHist(Lw, ka);", "    if (hasL) publishHist(Lw, ka);\n    STAMP(8);"),
+    (P, "    if (hasE && w == 0) lookBackE(Ew, ka);", "    STAMP(3);\n    if (hasE && w == 0) lookBackE(Ew, ka);\n    STAMP(4);"),
+    (P, "      const uint32_t ep = ka.epoch;", "      STAMP(5);\n      const uint32_t ep = ka.epoch;"),
+    (P, "    if (hasE && w != 0) place(Ew);", "    if (hasE && w != 0) place(Ew);\n    STAMP(6);"),
+    # the decoding wave: the next item's record written
+    (P, "      decodeItem(kw, ka, e, X, sN);\n", "      decodeItem(kw, ka, e, X, sN);\n      STAMP(12);\n"),
     (P, "        if (L.x == 0) {\n          asm volatile", "        STAMP(7);\n        if (L.x == 0) {\n          asm volatile"),
     (P, "      lp<u32x4> red4 = (lp<u32x4>)&hist[0];", "      STAMP(10);\n      lp<u32x4> red4 = (lp<u32x4>)&hist[0];"),
-    (P, "    iE = iL;\n", "    STAMP(9);\n    ++itc;\n    iE = iL;\n"),
+    (P, "    ++round;\n", "    STAMP(9);\n    ++itc;\n    ++round;\n"),
     ("codec.hip", "uint32_t deviceErrorCount(bool reset) {", "extern \"C\" void* dietgpu_debug_stamps() { void* p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_stamp)); return p; }\n\nuint32_t deviceErrorCount(bool reset) {"),
 ]
 # round-3 attribution variants of the three-item pipeline (outputs invalid)
@@ -190,8 +194,8 @@ PLAINALL = PLAINPART + [
 # by tools/skew_check.sh against tests/test_gpu_progress.py.  The product
 # kernel carries no hook (a one-line hook tipped its register allocation,
 # DESIGN.md section 7).
-PSKEW = [(P, "  __syncthreads();  // histogram zeroed\n",
-          "  if (tid == 0) skewDelay(100);\n  __syncthreads();  // histogram zeroed\n")]
+PSKEW = [(P, "  __syncthreads();  // histogram zeroed, records written\n",
+          "  if (tid == 0) skewDelay(100);\n  __syncthreads();  // histogram zeroed, records written\n")]
 # round 5: the decoder's raw float bytes loaded TWO 8-step segments ahead
 # (three register buffers), for archives read cold from HBM
 DEC2A = [(DH, """      int32_t g = min(nSeg, int32_t(nFull)) - 1;  // rvA holds segment g's bytes
