@@ -14,11 +14,27 @@
 // instead of being returned as an empty tensor.  An eleventh operator,
 // decompress_data_range, is not in the reference at all: it decodes a word
 // range of each archive (floatDecompressRange / ansDecodeBatchRange).
+//
+// Argument checks the reference lacks (its DietGpu.cpp says "FIXME: total
+// range checking" where they belong); each raises before any temp-memory
+// allocation or launch, and archives and results of valid calls are unchanged:
+//  - byte mode sizes the archive rows from the widest tensor in bytes, each
+//    with its own element size (the reference: the largest numel() times the
+//    first tensor's element size, too small for [uint8[4097], int32[4096]]);
+//  - compress_data_split_size: the splits must end inside t_in;
+//  - decompress_data_split_size: the splits must end inside t_out;
+//  - decompress_data in float mode: every ts_out[i] has ts_out[0]'s dtype
+//    (the capacities are counted in words of it);
+//  - every compressed input is 4-byte aligned and holds at least the 32-byte
+//    header that the decoders read first.
+// Not checked: a compressed input shorter than the archive that its header
+// describes (the header is on the device).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <limits>
 #include <optional>
@@ -88,6 +104,33 @@ void checkGpuTensor(const at::Tensor& t, int dev) {
   TORCH_CHECK(t.get_device() == dev, "inputs must be on one device");
 }
 
+// The splits of the split-size operators tile `t` from its start and must
+// end inside it: they are words when asFloat and bytes otherwise.  (The
+// reference checks neither: DietGpu.cpp "FIXME: total range checking".)
+void checkSplitSum(uint64_t sum, const at::Tensor& t, bool asFloat, const char* name) {
+  const uint64_t have = asFloat ? uint64_t(t.numel()) : uint64_t(t.numel()) * uint64_t(t.element_size());
+  TORCH_CHECK(sum <= have, "the split sizes sum to ", sum, asFloat ? " words" : " bytes", " but ", name, " holds ",
+              have);
+}
+
+// An archive on the device: contiguous uint8, 4-byte aligned (k_decode reads
+// the headers with scalar loads, which drop the low two address bits: the
+// header of an archive off 4 B alignment would be read from up to three
+// bytes before the tensor; ansDecodeBatchRange checks this itself, the full
+// decoders do not), and at least the 32-byte header that every archive
+// begins with and every decoder and k_info reads first.  (Whether the tensor
+// holds all of the archive that its header describes is not checked: the
+// header is on the device.)
+constexpr int64_t kArchiveHeaderBytes = 32;
+void checkArchiveTensor(const at::Tensor& t, int dev) {
+  TORCH_CHECK(t.device().type() == at::kCUDA && t.get_device() == dev && t.is_contiguous(),
+              "compressed inputs must be contiguous GPU tensors on one device");
+  TORCH_CHECK(t.scalar_type() == at::kByte, "compressed inputs must be uint8");
+  TORCH_CHECK(t.numel() >= kArchiveHeaderBytes, "compressed inputs must hold at least the ", kArchiveHeaderBytes,
+              "-byte archive header");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 4 == 0, "compressed inputs must be 4-byte aligned");
+}
+
 // The arena over the caller's temp_mem tensor (DietGpu.cpp:303-315), or an
 // empty one whose every allocation overflows to hipMalloc.
 StackDeviceMemory makeStack(int dev, const std::optional<at::Tensor>& tempMem) {
@@ -118,7 +161,7 @@ void checkArchiveSizes(const int32_t* sizes, int64_t n) {
 // ---------------------------------------------------------------- sizes ----
 
 std::tuple<int64_t, int64_t> max_float_compressed_output_size(const std::vector<at::Tensor>& ts) {
-  TORCH_CHECK(!ts.empty());
+  TORCH_CHECK(!ts.empty(), "the tensor list must not be empty");
   const auto tm = totalAndMax(ts);
   return {int64_t(ts.size()), int64_t(getMaxFloatCompressedSize(floatTypeOf(ts.front().scalar_type()),
                                                                 uint32_t(tm.second)))};
@@ -130,9 +173,13 @@ int64_t max_float_compressed_size(const at::Tensor& dtype, int64_t size) {
 }
 
 std::tuple<int64_t, int64_t> max_any_compressed_output_size(const std::vector<at::Tensor>& ts) {
-  TORCH_CHECK(!ts.empty());
-  const auto tm = totalAndMax(ts);
-  const uint64_t bytes = tm.second * uint64_t(ts.front().element_size());
+  TORCH_CHECK(!ts.empty(), "the tensor list must not be empty");
+  totalAndMax(ts);
+  // byte mode takes lists of mixed dtypes: the widest member in bytes, each
+  // tensor with its own element size (the reference multiplies the largest
+  // numel() by the first tensor's, DietGpu.cpp:139-148)
+  uint64_t bytes = 0;
+  for (const auto& t : ts) bytes = std::max(bytes, uint64_t(t.numel()) * uint64_t(t.element_size()));
   TORCH_CHECK(bytes <= kU32Max, "tensor too large");
   return {int64_t(ts.size()), int64_t(getMaxCompressedSize(uint32_t(bytes)))};
 }
@@ -152,9 +199,11 @@ std::pair<at::Tensor, at::Tensor> outputTensors(const std::optional<at::Tensor>&
   at::Tensor comp;
   if (outCompressed) {
     const auto& c = *outCompressed;
-    TORCH_CHECK(c.scalar_type() == at::kByte && c.device().type() == at::kCUDA && c.is_contiguous());
-    TORCH_CHECK(c.dim() == 2 && c.size(0) >= n && c.size(1) >= cols);
-    TORCH_CHECK(c.get_device() == dev);
+    TORCH_CHECK(c.scalar_type() == at::kByte && c.device().type() == at::kCUDA && c.is_contiguous(),
+                "out_compressed must be a contiguous uint8 GPU tensor");
+    TORCH_CHECK(c.dim() == 2 && c.size(0) >= n && c.size(1) >= cols, "out_compressed must be 2-d, at least [", n,
+                ", ", cols, "]");
+    TORCH_CHECK(c.get_device() == dev, "out_compressed must be on the input device");
     comp = c;
   } else {
     comp = at::empty({n, cols}, like.options().dtype(at::kByte));
@@ -162,8 +211,10 @@ std::pair<at::Tensor, at::Tensor> outputTensors(const std::optional<at::Tensor>&
   at::Tensor sizes;
   if (outSizes) {
     const auto& s = *outSizes;
-    TORCH_CHECK(s.scalar_type() == at::kInt && s.device().type() == at::kCUDA && s.dim() == 1);
-    TORCH_CHECK(s.is_contiguous() && s.size(0) >= n && s.get_device() == dev);
+    TORCH_CHECK(s.scalar_type() == at::kInt && s.device().type() == at::kCUDA && s.dim() == 1,
+                "out_compressed_bytes must be a 1-d int32 GPU tensor");
+    TORCH_CHECK(s.is_contiguous() && s.size(0) >= n && s.get_device() == dev,
+                "out_compressed_bytes must be contiguous, on the input device, with at least ", n, " entries");
     sizes = s;
   } else {
     sizes = at::empty({n}, like.options().dtype(at::kInt));
@@ -190,7 +241,7 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compressRes(bool asFloat, StackDevic
                                                         const std::vector<at::Tensor>& ts, bool checksum,
                                                         const std::optional<at::Tensor>& outCompressed,
                                                         const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!ts.empty());
+  TORCH_CHECK(!ts.empty(), "the tensor list must not be empty");
   const int dev = ts.front().get_device();
   const auto rc = asFloat ? max_float_compressed_output_size(ts) : max_any_compressed_output_size(ts);
   const int64_t cols = std::get<1>(rc);
@@ -230,7 +281,7 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data(bool asFloat, const st
                                                           bool checksum, const std::optional<at::Tensor>& tempMem,
                                                           const std::optional<at::Tensor>& outCompressed,
                                                           const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!tsIn.empty());
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
@@ -257,21 +308,25 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
     TORCH_CHECK(reinterpret_cast<uintptr_t>(tIn.data_ptr()) % 4 == 0,
                 "All splits should start on a 16 byte boundary; start pointer is not aligned");
   }
-  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt);
+  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt,
+              "t_in_split_sizes must be a contiguous CPU int32 tensor");
   const int64_t n = tSplit.numel();
   const int32_t* sp = tSplit.data_ptr<int32_t>();
   std::vector<uint32_t> split(static_cast<size_t>(n));
   uint32_t mx = 0;
+  uint64_t sum = 0;
   for (int64_t i = 0; i < n; ++i) {
     TORCH_CHECK(sp[i] > 0, "split sizes must be > 0");
     split[size_t(i)] = uint32_t(sp[i]);
     mx = std::max(mx, split[size_t(i)]);
+    sum += split[size_t(i)];
     if (!asFloat && i != n - 1) {
       TORCH_CHECK(sp[i] % 4 == 0,
                   "All splits should start on a 16 byte boundary; the size of an interior split is not a "
                   "multiple of 16 bytes");
     }
   }
+  checkSplitSum(sum, tIn, asFloat, "t_in");
   const int64_t cols = asFloat ? int64_t(getMaxFloatCompressedSize(ft, mx)) : int64_t(getMaxCompressedSize(mx));
   const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, tIn);
   auto res = makeStack(dev, tempMem);
@@ -293,7 +348,7 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
 // DietGpu.cpp:472-526
 std::vector<at::Tensor> compress_data_simple(bool asFloat, const std::vector<at::Tensor>& tsIn, bool checksum,
                                              std::optional<int64_t> tempMem) {
-  TORCH_CHECK(!tsIn.empty());
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
@@ -317,12 +372,16 @@ void checkOutDtype(const at::Tensor& t) {
 void checkStatusTensors(const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes, int64_t n,
                         int dev) {
   if (status) {
-    TORCH_CHECK(status->is_contiguous() && status->device().type() == at::kCUDA && status->scalar_type() == at::kByte);
-    TORCH_CHECK(status->numel() == n && status->get_device() == dev);
+    TORCH_CHECK(status->is_contiguous() && status->device().type() == at::kCUDA && status->scalar_type() == at::kByte,
+                "out_status must be a contiguous uint8 GPU tensor");
+    TORCH_CHECK(status->numel() == n && status->get_device() == dev, "out_status must have ", n,
+                " entries on the input device");
   }
   if (sizes) {
-    TORCH_CHECK(sizes->is_contiguous() && sizes->device().type() == at::kCUDA && sizes->scalar_type() == at::kInt);
-    TORCH_CHECK(sizes->numel() == n && sizes->get_device() == dev);
+    TORCH_CHECK(sizes->is_contiguous() && sizes->device().type() == at::kCUDA && sizes->scalar_type() == at::kInt,
+                "out_decompressed_words must be a contiguous int32 GPU tensor");
+    TORCH_CHECK(sizes->numel() == n && sizes->get_device() == dev, "out_decompressed_words must have ", n,
+                " entries on the input device");
   }
 }
 
@@ -336,7 +395,7 @@ void raiseOnChecksum(bool asFloat, bool mismatch) {
 int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at::Tensor>& tsIn,
                       const std::vector<at::Tensor>& tsOut, bool checksum, const std::optional<at::Tensor>& status,
                       const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size());
+  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
   const int dev = tsIn.front().get_device();
   std::vector<const void*> in(tsIn.size());
   std::vector<void*> out(tsIn.size());
@@ -344,10 +403,15 @@ int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at
   for (size_t i = 0; i < tsIn.size(); ++i) {
     const auto& ti = tsIn[i];
     const auto& to = tsOut[i];
-    TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous());
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous());
-    TORCH_CHECK(ti.scalar_type() == at::kByte, "compressed inputs must be uint8");
-    if (asFloat) checkOutDtype(to);
+    checkArchiveTensor(ti, dev);
+    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
+                "ts_out must be contiguous GPU tensors on the input device");
+    if (asFloat) {
+      checkOutDtype(to);
+      // the config's float type is ts_out[0]'s and every capacity is counted
+      // in words of it
+      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (ts_out) must share a dtype");
+    }
     const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
     TORCH_CHECK(c <= kU32Max);
     in[i] = ti.data_ptr();
@@ -376,7 +440,7 @@ int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at
 int64_t decompress_data(bool asFloat, const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsOut,
                         bool checksum, const std::optional<at::Tensor>& tempMem,
                         const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty());
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
@@ -391,7 +455,7 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
                               const std::vector<at::Tensor>& tsOut, const at::Tensor& tFirst,
                               const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
                               const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size());
+  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
@@ -405,12 +469,12 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
   for (size_t i = 0; i < tsIn.size(); ++i) {
     const auto& ti = tsIn[i];
     const auto& to = tsOut[i];
-    TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous());
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous());
-    TORCH_CHECK(ti.scalar_type() == at::kByte, "compressed inputs must be uint8");
+    checkArchiveTensor(ti, dev);
+    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
+                "ts_out must be contiguous GPU tensors on the input device");
     if (asFloat) {
       checkOutDtype(to);
-      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs must share a dtype");
+      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (ts_out) must share a dtype");
     }
     const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
     TORCH_CHECK(c <= kU32Max);
@@ -441,26 +505,30 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
                                    const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty());
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
-  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt);
+  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt,
+              "t_out_split_sizes must be a contiguous CPU int32 tensor");
   const int64_t n = tSplit.numel();
   TORCH_CHECK(n == int64_t(tsIn.size()), "one split size per compressed input");
   const int32_t* sp = tSplit.data_ptr<int32_t>();
   std::vector<uint32_t> split(static_cast<size_t>(n));
   std::vector<const void*> in(static_cast<size_t>(n));
+  uint64_t sum = 0;
   for (int64_t i = 0; i < n; ++i) {
     const auto& ti = tsIn[size_t(i)];
-    TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous());
-    TORCH_CHECK(ti.scalar_type() == at::kByte);
+    checkArchiveTensor(ti, dev);
     TORCH_CHECK(sp[i] > 0, "split sizes must be > 0");
     split[size_t(i)] = uint32_t(sp[i]);
+    sum += split[size_t(i)];
     in[size_t(i)] = ti.data_ptr();
   }
-  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev && tOut.is_contiguous());
+  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev && tOut.is_contiguous(),
+              "t_out must be a contiguous GPU tensor on the input device");
   if (asFloat) checkOutDtype(tOut);
+  checkSplitSum(sum, tOut, asFloat, "t_out");
   checkStatusTensors(status, sizes, n, dev);
   auto res = makeStack(dev, tempMem);
   auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
@@ -482,13 +550,11 @@ int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& 
 // DietGpu.cpp:834-917
 std::vector<at::Tensor> decompress_data_simple(bool asFloat, const std::vector<at::Tensor>& tsIn, bool checksum,
                                                std::optional<int64_t> tempMem) {
-  TORCH_CHECK(!tsIn.empty());
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
   const int dev = tsIn.front().get_device();
   TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
   c10::hip::HIPGuard guard(dev);
-  for (const auto& t : tsIn) {
-    TORCH_CHECK(t.device().type() == at::kCUDA && t.get_device() == dev && t.is_contiguous());
-  }
+  for (const auto& t : tsIn) checkArchiveTensor(t, dev);  // (before k_info reads the headers)
   std::optional<at::Tensor> scratch;
   if (tempMem && *tempMem >= int64_t(kSDMAlignment)) {
     scratch = at::empty({*tempMem}, tsIn.front().options().dtype(at::kByte));
