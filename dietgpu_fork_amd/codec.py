@@ -297,7 +297,7 @@ def ans_decode_range(archives, firsts, counts, outs=None, prob_bits=10, ws=None)
 def float_decompress_range(archives, firsts, counts, outs=None, dtype=None, prob_bits=10, ws=None):
     """Float words [firsts[i], firsts[i] + counts[i]) of each dense float
     archive into outs[i] -> (outs, ok, sz).  dtype: the archives' float type
-    (default: that of outs[0]); sparse archives are not supported."""
+    (default: that of outs[0]).  Sparse archives: sparse_decompress_range."""
     if outs is None:
         outs = [torch.empty([int(c)], dtype=dtype, device=archives[0].device) for c in counts]
     ft = FLOAT_TYPE[dtype if dtype is not None else outs[0].dtype]
@@ -305,14 +305,32 @@ def float_decompress_range(archives, firsts, counts, outs=None, dtype=None, prob
                        counts, outs, ws)
 
 
-def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None):
+def sparse_decompress_range(archives, firsts, counts, outs=None, dtype=None, prob_bits=10, ws=None):
+    """Float words [firsts[i], firsts[i] + counts[i]) of the element each
+    sparse float archive (16-byte aligned) encodes, into outs[i] -> (outs, ok,
+    sz): a bitmap rank finds the range's slice of the nonzero list, and only
+    that slice is decoded.  dtype: the archives' float type (default: that of
+    outs[0]).  An archive may appear in any number of members; its bitmap is
+    counted once per call."""
+    if outs is None:
+        outs = [torch.empty([int(c)], dtype=dtype, device=archives[0].device) for c in counts]
+    ft = FLOAT_TYPE[dtype if dtype is not None else outs[0].dtype]
+    return _range_call(N.lib().dietgpu_float_decompress_sparse_range, (ft, prob_bits), archives, firsts,
+                       counts, outs, ws)
+
+
+def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None, sparse=False):
     """Rows `rows` (a list or CPU tensor of row indices, repeats allowed) of a
     [R, row_words] table stored as one archive, into one [len(rows),
     row_words] tensor: one batched range decode whose members all read
-    `archive`.  dtype torch.uint8 reads a byte archive.  Returns the tensor;
+    `archive`.  dtype torch.uint8 reads a byte archive; sparse=True reads a
+    sparse float archive (not with torch.uint8).  Returns the tensor;
     reads the status back (a host synchronisation) and raises if any row
     lies outside the table."""
     import numpy as np
+
+    if sparse and dtype == torch.uint8:
+        raise ValueError("gather_rows: sparse archives hold float words, not torch.uint8")
 
     rows = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int64).reshape(-1)
     nb = int(rows.size)
@@ -330,6 +348,8 @@ def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None
     out_ptrs = np.uint64(out.data_ptr()) + np.arange(nb, dtype=np.uint64) * np.uint64(row_words * out.element_size())
     if dtype == torch.uint8:
         fn, head = N.lib().dietgpu_ans_decode_batch_range, (prob_bits,)
+    elif sparse:
+        fn, head = N.lib().dietgpu_float_decompress_sparse_range, (FLOAT_TYPE[dtype], prob_bits)
     else:
         fn, head = N.lib().dietgpu_float_decompress_range, (FLOAT_TYPE[dtype], prob_bits)
     ok, _ = _range_launch(fn, head, archive.device, nb, in_ptrs.ctypes.data, firsts.ctypes.data,

@@ -309,6 +309,15 @@ int dietgpu_float_decompress_range(dietgpu_stack* res, int ft, int pb, uint32_t 
   });
 }
 
+int dietgpu_float_decompress_sparse_range(dietgpu_stack* res, int ft, int pb, uint32_t nb, const void** in,
+                                          const uint32_t* first, const uint32_t* count, void** out,
+                                          uint8_t* succ, uint32_t* sizes, void* stream) {
+  return guarded([&] {
+    floatDecompressSparseRange(R(res), floatCfg(ft, pb, 0), nb, in, first, count, out, succ, sizes, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

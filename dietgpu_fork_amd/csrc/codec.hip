@@ -904,6 +904,13 @@ void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& c
                     [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, b.maxSize); });
 }
 
+void floatDecompressRangeDescs(const FloatDecompressConfig& config, DecodeCall c, uint32_t maxRangeBlocks) {
+  checkFloatConfig(config);
+  c.pb = config.ansConfig.probBits;
+  dispatchFloatType(config.floatType,
+                    [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, maxRangeBlocks); });
+}
+
 FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,
                                                const FloatDecompressConfig& config,
                                                uint32_t numInBatch, const void** in, void* out_dev,

@@ -115,6 +115,13 @@ bool persistentPreferred(uint32_t nb, uint32_t maxWords);
 // it never streams.
 FloatDecompressStatus floatDecompressDescs(const FloatDecompressConfig& config, DecodeCall c);
 
+// The dense range decode on descriptors (codec.hip decodeRangeBatchDevice):
+// words [c.in.size(b), + c.out.size(b)) of float archive c.in.start(b) into
+// c.out, both size columns device arrays a previous kernel may have written.
+// maxRangeBlocks: the most 4096-word blocks a member's range touches.  The
+// float type and prob bits come from the (validated) config.
+void floatDecompressRangeDescs(const FloatDecompressConfig& config, DecodeCall c, uint32_t maxRangeBlocks);
+
 // Compare the checksums stored in the archives c.in with the XOR of the
 // first c.out.size(b) bytes of each decoded element; synchronises c.s.
 std::vector<std::pair<int, std::string>> verifyChecksums(const DecodeCall& c, bool isFloat);

@@ -413,6 +413,10 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
     ok = ok && ah[kAnsMagic] == kANSMagicVersion && (ah[kAnsPrecision] & kTypeMask) == uint32_t(pb) &&
          ah[kAnsSize] == n;
   }
+  // (Every read up to here depends only on the headers: for an element whose
+  // size word is 0 they all lie in its first 64 bytes.  The sparse range
+  // decode relies on that for the zeroed 256 B element it passes for a member
+  // that is no sparse archive, sparse.hip k_sparseRangePlan.)
   // range form: words [rlo, rhi) of the element, blocks [blkFirst, blkEnd)
   uint32_t rlo = 0, rhi = 0;
   bool success;

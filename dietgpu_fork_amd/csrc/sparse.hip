@@ -15,7 +15,10 @@
 // expands one chunk per wave, adding the element's earlier workgroups' totals
 // (k_sparseExpand).  (A decoupled look-back across
 // the tiles of one element measured slower: with thousands of tiles its
-// chain dominates.)
+// chain dominates.)  A word range of an element is read without the rest
+// (floatDecompressSparseRange, an extension): the same chunk counts give the
+// rank of the range's ends, i.e. its slice of the nonzero list; the dense
+// range decode reads that slice and k_sparseExpandRange expands it.
 //
 // Wire format: 16 B header {u32 N, 12 B zero}, bitmap
 // ceil(N/8) bytes (bit 7 of byte k <-> element 8k) padded to 16, then a dense
@@ -568,6 +571,333 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   return status;
 }
 
+// ---------------------------------------------------------------------------
+// Range decode: words [first, first + count) of the element a
+// sparse archive encodes.  rank(i) = the set bitmap bits among words [0, i);
+// gap = N >= 2 && bit(N-2) == 0.  Word i < N-1 lives at list index rank(i),
+// word N-1 at rank(N-1) + gap, so the range needs the list slice
+// [rank(first), rank(end) + (gap && end == N)): at most count + 1 words.
+// Four stream-ordered launches: the chunk counts of each DISTINCT archive
+// (k_sparseRangeChunks), the ranks of each member's range
+// (k_sparseRangePlan), the dense range decode of the list slices into scratch
+// rows (k_decode<RNG>), the expansion (k_sparseExpandRange).
+// ---------------------------------------------------------------------------
+// The device columns of one call: per distinct archive its address and where
+// its counts live, per member its archive's slot, `first` and `count`.
+struct SparseRangeTabs {
+  const uint64_t* archPtr;    // [archives]
+  const uint64_t* archInfo;   // [archives] first k_sparseRangeChunks workgroup | chunks counted << 32
+  const uint64_t* slotFirst;  // [members] archive slot | first << 32
+  const uint32_t* count;      // [members]
+};
+
+// N of the sparse archive at a: word 0 of its header.  The 12 bytes after it
+// are don't-care (the reference leaves them uninitialised) and
+// are not looked at.  A word 0 equal to the float or the ANS magic is a dense
+// float or byte archive passed in by mistake, not an N: no sparse archive
+// holds 3.5e9 words or more (its dense part's raw bytes alone pass the
+// archives' 32-bit sizes in every float type), and a dense archive located
+// sparsePrefixBytes(magic) bytes further would be read far outside the
+// caller's buffer.  Then ok = false, N = 0.
+__device__ __forceinline__ uint32_t sparseSizeOf(gp<const uint8_t> a, bool& ok) {
+  const uint32_t n = readfirst(((gp<const uint32_t>)a)[kSparseSize]);
+  ok = n != kFloatMagicVersion && n != kANSMagicVersion;
+  return ok ? n : 0u;
+}
+
+// r1: k_sparseChunks' counting, once per distinct archive and only for the
+// chunks some member's range needs.  grid (workgroups of the archive with
+// the most chunks, archives): archive a's workgroup g owns chunks [256 g,
+// 256 g + 256) and entries 256 (g0 + g) + t of chunkPre, g0 + g of blockTot.
+// Workgroups wholly past the archive's N or its counted chunks write nothing
+// (no rank reads them).
+__global__ __launch_bounds__(kThreads) void k_sparseRangeChunks(SparseRangeTabs t, uint32_t archOffset,
+                                                                uint32_t* __restrict__ chunkPre,
+                                                                uint32_t* __restrict__ blockTot) {
+  __shared__ uint32_t red[kWaves];
+  const uint32_t slot = archOffset + blockIdx.y;
+  const uint64_t info = BatchDesc::tableAt(t.archInfo, slot);
+  const uint32_t g0 = uint32_t(info), nChunks = uint32_t(info >> 32);
+  if (blockIdx.x * kThreads >= nChunks) return;
+  gp<const uint8_t> a = (gp<const uint8_t>)reinterpret_cast<const uint8_t*>(BatchDesc::tableAt(t.archPtr, slot));
+  bool hdrOk;
+  const uint32_t n = sparseSizeOf(a, hdrOk);
+  if (uint64_t(blockIdx.x) * kThreads * kChunkWords >= n) return;
+  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
+  uint32_t cnt = 0;
+  const uint32_t i0 = c * kChunkWords;  // (c < 2^22 + 256: no wrap)
+  if (c < nChunks && uint64_t(c) * kChunkWords < n) {
+    gp<const uint64_t> bm = (gp<const uint64_t>)(a + kSparseHeaderBytes) + uint64_t(c) * (kChunkWords / 64);
+    uint64_t v[kChunkWords / 64];
+#pragma unroll
+    for (uint32_t k = 0; k < kChunkWords / 64; ++k) v[k] = n - i0 > 64 * k ? bm[k] : 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < kChunkWords / 64; ++k) {
+      uint64_t m = v[k];
+      const uint32_t rem = n - i0 - 64 * k;  // (used only when the word was loaded)
+      if (n - i0 > 64 * k && rem < 64) m = maskToBitmap(m) & ((1ull << rem) - 1);  // element order, tail cut
+      cnt += uint32_t(__popcll(m));
+    }
+  }
+  uint32_t total = 0;
+  const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
+  const uint64_t g = uint64_t(g0) + blockIdx.x;
+  if (c < nChunks) chunkPre[g * kThreads + threadIdx.x] = excl;
+  if (threadIdx.x == 0) blockTot[g] = total;
+}
+
+// This lane's share of rank(i) of archive `bm` (its bitmap), 1 <= i <= N:
+// chunk c = (i - 1) / 1024 holds the boundary (so i == N needs no chunk past
+// the counted ones); lanes stride over the totals of c's earlier workgroups,
+// lanes 0-15 count the chunk's bitmap words below the boundary, lane 16 adds
+// the chunk's prefix.  waveSum of the shares is the rank.
+__device__ __forceinline__ uint32_t rankShare(gp<const uint8_t> bm, gp<const uint32_t> chunkPre,
+                                              gp<const uint32_t> blockTot, uint32_t i, uint32_t lane) {
+  const uint32_t c = (i - 1) / kChunkWords;
+  const uint32_t within = i - c * kChunkWords;  // 1 .. 1024 words of chunk c lie below i
+  const uint32_t g = c / kThreads;
+  uint32_t part = 0;
+  for (uint32_t k0 = 0; k0 < g; k0 += 64) part += k0 + lane < g ? blockTot[k0 + lane] : 0u;
+  if (lane == 16) part += chunkPre[c];
+  if (lane < kChunkWords / 64 && 64 * lane < within) {
+    uint64_t m = maskToBitmap(*(gp<const uint64_t>)(bm + uint64_t(c) * (kChunkWords / 8) + 8 * lane));
+    const uint32_t rem = within - 64 * lane;
+    if (rem < 64) m &= (1ull << rem) - 1;
+    part += uint32_t(__popcll(m));
+  }
+  return part;
+}
+
+// r2: one wave per member: N, the range check, rank(first) and rank(end) ->
+// the dense archive's address, the list slice [listFirst, + listCount) (0, 0
+// for a failing or empty range) and flags (bit 0: the range is valid, bit 1:
+// gap).  A member that is a dense archive (sparseSizeOf) gets `dummy` (64
+// zero words, written here) as its dense archive, so that the dense decoder's
+// header reads -- the first 64 bytes of an element of size 0, see k_decode --
+// stay inside this call's memory and fail its magic check.
+// (at most 80 SGPRs, as its siblings: MI355X_MICROARCH.md, Residency)
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void k_sparseRangePlan(
+    SparseRangeTabs t, uint32_t numInBatch, const uint32_t* __restrict__ chunkPre,
+    const uint32_t* __restrict__ blockTot, uint64_t* __restrict__ densePtrs, uint32_t* __restrict__ listFirst,
+    uint32_t* __restrict__ listCount, uint8_t* __restrict__ flags, uint32_t* __restrict__ dummy) {
+  const uint32_t lane = threadIdx.x & 63, w = readfirst(threadIdx.x >> 6);
+  const uint32_t b = blockIdx.x * kWaves + w;
+  if (b >= numInBatch) return;
+  const uint64_t sf = BatchDesc::tableAt(t.slotFirst, b);
+  const uint32_t slot = uint32_t(sf), first = uint32_t(sf >> 32);
+  const uint32_t count = BatchDesc::tableAt(t.count, b);
+  const uint64_t info = BatchDesc::tableAt(t.archInfo, slot);
+  const uint64_t addr = BatchDesc::tableAt(t.archPtr, slot);
+  gp<const uint8_t> a = (gp<const uint8_t>)reinterpret_cast<const uint8_t*>(addr);
+  bool hdrOk;
+  const uint32_t n = sparseSizeOf(a, hdrOk);
+  const bool ok = hdrOk && first <= n && count <= n - first;
+  uint32_t lf = 0, lc = 0;
+  bool gap = false;
+  if (ok && count != 0) {
+    const uint32_t end = first + count;  // <= n: no wrap
+    gp<const uint8_t> bm = a + kSparseHeaderBytes;
+    gp<const uint32_t> pre = G(chunkPre) + uint64_t(uint32_t(info)) * kThreads;
+    gp<const uint32_t> tot = G(blockTot) + uint32_t(info);
+    gap = n >= 2 && ((bm[(n - 2) / 8] >> (7 - (n - 2) % 8)) & 1) == 0;
+    const uint32_t s0 = first ? rankShare(bm, pre, tot, first, lane) : 0u;
+    const uint32_t s1 = rankShare(bm, pre, tot, end, lane);
+    lf = waveSum(s0);
+    lc = waveSum(s1) - lf + (gap && end == n ? 1u : 0u);
+  }
+  if (!hdrOk) G(dummy)[lane] = 0;
+  if (lane == 0) {
+    G(densePtrs)[b] = hdrOk ? addr + sparsePrefixBytes(n) : reinterpret_cast<uint64_t>(dummy);
+    G(listFirst)[b] = lf;
+    G(listCount)[b] = lc;
+    G(flags)[b] = uint8_t((ok ? 1u : 0u) | (gap ? 2u : 0u));
+  }
+}
+
+// r4: expand the decoded list slices into the outputs, built like
+// k_sparseExpand: one wave per 1024-word chunk the range touches (grid
+// (ceil((ceil(maxCount / 1024) + 1) / 4), members): a range's start inside a
+// chunk is arbitrary), 16 bitmap words in lanes 0-15, a row's mask per
+// readlane, list index = the chunk's rank - listFirst + v_mbcnt (modulo 2^32:
+// the first chunk's rank lies at or below listFirst), every gather issued
+// before the stores; no LDS, no barrier.  Rows are masked to [first, end);
+// word i goes to out[i - first] with plain stores (the destination is not
+// row-aligned and is read right after).  Members that failed return before
+// any index is formed: for the others every index lies in [0, listCount) by
+// construction (listCount counts the same bitmap bits), whatever a corrupt
+// bitmap holds.  Writes outSuccess / outSize of every member.
+// (at most 80 SGPRs, as its siblings: MI355X_MICROARCH.md, Residency)
+template <int FT>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void k_sparseExpandRange(
+    SparseRangeTabs t, BatchDesc out, uint32_t batchOffset, const uint32_t* __restrict__ chunkPre,
+    const uint32_t* __restrict__ blockTot, const uint32_t* __restrict__ listFirst,
+    const uint8_t* __restrict__ flags, BatchDesc lists, const uint8_t* __restrict__ denseOk,
+    uint8_t* __restrict__ outSuccess, uint32_t* __restrict__ outSize) {
+  using W = WordOf<FT>;
+  constexpr uint32_t kRows = kChunkWords / 64;
+  const uint32_t b = batchOffset + blockIdx.y;
+  const uint32_t count = BatchDesc::tableAt(t.count, b);
+  const uint32_t fl = flags[b];
+  const bool ok = (fl & 1) != 0 && denseOk[b] != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (outSuccess) G(outSuccess)[b] = ok ? 1 : 0;
+    if (outSize) G(outSize)[b] = ok ? count : 0u;
+  }
+  if (!ok || count == 0) return;
+  const uint64_t sf = BatchDesc::tableAt(t.slotFirst, b);
+  const uint32_t slot = uint32_t(sf), first = uint32_t(sf >> 32);
+  const uint32_t end = first + count;  // <= N (k_sparseRangePlan)
+  const uint32_t lane = threadIdx.x & 63, w = readfirst(threadIdx.x >> 6);
+  const uint32_t c = first / kChunkWords + blockIdx.x * kWaves + w;
+  if (c > (end - 1) / kChunkWords) return;
+  const uint32_t i0 = c * kChunkWords;
+  const uint64_t info = BatchDesc::tableAt(t.archInfo, slot);
+  gp<const uint8_t> a = (gp<const uint8_t>)reinterpret_cast<const uint8_t*>(BatchDesc::tableAt(t.archPtr, slot));
+  gp<const uint8_t> bm = a + kSparseHeaderBytes;
+  uint64_t mv = 0;
+  if (lane < kRows && 64 * lane < end - i0) mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
+  // the chunk's rank, as k_sparseExpand sums it, less the slice's start
+  gp<const uint32_t> tot = G(blockTot) + uint32_t(info);
+  const uint32_t g = c / kThreads;
+  uint32_t part = 0;
+  for (uint32_t k0 = 0; k0 < g; k0 += 64) part += k0 + lane < g ? tot[k0 + lane] : 0u;
+  uint32_t base = readfirst(G(chunkPre)[uint64_t(uint32_t(info)) * kThreads + c]) + waveSum(part) -
+                  BatchDesc::tableAt(listFirst, b);
+  // x[N-1] is read one slot further when x[N-2] == 0: only a range that ends
+  // at N reaches it
+  const uint32_t n = ((gp<const uint32_t>)a)[kSparseSize];
+  const bool gap = (fl & 2) != 0;
+  gp<const W> list = (gp<const W>)lists.start(b);
+  W v[kRows];
+#pragma unroll
+  for (uint32_t j = 0; j < kRows; ++j) {
+    const uint64_t m = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv >> 32)), int(j)))) << 32) |
+                       uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv)), int(j)));
+    const uint32_t i = i0 + 64 * j + lane;
+    uint32_t src = base + mbcnt(m);
+    if (gap && i + 1 == n) src += 1;
+    // (i0 + 1023 may wrap past 2^32 - 1 in the last chunk of a 2^32-word
+    // element: compare offsets from i0, which do not)
+    const bool in = i - i0 < end - i0 && i >= first;
+    v[j] = in && ((m >> lane) & 1) ? list[src] : W(0);
+    base += uint32_t(__popcll(m));
+  }
+  gp<W> y = (gp<W>)out.start(b);
+#pragma unroll
+  for (uint32_t j = 0; j < kRows; ++j) {
+    const uint32_t i = i0 + 64 * j + lane;
+    if (i - i0 < end - i0 && i >= first) y[i - first] = v[j];
+  }
+}
+
+// One range call: the members `in` (archives), first / count / out as host
+// columns, already validated.
+struct SparseRangeCall {
+  StackDeviceMemory& res;
+  hipStream_t s;
+  uint32_t nb;
+  const std::vector<uint64_t>& in;
+  const std::vector<uint64_t>& out;
+  const uint32_t* first;
+  const uint32_t* count;
+  uint8_t* outSuccess_dev;
+  uint32_t* outSize_dev;
+};
+
+template <int FT>
+void sparseRangeT(const FloatDecompressConfig& config, const SparseRangeCall& c) {
+  using W = WordOf<FT>;
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const uint32_t nb = c.nb;
+  // the distinct archives and, of each, the largest range end among its
+  // members (64 bits: first + count may pass 2^32; such a member fails on the
+  // device, where N is known)
+  std::vector<uint32_t> order(nb);
+  for (uint32_t i = 0; i < nb; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return c.in[x] < c.in[y]; });
+  std::vector<uint64_t> archPtr, maxEnd, slotFirst(nb);
+  uint32_t maxCount = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t i = order[k];
+    if (k == 0 || c.in[i] != archPtr.back()) {
+      archPtr.push_back(c.in[i]);
+      maxEnd.push_back(0);
+    }
+    slotFirst[i] = uint64_t(archPtr.size() - 1) | (uint64_t(c.first[i]) << 32);
+    // a range that ends past 2^32 - 1 words fails whatever N is (the plan
+    // kernel refuses it; nothing is counted, decoded or expanded for it), so
+    // it sizes neither the counts nor the scratch rows
+    const uint64_t end = uint64_t(c.first[i]) + c.count[i];
+    if (end > uint64_t(UINT32_MAX)) continue;
+    maxEnd.back() = std::max(maxEnd.back(), end);
+    maxCount = std::max(maxCount, c.count[i]);
+  }
+  const uint32_t nArch = uint32_t(archPtr.size());
+  std::vector<uint64_t> archInfo(nArch);
+  uint64_t totalBlocks = 0;
+  uint32_t maxCblocks = 1;
+  for (uint32_t a = 0; a < nArch; ++a) {
+    const uint64_t chunks = (maxEnd[a] + kChunkWords - 1) / kChunkWords;  // <= 2^22
+    const uint32_t cblocks = uint32_t((chunks + kThreads - 1) / kThreads);
+    archInfo[a] = totalBlocks | (chunks << 32);
+    totalBlocks += cblocks;
+    maxCblocks = std::max(maxCblocks, cblocks);
+  }
+  DG_CHECK(totalBlocks * kThreads <= uint64_t(UINT32_MAX), "range ends too large for one call");
+  const std::vector<uint32_t> counts(c.count, c.count + nb);
+  const auto t = uploadTables(res, s, {&archPtr, &archInfo, &c.out, &slotFirst}, counts);
+  const SparseRangeTabs tabs{t.u64[0], t.u64[1], t.u64[3], t.u32};
+  auto chunkPre = res.alloc<uint32_t>(s, std::max<size_t>(size_t(totalBlocks) * kThreads, 1));
+  auto blockTot = res.alloc<uint32_t>(s, std::max<size_t>(size_t(totalBlocks), 1));
+  auto densePtrs = res.alloc<uint64_t>(s, nb);
+  auto listFirst = res.alloc<uint32_t>(s, nb);
+  auto listCount = res.alloc<uint32_t>(s, nb);
+  auto flags = res.alloc<uint8_t>(s, nb);
+  auto denseOk = res.alloc<uint8_t>(s, nb);
+  auto dummy = res.alloc<uint32_t>(s, 64);
+  // the list slices: 16 B-aligned rows of count + 1 words at most.  Sized by
+  // the call's largest count before any N is known: a member whose count
+  // cannot be valid but still ends below 2^32 makes every row that long, and
+  // a call whose rows do not fit the arena throws (GpuFloatCodec.h)
+  const uint64_t rowWords = (uint64_t(maxCount) + 1 + 15) / 16 * 16 + 16;
+  auto slices = res.alloc<uint8_t>(s, size_t(nb) * rowWords * sizeof(W));
+  if (totalBlocks != 0) {
+    forGridYSlices(nArch, [&](uint32_t y0, uint32_t ny) {
+      prof::Scope p("sparse", s);
+      k_sparseRangeChunks<<<dim3(maxCblocks, ny), kThreads, 0, s>>>(tabs, y0, chunkPre.data(), blockTot.data());
+      HIP_LAUNCH_CHECK();
+    });
+  }
+  {
+    prof::Scope p("sparse", s);
+    k_sparseRangePlan<<<divUp(nb, kWaves), kThreads, 0, s>>>(tabs, nb, chunkPre.data(), blockTot.data(),
+                                                             densePtrs.data(), listFirst.data(), listCount.data(),
+                                                             flags.data(), dummy.data());
+    HIP_LAUNCH_CHECK();
+  }
+  // dense range decode of the slices.  The slice's start inside a block is
+  // not known here, hence one block more (workgroups past a slice's last
+  // block return at once)
+  DecodeCall dense{res, s};
+  dense.nb = nb;
+  dense.in = BatchDesc::pointers(densePtrs.data(), listFirst.data());
+  dense.out = BatchDesc::strided(slices.data(), rowWords * sizeof(W), 0);
+  dense.out.sizes = listCount.data();
+  dense.outSuccess_dev = denseOk.data();
+  const uint32_t maxRangeBlocks = uint32_t((uint64_t(maxCount) + 1 + kBlockSize - 1) / kBlockSize) + 1;
+  floatDecompressRangeDescs(config, dense, maxRangeBlocks);
+  const BatchDesc outs = BatchDesc::pointers(t.u64[2], nullptr);
+  const uint32_t chunkWaves = uint32_t((uint64_t(maxCount) + kChunkWords - 1) / kChunkWords) + 1;
+  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
+    prof::Scope p("sparse", s);
+    k_sparseExpandRange<FT><<<dim3(divUp(chunkWaves, kWaves), ny), kThreads, 0, s>>>(
+        tabs, outs, y0, chunkPre.data(), blockTot.data(), listFirst.data(), flags.data(), dense.out, denseOk.data(),
+        c.outSuccess_dev, c.outSize_dev);
+    HIP_LAUNCH_CHECK();
+  });
+}
+
 }  // namespace
 
 uint32_t getMaxSparseFloatCompressedSize(FloatType ft, uint32_t size) {
@@ -633,6 +963,29 @@ FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
   c.outSize_dev = outSize_dev;
   return dispatchFloatType(config.floatType,
                            [&](auto f) { return sparseDecompressT<decltype(f)::value>(config, c); });
+}
+
+// Every host check precedes the first allocation, upload or launch.
+void floatDecompressSparseRange(StackDeviceMemory& res, const FloatDecompressConfig& config,
+                                uint32_t numInBatch, const void** in, const uint32_t* first,
+                                const uint32_t* count, void** out, uint8_t* outSuccess_dev,
+                                uint32_t* outSize_dev, hipStream_t stream) {
+  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
+  const int ft = int(config.floatType);
+  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
+  const int pb = config.ansConfig.probBits;
+  DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  if (numInBatch == 0) return;
+  const uint32_t ws = floatWordBytes(ft);
+  const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DG_CHECK(op[i] % ws == 0, "float output " << i << " not aligned to its word size");
+    // (the compressor requires it of its output; the bitmap is read as u64)
+    DG_CHECK(ip[i] % 16 == 0, "sparse archive " << i << " must be 16-byte aligned");
+  }
+  const SparseRangeCall c{res, stream, numInBatch, ip, op, first, count, outSuccess_dev, outSize_dev};
+  dispatchFloatType(config.floatType, [&](auto f) { sparseRangeT<decltype(f)::value>(config, c); });
 }
 
 }  // namespace dietgpu

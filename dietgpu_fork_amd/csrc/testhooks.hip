@@ -144,6 +144,20 @@ int dietgpu_test_range_config(dietgpu_stack* res, int float_type, int use_checks
   });
 }
 
+int dietgpu_test_sparse_range_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                     uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
+                                     uint32_t* out_size_dev, void* stream) {
+  return guardedTest([&] {
+    using namespace dietgpu;
+    DG_CHECK(res && res->mem, "null dietgpu_stack");
+    DG_CHECK(float_type >= 1 && float_type <= 4, "float_type must be 1..4");
+    const FloatDecompressConfig cfg(FloatType(float_type), ANSCodecConfig(kANSDefaultProbBits), false,
+                                    use_checksum != 0);
+    floatDecompressSparseRange(*res->mem, cfg, 1, &in, &first, &count, &out, out_success_dev, out_size_dev,
+                               reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
 int dietgpu_test_enc_magic(uint32_t* magic_dev, void* stream) {
   return guardedTest([&] { dietgpu::testEncMagic(reinterpret_cast<hipStream_t>(stream), magic_dev); });
 }

@@ -128,13 +128,39 @@ FloatDecompressStatus floatDecompressBatchStride(
     uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream);
 
 // Range decode of dense float archives (see ansDecodeBatchRange): first /
-// count in float words, out[b] word-aligned.  Sparse archives are not
-// supported (a word's position in the nonzero list needs a bitmap rank).
+// count in float words, out[b] word-aligned.  For sparse archives:
+// floatDecompressSparseRange.
 void floatDecompressRange(StackDeviceMemory& res,
                           const FloatDecompressConfig& config,
                           uint32_t numInBatch, const void** in,
                           const uint32_t* first, const uint32_t* count,
                           void** out, uint8_t* outSuccess_dev,
                           uint32_t* outSize_dev, hipStream_t stream);
+
+// Range decode of sparse float archives: out[b][j] = word first[b] + j of the
+// element that sparse archive in[b] encodes, 0 <= j < count[b], bitwise what
+// floatDecompressSparse puts there; nothing else is written.  A bitmap rank
+// locates the range's slice of the nonzero list, a dense range decode reads
+// that slice only.  in[b] 16-byte aligned, out[b] word-aligned; an archive may
+// appear in any number of members (its bitmap is counted once per call).
+// outSuccess_dev[b] = 1 iff the range lies inside in[b]'s element
+// (first <= N && count <= N - first), the dense archive is valid for this
+// config and holds the list slice; outSize_dev[b] = count[b] then, else 0
+// (and out[b] is untouched).  An empty range succeeds.  Header bytes 4..15
+// are ignored, as by floatDecompressSparse; a dense float or byte archive
+// passed in (word 0 is its magic) fails without being read further.
+// Temporary memory is sized before any N is known: numInBatch rows of the
+// largest count[b] + 32 words (members with first + count >= 2^32, which
+// always fail, aside), and 4 bytes per 1024 words up to each archive's
+// largest range end.  A call whose rows do not fit `res` throws as a whole,
+// so one absurd count turns per-member status into a call-level error.
+// config.useChecksum must be false (archives written with a checksum decode
+// normally).  No host synchronisation.
+void floatDecompressSparseRange(StackDeviceMemory& res,
+                                const FloatDecompressConfig& config,
+                                uint32_t numInBatch, const void** in,
+                                const uint32_t* first, const uint32_t* count,
+                                void** out, uint8_t* outSuccess_dev,
+                                uint32_t* outSize_dev, hipStream_t stream);
 
 } // namespace dietgpu

@@ -31,6 +31,8 @@
  *   dietgpu_ans_decode_batch_range, dietgpu_float_decompress_range (words
  *   [first, first + count) of an archive; no checksum flag: a range cannot be
  *   checked against a whole element's checksum)
+ *   dietgpu_float_decompress_sparse_range (the same of a sparse archive: a
+ *   bitmap rank, then a range decode of the nonzero list's slice)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -179,6 +181,16 @@ int dietgpu_float_decompress_range(dietgpu_stack* res, int float_type, int prob_
                                    uint32_t num_in_batch, const void** in, const uint32_t* first,
                                    const uint32_t* count, void** out, uint8_t* out_success_dev,
                                    uint32_t* out_size_dev, void* stream);
+/* ... of sparse float archives (in[b] 16-byte aligned).  out_success_dev[b] =
+ * 1 iff the range lies inside in[b]'s element and the dense archive is valid
+ * and holds the nonzero list's slice (a dense archive passed in fails).
+ * Temporary memory: num_in_batch rows of the largest count + 32 words; a call
+ * whose rows do not fit `res` returns an error as a whole. */
+int dietgpu_float_decompress_sparse_range(dietgpu_stack* res, int float_type, int prob_bits,
+                                          uint32_t num_in_batch, const void** in,
+                                          const uint32_t* first, const uint32_t* count, void** out,
+                                          uint8_t* out_success_dev, uint32_t* out_size_dev,
+                                          void* stream);
 
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "hist", "coalesce") is bracketed

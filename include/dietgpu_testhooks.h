@@ -51,6 +51,12 @@ int dietgpu_test_range_config(dietgpu_stack* res, int float_type, int use_checks
                               uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
                               uint32_t* out_size_dev, void* stream);
 
+/* The same for floatDecompressSparseRange (float_type 1..4, `in` a sparse
+ * archive). */
+int dietgpu_test_sparse_range_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                     uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
+                                     uint32_t* out_size_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
