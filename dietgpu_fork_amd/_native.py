@@ -81,6 +81,7 @@ def _declare(L):
         "dietgpu_ans_decode_batch_range": (c_int, [vp, c_int, c_u32, P, P, P, P, P, P, P]),
         "dietgpu_float_decompress_range": (c_int, [vp, c_int, c_int, c_u32, P, P, P, P, P, P, P]),
         "dietgpu_float_decompress_sparse_range": (c_int, [vp, c_int, c_int, c_u32, P, P, P, P, P, P, P]),
+        "dietgpu_float_decompress_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),

@@ -256,6 +256,41 @@ def float_decompress_pointer(archives, outs, ft=None, prob_bits=10, checksum=Fal
     return ok, sz
 
 
+def float_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None):
+    """accs[i] += the element dense float archive archives[i] encodes, in one
+    kernel (k_decode's accumulate form) -> (ok, sz) as float_decompress_pointer.
+    The accumulators' dtype selects the mode: the archives' own float type (the
+    sum is formed in it), or float32 for fp16 / bf16 archives (acc + float(x));
+    `ft` names the archives' type and defaults to the accumulators'.  One
+    accumulator dtype per call; accumulators of two members must not overlap.
+    A failing member's accumulator is untouched.  No checksum is verified."""
+    nb = len(archives)
+    if len(accs) != nb:
+        raise ValueError("archives and accs must have one entry per member")
+    if nb == 0:
+        raise ValueError("float_decompress_accumulate: empty batch")
+    if any(a.dtype != accs[0].dtype for a in accs):
+        raise ValueError("float_decompress_accumulate: the accumulators must share a dtype")
+    if accs[0].dtype not in FLOAT_TYPE:
+        raise ValueError(f"float_decompress_accumulate: unsupported accumulator dtype {accs[0].dtype}")
+    if any(not a.is_contiguous() for a in accs):
+        raise ValueError("float_decompress_accumulate: the accumulators must be contiguous")
+    acc_ft = FLOAT_TYPE[accs[0].dtype]
+    ft = ft or acc_ft
+    if not (acc_ft == ft or (ft in (1, 2) and acc_ft == 3)):
+        raise ValueError(f"float_decompress_accumulate: accumulator type {acc_ft} does not go with float type {ft}")
+    dev = archives[0].device
+    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
+    sz = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    rc = N.lib().dietgpu_float_decompress_accumulate(
+        ws.h, ft, prob_bits, nb, N.ptr_array([a.data_ptr() for a in archives]),
+        N.ptr_array([a.data_ptr() for a in accs]), N.u32_array([a.numel() for a in accs]), acc_ft,
+        ok.data_ptr(), sz.data_ptr(), _s())
+    N.check(rc)
+    return ok, sz
+
+
 # ---------------------------------------------------------------- range ----
 
 def _range_launch(fn, head, dev, nb, in_ptrs, firsts, counts, out_ptrs, ws):

@@ -318,6 +318,22 @@ int dietgpu_float_decompress_sparse_range(dietgpu_stack* res, int ft, int pb, ui
   });
 }
 
+int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int ft, int pb, uint32_t nb, const void** in,
+                                        void** acc, const uint32_t* cap, int acc_type, uint8_t* succ,
+                                        uint32_t* sizes, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at: a bad pair is refused
+    // whatever else the call holds)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    DG_CHECK(acc_type == ft || ((ft == 1 || ft == 2) && acc_type == 3),
+             "acc_type " << acc_type << " does not go with float_type " << ft
+                         << " (float_type itself, or 3 for float_type 1 / 2)");
+    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    floatDecompressAccumulate(R(res), cfg, nb, in, acc, cap, FloatType(acc_type), succ, sizes, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

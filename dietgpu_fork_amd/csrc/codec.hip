@@ -500,6 +500,32 @@ void decodeRangeBatchDevice(const DecodeCall& c, uint32_t maxRangeBlocks) {
   });
 }
 
+// Decode-and-accumulate: acc[b][i] += word i of archive b,
+// c.out being the accumulators (capacities in accumulator words).  The full
+// decode's grid rule -- P chunks per workgroup from the resident-slot count of
+// the instance launched -- without remaining-work priorities, and plain
+// stores: the accumulator is read again by the next peer's call.
+template <int FT, int ACC>
+void decodeAccumulateBatchDevice(const DecodeCall& c) {
+  checkProbBits(c.pb);
+  if (c.nb == 0) return;
+  using Cfg = DecCfg<FT>;
+  constexpr uint32_t kMaxDecodeChunks = 8;  // as decodeBatchDevice
+  const uint32_t lds = Cfg::ldsBytes(c.pb);
+  const uint32_t chunks = std::max(1u, divUp(divUp(c.maxCapacity, kBlockSize), uint32_t(Cfg::kBlocksPerWG)));
+  const uint32_t slots = residentSlots(reinterpret_cast<const void*>(&k_decode<FT, false, false, false, ACC>),
+                                       dec::kThreads, lds);
+  forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
+    prof::Scope p("decode_accumulate", c.s);
+    const uint32_t P =
+        std::min(kMaxDecodeChunks, std::max(1u, uint32_t((uint64_t(chunks) * ny + slots / 2) / slots)));
+    dim3 g(divUp(chunks, P), ny);
+    k_decode<FT, false, false, false, ACC><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
+                                                                          P, c.outSuccess_dev, c.outSize_dev);
+    HIP_LAUNCH_CHECK();
+  });
+}
+
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
 // (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112; the float
 // codec checksums `capacity` bytes, float words treated as bytes).  Host sync.
@@ -902,6 +928,34 @@ void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& c
   c.pb = config.ansConfig.probBits;
   dispatchFloatType(config.floatType,
                     [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, b.maxSize); });
+}
+
+void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,
+                               const void** in, void** acc, const uint32_t* accCapacity, FloatType accType,
+                               uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
+  checkFloatConfig(config);
+  DG_CHECK(!config.useChecksum,
+           "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded words)");
+  const bool half = config.floatType == FloatType::kFloat16 || config.floatType == FloatType::kBFloat16;
+  const bool wide = half && accType == FloatType::kFloat32;
+  DG_CHECK(accType == config.floatType || wide,
+           "accumulator type " << int(accType) << " does not go with float type " << int(config.floatType)
+                               << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
+  if (numInBatch == 0) return;
+  for (uint32_t i = 0; i < numInBatch; ++i)
+    // (the decoder reads the headers with scalar loads, which drop the low
+    // two address bits)
+    DG_CHECK(reinterpret_cast<uintptr_t>(in[i]) % 4 == 0, "archive " << i << " must be 4-byte aligned");
+  const auto b = pointerBatch(res, stream, numInBatch, in, acc, accCapacity, false, floatWordBytes(int(accType)));
+  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
+  c.pb = config.ansConfig.probBits;
+  dispatchFloatType(config.floatType, [&](auto ft) {
+    constexpr int FT = decltype(ft)::value;
+    if constexpr (FT == 1 || FT == 2) {
+      if (wide) return decodeAccumulateBatchDevice<FT, 2>(c);
+    }
+    decodeAccumulateBatchDevice<FT, 1>(c);
+  });
 }
 
 void floatDecompressRangeDescs(const FloatDecompressConfig& config, DecodeCall c, uint32_t maxRangeBlocks) {

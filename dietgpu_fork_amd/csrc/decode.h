@@ -27,6 +27,10 @@
 //    earlier) and writes them with 16 B stores.
 //  * The same kernel body decodes a word range of an element (RNG, DESIGN.md
 //    5.2b): only the blocks the range touches, masked at the range's edges.
+//  * ... and adds the joined words to the destination instead of storing them
+//    (ACC): the destination words are loaded a segment ahead
+//    beside the raw bytes, the sum is the correctly rounded one in the
+//    accumulator's type, which for fp16 / bf16 archives may be fp32.
 #pragma once
 
 #include <type_traits>
@@ -193,11 +197,21 @@ __device__ __forceinline__ void setPrioRemaining(uint32_t left, uint32_t total) 
 }
 
 // Join 8 decoded symbols (u16 sym << 8 in LDS) with their raw bytes.
-template <int FT>
+// ACC: what becomes of the joined words x: 0 stored; 1 added
+// to the destination in the archive's word type, acc = acc + x; 2 (fp16 /
+// bf16 only) added to an fp32 destination, acc = acc + float(x).
+template <int FT, int ACC = 0>
 struct Join {
+  static_assert(ACC == 0 || (FT != 0 && (ACC == 1 || (ACC == 2 && (FT == 1 || FT == 2)))),
+                "accumulate: float archives only; an fp32 accumulator only for fp16 / bf16");
   using WordT = typename FloatTraits<FT>::WordT;
+  // the accumulator's words (bit patterns)
+  using AccT = std::conditional_t<ACC == 2, uint32_t, WordT>;
   // raw dwords per 8-word chunk
   static constexpr int kR = FT == 0 ? 1 : (FT <= 2 ? 2 : (FT == 3 ? 6 : 12));
+  // dwords of the 8 joined words / of the 8 accumulator words of a chunk
+  static constexpr int kW = 2 * int(sizeof(WordT));
+  static constexpr int kD = ACC == 0 ? 1 : 2 * int(sizeof(AccT));
 
   // raw bytes of the chunk starting at word i0 (i0 a multiple of 8)
   static __device__ __forceinline__ void load(uint32_t (&r)[kR], gp<const uint8_t> raw, uint32_t n,
@@ -304,6 +318,135 @@ struct Join {
       }
     }
   }
+
+  // ---- accumulate forms (ACC != 0) ----
+  // acc + x, correctly rounded (nearest even, denormals kept) in the
+  // accumulator's type, on bit patterns.  16-bit accumulators: fp16 adds in
+  // the type itself; bf16 widens to f32, adds and rounds once, which is the
+  // correctly rounded bf16 sum (an f32 sum of two 8-bit significands is exact
+  // or rounds innocuously: 24 >= 2 * 8 + 2).
+  static __device__ __forceinline__ float widen(uint32_t h) {  // a 16-bit word (upper half ignored) as f32
+    if constexpr (FT == 1) return float(__builtin_bit_cast(_Float16, uint16_t(h)));
+    else return __builtin_bit_cast(float, h << 16);
+  }
+  static __device__ __forceinline__ uint32_t bf16Of(float f) {
+    return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f));
+  }
+  static __device__ __forceinline__ uint32_t f32Sum(uint32_t a, float x) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, a) + x);
+  }
+  // two packed 16-bit words (ACC 1)
+  static __device__ __forceinline__ uint32_t sumPk16(uint32_t a, uint32_t x) {
+    if constexpr (FT == 1) {
+      typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+      return __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, a) + __builtin_bit_cast(h2, x));
+    } else {
+      const float lo = __builtin_bit_cast(float, a << 16) + __builtin_bit_cast(float, x << 16);
+      const float hi = __builtin_bit_cast(float, a & 0xffff0000u) + __builtin_bit_cast(float, x & 0xffff0000u);
+      return bf16Of(lo) | (bf16Of(hi) << 16);
+    }
+  }
+  static __device__ __forceinline__ AccT sumOne(AccT a, WordT x) {
+    if constexpr (ACC == 2) {
+      return f32Sum(a, widen(x));
+    } else if constexpr (FT == 1) {
+      return __builtin_bit_cast(uint16_t, _Float16(__builtin_bit_cast(_Float16, a) + __builtin_bit_cast(_Float16, x)));
+    } else if constexpr (FT == 2) {
+      return AccT(bf16Of(widen(a) + widen(x)));
+    } else if constexpr (FT == 3) {
+      return f32Sum(a, __builtin_bit_cast(float, x));
+    } else {
+      return __builtin_bit_cast(uint64_t, __builtin_bit_cast(double, a) + __builtin_bit_cast(double, x));
+    }
+  }
+
+  // the joined words of a full chunk as dwords in memory order: vec()'s join
+  // without its stores (vec itself stays as it is: restating it over this
+  // changed the code of existing instances)
+  static __device__ __forceinline__ void words(uint32_t (&o)[kW], const uint32_t (&s)[4], const uint32_t (&s1)[4],
+                                               const uint32_t (&r)[kR]) {
+    if constexpr (FT == 0) {
+      o[0] = __builtin_amdgcn_perm(s[1], s[0], 0x07050301u);
+      o[1] = __builtin_amdgcn_perm(s[3], s[2], 0x07050301u);
+    } else if constexpr (FT == 1 || FT == 2) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t t = pair16(s[k], r[k >> 1], k & 1);  // exp << 8 | raw per half
+        // bf16: rotate each 16-bit half right by one (raw = mant << 1 | sign)
+        o[k] = FT == 1 ? t : (((t >> 1) & 0x7fff7fffu) | ((t << 15) & 0x80008000u));
+      }
+    } else if constexpr (FT == 3) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t h = pair16(s[k], r[4 + (k >> 1)], k & 1);  // [hb, sym] x 2
+        const uint32_t w0 = __builtin_amdgcn_perm(h, r[k], 0x05040100u);
+        const uint32_t w1 = __builtin_amdgcn_perm(h, r[k], 0x07060302u);
+        o[2 * k] = __builtin_amdgcn_alignbit(w0, w0, 1);
+        o[2 * k + 1] = __builtin_amdgcn_alignbit(w1, w1, 1);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // [s1, s0] pairs, then vhi = [h16, s1, s0] per word; w = rotr64(vhi:lo, 1)
+        const uint32_t p = __builtin_amdgcn_perm(s[k], s1[k], 0x07030501u);
+        const uint32_t vh0 = __builtin_amdgcn_perm(p, r[8 + k], 0x05040100u);
+        const uint32_t vh1 = __builtin_amdgcn_perm(p, r[8 + k], 0x07060302u);
+        const uint32_t l0 = r[2 * k], l1 = r[2 * k + 1];
+        o[4 * k] = __builtin_amdgcn_alignbit(vh0, l0, 1);
+        o[4 * k + 1] = __builtin_amdgcn_alignbit(l0, vh0, 1);
+        o[4 * k + 2] = __builtin_amdgcn_alignbit(vh1, l1, 1);
+        o[4 * k + 3] = __builtin_amdgcn_alignbit(l1, vh1, 1);
+      }
+    }
+  }
+
+  // the accumulator words [i0, i0 + 8) (16 B loads; i0 a multiple of 8)
+  static __device__ __forceinline__ void loadAcc(uint32_t (&d)[kD], gp<const uint8_t> accB, uint32_t i0) {
+    gp<const u32x4> p = (gp<const u32x4>)(accB + uint64_t(sizeof(AccT)) * i0);
+#pragma unroll
+    for (int j = 0; j < kD / 4; ++j) {
+      const u32x4 v = p[j];
+      d[4 * j] = v.x; d[4 * j + 1] = v.y; d[4 * j + 2] = v.z; d[4 * j + 3] = v.w;
+    }
+  }
+
+  // vector accumulate of a full chunk: acc[i0 .. i0 + 8) += the joined words.
+  // d: those accumulator words (loadAcc, a segment earlier; fp64 loads them
+  // here).  Plain stores: the next peer's call reads the accumulator again.
+  static __device__ __forceinline__ void vecAcc(gp<uint8_t> accB, uint32_t i0, const uint32_t (&s)[4],
+                                                const uint32_t (&s1)[4], const uint32_t (&r)[kR],
+                                                const uint32_t (&d)[kD]) {
+    gp<u32x4> p = (gp<u32x4>)(accB + uint64_t(sizeof(AccT)) * i0);
+    uint32_t o[kW], t[kD];
+    if constexpr (FT == 4) {
+      loadAcc(t, accB, i0);
+      words(o, s, s1, r);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint64_t sum = sumOne(uint64_t(t[2 * k]) | (uint64_t(t[2 * k + 1]) << 32),
+                                    uint64_t(o[2 * k]) | (uint64_t(o[2 * k + 1]) << 32));
+        t[2 * k] = uint32_t(sum);
+        t[2 * k + 1] = uint32_t(sum >> 32);
+      }
+    } else {
+      words(o, s, s1, r);
+      if constexpr (ACC == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          t[2 * k] = f32Sum(d[2 * k], widen(o[k]));
+          t[2 * k + 1] = f32Sum(d[2 * k + 1], widen(o[k] >> 16));
+        }
+      } else if constexpr (FT == 3) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = f32Sum(d[k], __builtin_bit_cast(float, o[k]));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = sumPk16(d[k], o[k]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kD / 4; ++j) p[j] = u32x4{t[4 * j], t[4 * j + 1], t[4 * j + 2], t[4 * j + 3]};
+  }
 };
 
 // 64-bit decode table of one archive: entry[slot] = {pdf | sym << 24,
@@ -374,7 +517,17 @@ __device__ __forceinline__ void buildLut64(gp<const uint16_t> pdfIn, lp<u32x2> l
 // it are never reached).  Chunks of 8 words wholly inside the range whose
 // destination is 16 B-aligned take the vector join, every other chunk the
 // masked scalar one: nothing outside out[0 .. count) is written.
-template <int FT, bool NT, bool BAL, bool RNG = false>
+// ACC: accumulate forms: the joined words are added to the
+// destination (1: in the archive's word type, 2: an fp32 destination of an
+// fp16 / bf16 archive) instead of stored; out.size(b) counts accumulator
+// words.  Status and sizes as the full decode; a failing member's accumulator
+// is neither read nor written, nor is anything outside acc[0 .. n).  A chunk
+// that takes the vector join takes the vector accumulate: its destination
+// words are loaded with 16 B loads where its raw bytes are (a segment ahead,
+// double-buffered; fp64, register-bound, loads them at the join) and written
+// back with plain 16 B stores, the next peer's call reads them again.  Every
+// other chunk reads, adds and writes word by word.
+template <int FT, bool NT, bool BAL, bool RNG = false, int ACC = 0>
 __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(4))) void k_decode(const InlineTable,
                                                           BatchDesc in, BatchDesc out,
                                                           uint32_t batchOffset, int pb,
@@ -383,7 +536,12 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
                                                           uint32_t* __restrict__ outSize) {
   using Cfg = DecCfg<FT>;
   using WordT = typename FloatTraits<FT>::WordT;
-  constexpr int S = Cfg::S, R = Join<FT>::kR;
+  using J = Join<FT, ACC>;
+  using AccT = typename J::AccT;
+  constexpr int S = Cfg::S, R = J::kR, D = J::kD;
+  static_assert(!(ACC && (RNG || NT || BAL)), "accumulate: whole elements, plain stores, no priorities");
+  // destination words prefetched with the raw bytes
+  constexpr bool kAccAhead = ACC != 0 && FT != 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   lp<uint8_t> L = (lp<uint8_t>)smem;
   const uint32_t lutBytes = Cfg::lutBytes(pb);
@@ -478,6 +636,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   uint32_t x0[S];
   uint2 bwE[S][2];
   uint32_t rvA[R], rvB[R];
+  uint32_t dvA[D], dvB[D];
   auto issue = [&](uint32_t blk0) __attribute__((always_inline)) {
     const uint32_t off = dec::kChunk * l;
     const uint32_t bkMine = blk0 + (lane >> 5);
@@ -485,7 +644,10 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
     // loadable unmasked) when both blocks of the pair are whole
     const uint32_t uwMin = min(blockSymbols(blk0 + 1, blkEnd, n), blockSymbols(blk0, blkEnd, n));
     const uint32_t iTop = bkMine * kBlockSize + (kBlockSize / 32 / dec::kSegSteps - 1) * dec::kSegWords + off;
-    if (FT != 0 && vecIO && uwMin == kBlockSize && wholeInRange(iTop)) Join<FT>::load(rvA, raw, n, iTop);
+    if (FT != 0 && vecIO && uwMin == kBlockSize && wholeInRange(iTop)) {
+      J::load(rvA, raw, n, iTop);
+      if constexpr (kAccAhead) J::loadAcc(dvA, outB, iTop);
+    }
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       const AnsSections arc(arch[s], nBlocks);
@@ -592,15 +754,17 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
       constexpr bool kVec = decltype(vecTag)::value;
       // raw float bytes, double-buffered: a full segment's bytes are loaded
       // before the previous segment's steps, a whole segment ahead of use
-      auto loadRaw = [&](int32_t g, bool fullSeg, uint32_t (&rv)[R]) {
+      auto loadRaw = [&](int32_t g, bool fullSeg, uint32_t (&rv)[R], uint32_t (&dv)[D]) {
         const uint32_t segW0 = uint32_t(g) * dec::kSegWords;
         const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
         const uint32_t bk = blk0 + (lane >> 5);
         if (FT != 0 && kVec && (fullSeg || segW0 + off + dec::kChunk <= uw) &&
-            wholeInRange(bk * kBlockSize + segW0 + off))
-          Join<FT>::load(rv, raw, n, bk * kBlockSize + segW0 + off);
+            wholeInRange(bk * kBlockSize + segW0 + off)) {
+          J::load(rv, raw, n, bk * kBlockSize + segW0 + off);
+          if constexpr (kAccAhead) J::loadAcc(dv, outB, bk * kBlockSize + segW0 + off);
+        }
       };
-      auto join = [&](int32_t g, bool fullSeg, const uint32_t (&rv)[R]) {
+      auto join = [&](int32_t g, bool fullSeg, const uint32_t (&rv)[R], const uint32_t (&dv)[D]) {
         const uint32_t segW0 = uint32_t(g) * dec::kSegWords;
         const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
         const uint32_t bk = blk0 + (lane >> 5);
@@ -627,15 +791,19 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 #pragma unroll
             for (int k = 0; k < 4; ++k) sv1[k] = 0;
           }
-          Join<FT>::template vec<NT>(outB, i0, sv, sv1, rv);
+          if constexpr (ACC) J::vecAcc(outB, i0, sv, sv1, rv, dv);
+          else J::template vec<NT>(outB, i0, sv, sv1, rv);
+        } else if constexpr (ACC) {
+          gp<AccT> a = (gp<AccT>)outB + uint64_t(i0);
+          for (uint32_t k = k0; k < k1; ++k) a[k] = J::sumOne(a[k], J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k));
         } else {
           gp<WordT> o = (gp<WordT>)outB;
           for (uint32_t k = k0; k < k1; ++k)
-            o[i0 + k] = Join<FT>::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
+            o[i0 + k] = J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
         }
       };
 
-      if (nSeg > 0 && !(kVec && rawEarly)) loadRaw(nSeg - 1, uint32_t(nSeg - 1) < nFull, rvA);
+      if (nSeg > 0 && !(kVec && rawEarly)) loadRaw(nSeg - 1, uint32_t(nSeg - 1) < nFull, rvA, dvA);
       // partial segments (a pair with an element's tail block, or with no
       // second block at all): masked steps, unrolled like the full segments
       // (constant LDS offsets, the ring checked every kUnroll steps); steps
@@ -664,15 +832,16 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
           }
         }
         __builtin_amdgcn_wave_barrier();
-        join(g, false, rvA);
+        join(g, false, rvA, dvA);
         __builtin_amdgcn_wave_barrier();
-        if (g > gMin) loadRaw(g - 1, uint32_t(g - 1) < nFull, rvA);
+        if (g > gMin) loadRaw(g - 1, uint32_t(g - 1) < nFull, rvA, dvA);
       }
       // full segments: unrolled, unmasked
-      auto fullSeg = [&](int32_t g, const uint32_t (&cur)[R], uint32_t (&nxt)[R]) {
+      auto fullSeg = [&](int32_t g, const uint32_t (&cur)[R], uint32_t (&nxt)[R], const uint32_t (&dcur)[D],
+                         uint32_t (&dnxt)[D]) {
         if constexpr (BAL)
           setPrioRemaining((chunksPerWG - 1 - pass) * uint32_t(nSeg) + uint32_t(g), chunksPerWG * uint32_t(nSeg));
-        if (g > 0) loadRaw(g - 1, true, nxt);
+        if (g > 0) loadRaw(g - 1, true, nxt, dnxt);
 #pragma unroll
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
 #pragma unroll
@@ -687,15 +856,15 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
           }
         }
         __builtin_amdgcn_wave_barrier();
-        join(g, true, cur);
+        join(g, true, cur, dcur);
         __builtin_amdgcn_wave_barrier();
       };
       int32_t g = min(nSeg, int32_t(nFull)) - 1;  // rvA holds segment g's bytes
       for (; g >= 1; g -= 2) {
-        fullSeg(g, rvA, rvB);
-        fullSeg(g - 1, rvB, rvA);
+        fullSeg(g, rvA, rvB, dvA, dvB);
+        fullSeg(g - 1, rvB, rvA, dvB, dvA);
       }
-      if (g == 0) fullSeg(0, rvA, rvB);
+      if (g == 0) fullSeg(0, rvA, rvB, dvA, dvB);
     };
     if (vecIn && vecOut)
       run(std::true_type{});

@@ -13,7 +13,9 @@
 // (outSize 0, see dietgpu_device_error_count in include/dietgpu_c.h) raises
 // instead of being returned as an empty tensor.  An eleventh operator,
 // decompress_data_range, is not in the reference at all: it decodes a word
-// range of each archive (floatDecompressRange / ansDecodeBatchRange).
+// range of each archive (floatDecompressRange / ansDecodeBatchRange).  Nor is
+// the twelfth, decompress_data_accumulate: it adds each archive's element to
+// an accumulator tensor in place (floatDecompressAccumulate).
 //
 // Argument checks the reference lacks (its DietGpu.cpp says "FIXME: total
 // range checking" where they belong); each raises before any temp-memory
@@ -501,6 +503,63 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
   return int64_t(res.getMaxMemoryUsage());
 }
 
+// Extension (no reference counterpart): ts_acc[i] += the element that dense
+// float archive ts_in[i] encodes, in place, in one kernel
+// (floatDecompressAccumulate).  The accumulators share one dtype, which
+// selects the mode: float16 / bfloat16 / float64 accumulators take archives
+// of their own type; float32 accumulators take fp32 archives or, with the
+// sum kept in fp32, fp16 / bf16 ones -- which of the three is read from
+// ts_in[0]'s header (one k_info launch and a 4-byte copy to the host), so a
+// float32 call synchronises the stream once.  A member whose archive has
+// another type fails with status 0, as in decompress_data.  No checksum flag:
+// none can be verified, and archives written with one are accepted.
+int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsAcc,
+                                   const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
+                                   const std::optional<at::Tensor>& sizes) {
+  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsAcc.size(), "ts_in and ts_acc must have the same, nonzero length");
+  for (const auto& ta : tsAcc) {
+    checkOutDtype(ta);
+    TORCH_CHECK(ta.scalar_type() == tsAcc.front().scalar_type(), "the accumulators (ts_acc) must share a dtype");
+  }
+  const int dev = tsIn.front().get_device();
+  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  c10::hip::HIPGuard guard(dev);
+  std::vector<const void*> in(tsIn.size());
+  std::vector<void*> acc(tsIn.size());
+  std::vector<uint32_t> cap(tsIn.size());
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    const auto& ti = tsIn[i];
+    const auto& ta = tsAcc[i];
+    checkArchiveTensor(ti, dev);
+    TORCH_CHECK(ta.device().type() == at::kCUDA && ta.get_device() == dev && ta.is_contiguous(),
+                "ts_acc must be contiguous GPU tensors on the input device");
+    TORCH_CHECK(uint64_t(ta.numel()) <= kU32Max);
+    in[i] = ti.data_ptr();
+    acc[i] = ta.data_ptr();
+    cap[i] = uint32_t(ta.numel());
+  }
+  checkStatusTensors(status, sizes, int64_t(tsIn.size()), dev);
+  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
+  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
+  auto res = makeStack(dev, tempMem);
+  const hipStream_t s = currentStream(dev);
+  const FloatType accType = floatTypeOf(tsAcc.front().scalar_type());
+  FloatType ft = accType;
+  if (accType == FloatType::kFloat32) {
+    at::Tensor type = at::zeros({1}, tsIn.front().options().dtype(at::kInt));
+    floatGetCompressedInfo(res, in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
+                           s);
+    const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
+    TORCH_CHECK(t0 != 4, "float32 accumulators take float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
+    // (anything that is no float archive is decoded as fp32 and fails on the
+    // device with status 0, like any other invalid member)
+    if (t0 == 1 || t0 == 2) ft = FloatType(t0);
+  }
+  const FloatDecompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, false);
+  floatDecompressAccumulate(res, cfg, uint32_t(tsIn.size()), in.data(), acc.data(), cap.data(), accType, st, sz, s);
+  return int64_t(res.getMaxMemoryUsage());
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -622,6 +681,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "decompress_data_range(bool compress_as_float, Tensor[] ts_in, Tensor[] ts_out, Tensor t_first, Tensor? "
       "temp_mem=None, Tensor? out_status=None, Tensor? out_decompressed_words=None) -> int");
+  m.def(
+      "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, Tensor? temp_mem=None, Tensor? out_status=None, "
+      "Tensor? out_sizes=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -636,4 +698,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("decompress_data_split_size", &dietgpu::decompress_data_split_size);
   m.impl("decompress_data_simple", &dietgpu::decompress_data_simple);
   m.impl("decompress_data_range", &dietgpu::decompress_data_range);
+  m.impl("decompress_data_accumulate", &dietgpu::decompress_data_accumulate);
 }

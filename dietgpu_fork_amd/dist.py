@@ -61,6 +61,17 @@ class GpuFloatCodec:
         if not bool((status != 0).all()):
             raise RuntimeError("compressed collective: an archive failed to decode")
 
+    def accumulate(self, archives, accs):
+        """accs[i] += the element archives[i] encodes, in place (k_decode's
+        accumulate form; the accumulators' dtype is the archives' own or, for
+        fp16 / bf16 archives, float32)."""
+        from . import ops
+
+        status = torch.empty(len(archives), dtype=torch.uint8, device=accs[0].device)
+        ops.decompress_data_accumulate(archives, accs, out_status=status)
+        if not bool((status != 0).all()):
+            raise RuntimeError("compressed collective: an archive failed to decode")
+
 
 def _check_sizes(sizes, what):
     """Archive sizes seen by every rank: 0 marks an element whose compression
@@ -179,3 +190,131 @@ def all_to_all_compressed(tensors, group=None, codec=None):
     outs = [torch.empty(int(rmeta[r, 0]), dtype=dtype, device=dev) for r in range(world)]
     codec.decompress(archives, outs)
     return outs
+
+
+_FLOAT_DTYPES = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
+
+
+def _archive_info(archive):
+    """(numel, dtype) of a dense float archive, from its header (32 bytes read
+    on the host)."""
+    h = archive[:32].cpu().numpy().view("<u4")
+    if h.size < 3 or int(h[0]) != 0xf00f0001 or int(h[2]) & 0xf not in _FLOAT_DTYPES:
+        raise RuntimeError("reduce_archives: not a dense float archive")
+    return int(h[1]), _FLOAT_DTYPES[int(h[2]) & 0xf]
+
+
+def _acc_dtype(dtype, acc_dtype):
+    if acc_dtype is None:
+        return torch.float32 if dtype in (torch.float16, torch.bfloat16) else dtype
+    if acc_dtype != dtype and not (acc_dtype == torch.float32 and dtype in (torch.float16, torch.bfloat16)):
+        raise ValueError(f"acc_dtype {acc_dtype} does not go with {dtype}: the tensors' dtype, or float32 for "
+                         "float16 / bfloat16")
+    return acc_dtype
+
+
+def reduce_archives(own, archives, codec, acc_dtype=None):
+    """The local part of a compressed reduction: `own` (this rank's flat,
+    uncompressed contribution) plus the elements of `archives` (the peers'
+    archives, ascending rank order), added one after the other in that order,
+
+        round_dtype((...((own + x_1) + x_2) + ...)),
+
+    every add correctly rounded in acc_dtype (default: float32 for float16 /
+    bfloat16 tensors, else the tensors' dtype) and the result rounded once to
+    the tensors' dtype.  One codec.accumulate call per peer; no decoded
+    temporary.  The accumulator starts as `own` converted to acc_dtype, not as
+    +0.0: with no archives the result is `own` bit for bit (-0.0 included).
+    own=None: the first archive's element takes the place of `own`."""
+    if own is None:
+        if not archives:
+            raise ValueError("reduce_archives: nothing to reduce")
+        n, dtype = _archive_info(archives[0])
+        own = torch.empty(n, dtype=dtype, device=archives[0].device)
+        codec.decompress([archives[0]], [own])
+        archives = archives[1:]
+    dtype = own.dtype
+    acc = own.contiguous().view(-1).to(_acc_dtype(dtype, acc_dtype), copy=True)
+    for a in archives:
+        codec.accumulate([a], [acc])
+    return acc.to(dtype)
+
+
+def reduce_scatter_compressed(tensors, group=None, codec=None, acc_dtype=None):
+    """Reduce-scatter (sum) of float tensors with compressed traffic:
+    tensors[j] is this rank's contribution to rank j's result; every rank's
+    tensors[j] has the same numel and dtype.  Returns this rank's flat reduced
+    tensor: element i is
+
+        round_dtype((...((x_j + x_r1) + x_r2) + ...)),
+
+    x_j this rank's own tensors[j] (never compressed), r1 < r2 < ... the
+    other ranks ascending, every add done in acc_dtype (reduce_archives).  The
+    order is fixed, so the result is deterministic and reproducible; it is not
+    the order of RCCL's ring, so it is not bit-equal to dist.reduce_scatter.
+
+    The W - 1 outgoing tensors are compressed in one batch; one all-gather
+    exchanges the whole (source, destination) table of (numel, archive size),
+    so an abandoned archive or a numel mismatch raises on every rank before
+    the payload moves; one all_to_all_single moves the packed archives."""
+    codec = codec or GpuFloatCodec()
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    if len(tensors) != world:
+        raise ValueError("reduce_scatter_compressed: one tensor per destination rank")
+    dtype, dev = tensors[0].dtype, tensors[0].device
+    _acc_dtype(dtype, acc_dtype)
+    flat = [t.contiguous().view(-1) for t in tensors]
+    numels = torch.tensor([t.numel() for t in flat], dtype=torch.int64)
+    # the tensors that travel: every destination but this rank, empties aside
+    going = [j for j in range(world) if j != rank and flat[j].numel() > 0]
+    sizes = torch.zeros(world, dtype=torch.int64)
+    comp = torch.zeros([0, 16], dtype=torch.uint8, device=dev)
+    if going:
+        comp, csz = codec.compress([flat[j] for j in going])
+        sizes[going] = csz.to("cpu", torch.int64)
+    meta = torch.stack([numels, sizes], dim=1).to(dev)  # row j goes to rank j
+    allmeta = torch.empty([world * world, 2], dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(allmeta, meta, group=group)
+    allmeta = allmeta.view(world, world, 2).cpu()  # [source, destination]
+    for j in range(world):
+        col = allmeta[:, j, 0]
+        if not bool((col == col[0]).all()):
+            raise RuntimeError(f"reduce_scatter_compressed: the ranks' tensors[{j}] differ in numel: {col.tolist()}")
+    travels = (~torch.eye(world, dtype=torch.bool)) & (allmeta[:, :, 0] > 0)
+    _check_sizes(allmeta[:, :, 1][travels], "reduce_scatter_compressed")
+    asizes = torch.where(travels, allmeta[:, :, 1], torch.zeros_like(allmeta[:, :, 1]))
+    lens = (asizes[rank] + 15) // 16 * 16  # what this rank sends to each destination
+    rlens = (asizes[:, rank] + 15) // 16 * 16  # ... and receives from each source
+    recv = torch.empty(max(int(rlens.sum()), 16), dtype=torch.uint8, device=dev)
+    if int(asizes.sum()) > 0:  # (the same on every rank)
+        glens = lens[going]
+        send = _pack(comp, asizes[rank][going], torch.cumsum(glens, 0) - glens, int(glens.sum()), dev)
+        dist.all_to_all_single(recv[: int(rlens.sum())], send[: int(lens.sum())],
+                               output_split_sizes=rlens.tolist(), input_split_sizes=lens.tolist(), group=group)
+    roffs = torch.cumsum(rlens, 0) - rlens
+    archives = [recv[int(roffs[r]):int(roffs[r]) + int(asizes[r, rank])] for r in range(world) if travels[r, rank]]
+    return reduce_archives(flat[rank], archives, codec, acc_dtype)
+
+
+def all_reduce_compressed(tensor, group=None, codec=None, acc_dtype=None):
+    """All-reduce (sum) of a float tensor with compressed traffic: a
+    reduce_scatter_compressed of the contiguous shards shard_range(numel, r, W)
+    of the flattened tensor, then an all_gather_compressed of the reduced
+    shards.  Element i of rank j's shard is summed in the order documented
+    there (rank j's own value first, the other ranks ascending, in acc_dtype,
+    rounded once), and the lossless all-gather hands every rank the same
+    bits.  Shards may be empty (numel < W).  Returns a tensor of the input's
+    shape."""
+    codec = codec or GpuFloatCodec()
+    world = dist.get_world_size(group)
+    flat = tensor.contiguous().view(-1)
+    if flat.numel() == 0:
+        return tensor.clone()
+    ranges = [shard_range(flat.numel(), r, world) for r in range(world)]
+    mine = reduce_scatter_compressed([flat[a:b] for a, b in ranges], group=group, codec=codec, acc_dtype=acc_dtype)
+    # (a rank whose shard is empty sends one word that nobody keeps: every
+    # rank knows the shard sizes)
+    send = mine if mine.numel() else torch.zeros(1, dtype=flat.dtype, device=flat.device)
+    got = all_gather_compressed([send], group=group, codec=codec)
+    return torch.cat([g[: b - a] for g, (a, b) in zip(got, ranges)]).view(tensor.shape)

@@ -6,7 +6,9 @@ with ``torch.ops.load_library`` exactly as the reference's harnesses load its
 ``DietGpu.cpp`` extension (dietgpu/DietGpu.cpp:921-978: its ten operators
 with the same schemas, validation and return values).  An eleventh,
 ``decompress_data_range``, is an extension the reference does not have: it
-decodes a word range of each archive.  This module only loads that library
+decodes a word range of each archive.  A twelfth,
+``decompress_data_accumulate``, adds each archive's element to an accumulator
+tensor in place.  This module only loads that library
 and forwards ``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.
 """
 import os
@@ -30,6 +32,7 @@ OPS = (
     "decompress_data_simple",
     # extension (not in the reference)
     "decompress_data_range",
+    "decompress_data_accumulate",
 )
 
 _LOADED = False

@@ -163,4 +163,29 @@ void floatDecompressSparseRange(StackDeviceMemory& res,
                                 void** out, uint8_t* outSuccess_dev,
                                 uint32_t* outSize_dev, hipStream_t stream);
 
+// Decode-and-accumulate: acc[b][i] = acc[b][i] + x[i], 0 <= i < n, where x is
+// the element (n words) that dense float archive in[b] encodes: one kernel,
+// no temporary.  accType is the accumulators' type: config.floatType (the
+// sum is formed in the archive's own type), or kFloat32 when config.floatType
+// is kFloat16 / kBFloat16 (acc + float(x), x widened exactly); anything else
+// throws.  Every sum is the correctly rounded IEEE sum in the accumulator's
+// type (nearest even, denormals kept, x + (-x) = +0, overflow to +-inf); a
+// NaN result is some NaN.  in[b] 4-byte aligned; acc[b] aligned to the
+// accumulator's word, accCapacity[b] in accumulator words.  Status as
+// floatDecompress: outSuccess_dev[b] = 1 iff the archive is valid for this
+// config and accCapacity[b] >= n; outSize_dev[b] = n for a valid archive,
+// else 0.  A failing member's accumulator is neither read nor written, and
+// nothing outside acc[b][0 .. n) ever is.  Two members whose accumulators
+// overlap are the caller's error: the result is undefined and not checked
+// for.  config.useChecksum must be false: the decoder verifies a checksum on
+// the decoded words, which an accumulated destination no longer holds
+// (archives written with a checksum decode normally).  No host
+// synchronisation, no allocation outside `res`.
+void floatDecompressAccumulate(StackDeviceMemory& res,
+                               const FloatDecompressConfig& config,
+                               uint32_t numInBatch, const void** in, void** acc,
+                               const uint32_t* accCapacity, FloatType accType,
+                               uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+                               hipStream_t stream);
+
 } // namespace dietgpu

@@ -192,8 +192,21 @@ int dietgpu_float_decompress_sparse_range(dietgpu_stack* res, int float_type, in
                                           uint8_t* out_success_dev, uint32_t* out_size_dev,
                                           void* stream);
 
+/* Decode-and-accumulate: acc[b][i] += word i of the element dense float
+ * archive in[b] encodes (floatDecompressAccumulate, GpuFloatCodec.h).
+ * dietgpu_float_decompress's arguments without the checksum flag, plus
+ * acc_type, the accumulators' float type: float_type itself, or 3 (fp32)
+ * when float_type is 1 or 2 (fp16 / bf16).  acc_capacity counts accumulator
+ * words.  Accumulators of two members must not overlap (not checked).
+ * Archives written with a checksum are accepted; none is verified. */
+int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int float_type, int prob_bits,
+                                        uint32_t num_in_batch, const void** in, void** acc,
+                                        const uint32_t* acc_capacity, int acc_type,
+                                        uint8_t* out_success_dev, uint32_t* out_size_dev,
+                                        void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
- * named kernel family ("encode", "decode", "decode_range", "hist", "coalesce") is bracketed
+ * named kernel family ("encode", "decode", "decode_range", "decode_accumulate", "hist", "coalesce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);
