@@ -119,6 +119,35 @@ def compress_path(mode):
         set_compress_path("auto")
 
 
+def _pointer_compress(fn, head, ts, row_width, ws, mid=()):
+    """The pointer-form compress call fn(ws, *head, nb, ins, sizes, *mid, outs,
+    out sizes, stream): ts[i] -> row i of a [nb, row_width(largest numel)]
+    matrix -> (out, sizes)."""
+    nb = len(ts)
+    dev = ts[0].device
+    cols = row_width(max(t.numel() for t in ts))
+    out = torch.empty([nb, cols], dtype=torch.uint8, device=dev)
+    sizes = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    N.check(fn(ws.h, *head, nb, N.ptr_array([t.data_ptr() for t in ts]), N.u32_array([t.numel() for t in ts]), *mid,
+               N.ptr_array([out.data_ptr() + i * cols for i in range(nb)]), sizes.data_ptr(), _s()))
+    return out, sizes
+
+
+def _pointer_decode(fn, head, archives, outs, ws, tail=()):
+    """The pointer-form decode call fn(ws, *head, nb, archives, outs,
+    capacities, *tail, ok, sz, stream): archives[i] -> outs[i] -> (ok, sz)."""
+    nb = len(archives)
+    dev = archives[0].device
+    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
+    sz = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    N.check(fn(ws.h, *head, nb, N.ptr_array([a.data_ptr() for a in archives]),
+               N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]), *tail,
+               ok.data_ptr(), sz.data_ptr(), _s()))
+    return ok, sz
+
+
 # ------------------------------------------------------------------ ANS ----
 
 def ans_encode_stride(data2d, prob_bits=10, checksum=False, ws=None, histogram=None,
@@ -157,32 +186,12 @@ def ans_decode_stride(archives2d, n, prob_bits=10, checksum=False, ws=None, out=
 
 def ans_encode_pointer(ts, prob_bits=10, checksum=False, ws=None):
     """ts: list of uint8 CUDA tensors -> (list of archive rows, sizes)"""
-    nb = len(ts)
-    dev = ts[0].device
-    cols = max_compressed_size(max(t.numel() for t in ts))
-    out = torch.empty([nb, cols], dtype=torch.uint8, device=dev)
-    sizes = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_ans_encode_batch_pointer(
-        ws.h, prob_bits, int(checksum), nb, N.ptr_array([t.data_ptr() for t in ts]),
-        N.u32_array([t.numel() for t in ts]), None,
-        N.ptr_array([out.data_ptr() + i * cols for i in range(nb)]), sizes.data_ptr(), _s())
-    N.check(rc)
-    return out, sizes
+    return _pointer_compress(N.lib().dietgpu_ans_encode_batch_pointer, (prob_bits, int(checksum)), ts,
+                             max_compressed_size, ws, mid=(None,))  # no histograms
 
 
 def ans_decode_pointer(archives, outs, prob_bits=10, checksum=False, ws=None):
-    nb = len(archives)
-    dev = archives[0].device
-    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
-    sz = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_ans_decode_batch_pointer(
-        ws.h, prob_bits, int(checksum), nb, N.ptr_array([a.data_ptr() for a in archives]),
-        N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]),
-        ok.data_ptr(), sz.data_ptr(), _s())
-    N.check(rc)
-    return ok, sz
+    return _pointer_decode(N.lib().dietgpu_ans_decode_batch_pointer, (prob_bits, int(checksum)), archives, outs, ws)
 
 
 # ---------------------------------------------------------------- float ----
@@ -227,33 +236,13 @@ def float_decompress_stride(archives2d, n, dtype, prob_bits=10, checksum=False, 
 
 def float_compress_pointer(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
-    nb = len(ts)
-    dev = ts[0].device
-    cols = max_float_compressed_size(ft, max(t.numel() for t in ts))
-    out = torch.empty([nb, cols], dtype=torch.uint8, device=dev)
-    sizes = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_float_compress(
-        ws.h, ft, prob_bits, int(checksum), nb, N.ptr_array([t.data_ptr() for t in ts]),
-        N.u32_array([t.numel() for t in ts]),
-        N.ptr_array([out.data_ptr() + i * cols for i in range(nb)]), sizes.data_ptr(), _s())
-    N.check(rc)
-    return out, sizes
+    return _pointer_compress(N.lib().dietgpu_float_compress, (ft, prob_bits, int(checksum)), ts,
+                             lambda n: max_float_compressed_size(ft, n), ws)
 
 
 def float_decompress_pointer(archives, outs, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[outs[0].dtype]
-    nb = len(archives)
-    dev = archives[0].device
-    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
-    sz = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_float_decompress(
-        ws.h, ft, prob_bits, int(checksum), nb, N.ptr_array([a.data_ptr() for a in archives]),
-        N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]),
-        ok.data_ptr(), sz.data_ptr(), _s())
-    N.check(rc)
-    return ok, sz
+    return _pointer_decode(N.lib().dietgpu_float_decompress, (ft, prob_bits, int(checksum)), archives, outs, ws)
 
 
 def float_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None):
@@ -279,16 +268,8 @@ def float_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None):
     ft = ft or acc_ft
     if not (acc_ft == ft or (ft in (1, 2) and acc_ft == 3)):
         raise ValueError(f"float_decompress_accumulate: accumulator type {acc_ft} does not go with float type {ft}")
-    dev = archives[0].device
-    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
-    sz = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_float_decompress_accumulate(
-        ws.h, ft, prob_bits, nb, N.ptr_array([a.data_ptr() for a in archives]),
-        N.ptr_array([a.data_ptr() for a in accs]), N.u32_array([a.numel() for a in accs]), acc_ft,
-        ok.data_ptr(), sz.data_ptr(), _s())
-    N.check(rc)
-    return ok, sz
+    return _pointer_decode(N.lib().dietgpu_float_decompress_accumulate, (ft, prob_bits), archives, accs, ws,
+                           tail=(acc_ft,))
 
 
 # ---------------------------------------------------------------- range ----
@@ -397,33 +378,14 @@ def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None
 
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
-    nb = len(ts)
-    dev = ts[0].device
-    cols = max_sparse_float_compressed_size(ft, max(t.numel() for t in ts))
-    out = torch.empty([nb, cols], dtype=torch.uint8, device=dev)
-    sizes = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_float_compress_sparse(
-        ws.h, ft, prob_bits, int(checksum), nb, N.ptr_array([t.data_ptr() for t in ts]),
-        N.u32_array([t.numel() for t in ts]),
-        N.ptr_array([out.data_ptr() + i * cols for i in range(nb)]), sizes.data_ptr(), _s())
-    N.check(rc)
-    return out, sizes
+    return _pointer_compress(N.lib().dietgpu_float_compress_sparse, (ft, prob_bits, int(checksum)), ts,
+                             lambda n: max_sparse_float_compressed_size(ft, n), ws)
 
 
 def sparse_decompress(archives, outs, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[outs[0].dtype]
-    nb = len(archives)
-    dev = archives[0].device
-    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
-    sz = torch.empty([nb], dtype=torch.int32, device=dev)
-    ws = _ws(ws, dev)
-    rc = N.lib().dietgpu_float_decompress_sparse(
-        ws.h, ft, prob_bits, int(checksum), nb, N.ptr_array([a.data_ptr() for a in archives]),
-        N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]),
-        ok.data_ptr(), sz.data_ptr(), _s())
-    N.check(rc)
-    return ok, sz
+    return _pointer_decode(N.lib().dietgpu_float_decompress_sparse, (ft, prob_bits, int(checksum)), archives, outs,
+                           ws)
 
 
 def profile(on=True):

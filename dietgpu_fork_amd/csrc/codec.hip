@@ -425,105 +425,65 @@ void encodeBatchDevice(const CompressCall& c) {
   compressThreeKernel<FT>(c);
 }
 
+// One decode call in any form (DecodeCall, codec_internal.h): the form picks
+// the k_decode instance and the profile family, planDecode (decode_plan.h) the
+// grid of each slice.
 template <int FT>
 void decodeBatchDevice(const DecodeCall& c) {
   checkProbBits(c.pb);
   if (c.nb == 0) return;
-  const hipStream_t s = c.s;
-  const int pb = c.pb;
-  const uint32_t maxBlocks = divUp(c.maxCapacity, kBlockSize);
-  auto launch = [&](auto ntTag) {
-    constexpr bool NT = decltype(ntTag)::value;
-    using Cfg = DecCfg<FT>;
+  using Cfg = DecCfg<FT>;
+  const uint32_t lds = Cfg::ldsBytes(c.pb);
+  auto run = [&](const char* family, auto nt, auto rng, auto acc) {
+    constexpr bool NT = decltype(nt)::value, RNG = decltype(rng)::value;
+    constexpr int ACC = decltype(acc)::value;
+    constexpr bool kFull = !RNG && ACC == 0;  // the only form with a BAL instance
+    const uint32_t maxBlocks = RNG ? c.maxRangeBlocks : divUp(c.maxCapacity, kBlockSize);
+    // the resident workgroups of the instance launched (full: of its BAL
+    // instance); a range's grid does not depend on them
+    const uint32_t slots =
+        RNG ? 0
+            : residentSlots(reinterpret_cast<const void*>(&k_decode<FT, NT, kFull, RNG, ACC>), dec::kThreads, lds);
     forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
-      prof::Scope p("decode", s);
-      // about one generation of resident workgroups; each decodes P chunks
-      // (one table build per P chunks).  P is capped at kMaxDecodeChunks:
-      // large batches then run several generations, which measured faster
-      // than long persistent loops (c3: 3.02 ms at P = 64, 2.31 ms at P = 8,
-      // 2.60 ms at P = 1; c2's P = 2 is unaffected)
-      constexpr uint32_t kMaxDecodeChunks = 8;
-      const uint32_t lds = Cfg::ldsBytes(pb);
-      const uint32_t chunks = std::max(1u, divUp(maxBlocks, Cfg::kBlocksPerWG));
-      const uint32_t slots =
-          residentSlots(reinterpret_cast<const void*>(&k_decode<FT, NT, true>), dec::kThreads, lds);
-      // capacityOnly: the capacity is all the host knows and may far exceed
-      // the archives' sizes (the sparse codec's nonzero lists): one chunk per
-      // workgroup, so the chunks that exist run side by side instead of P
-      // passes of a workgroup while the grid's upper part exits at once
-      // (5 x 15M fp32 at 50 % zeros: the list decode 77 -> see DESIGN)
-      const uint32_t P = c.capacityOnly ? 1u
-                                      : std::min(kMaxDecodeChunks,
-                                                 std::max(1u, uint32_t((uint64_t(chunks) * ny + slots / 2) / slots)));
-      dim3 g(divUp(chunks, P), ny);
-      // remaining-work wave priorities balance the finish of a single
-      // generation (c2 decode −2 %); across several generations they cost
-      // (c3 decode 2.02 ms without, 2.32 ms with, same-box A/B).  A template
-      // parameter: a runtime flag changed the step loop's code (c2 +25 %)
-      if (uint64_t(g.x) * ny <= slots)
-        k_decode<FT, NT, true><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
-                                                             c.outSuccess_dev, c.outSize_dev);
-      else
-        k_decode<FT, NT, false><<<g, dec::kThreads, lds, s>>>(kernargTable(c.tabs), c.in, c.out, y0, pb, P,
-                                                              c.outSuccess_dev, c.outSize_dev);
-      HIP_LAUNCH_CHECK();
+      prof::Scope p(family, c.s);
+      const DecodePlan plan = planDecode(c.form, c.capacityOnly, maxBlocks, Cfg::kBlocksPerWG, ny, slots);
+      // BAL is a template parameter: a runtime flag changed the step loop's
+      // code (c2 +25 %)
+      auto launch = [&](auto bal) {
+        k_decode<FT, NT, decltype(bal)::value, RNG, ACC><<<dim3(plan.gridX, ny), dec::kThreads, lds, c.s>>>(
+            kernargTable(c.tabs), c.in, c.out, y0, c.pb, plan.chunksPerWG, c.outSuccess_dev, c.outSize_dev);
+        HIP_LAUNCH_CHECK();
+      };
+      if constexpr (kFull) {
+        if (plan.balance) return launch(std::true_type{});
+      }
+      launch(std::false_type{});
     });
   };
-  // streaming stores when nobody re-reads the output right away (fp64's
-  // 8-dword rows measured slower with them)
-  if constexpr (FT != 4) {
-    if (c.streamOut) return launch(std::true_type{});
+  constexpr std::true_type yes;
+  constexpr std::false_type no;
+  constexpr std::integral_constant<int, 0> store;
+  switch (c.form) {
+    case DecodeForm::kFull:
+      // streaming stores when nobody re-reads the output right away (fp64's
+      // 8-dword rows measured slower with them)
+      if constexpr (FT != 4) {
+        if (c.streamOut) return run("decode", yes, no, store);
+      }
+      return run("decode", no, no, store);
+    case DecodeForm::kRange:
+      // plain stores: a range is read right after it is fetched, and its edge
+      // rows are partial cache lines
+      return run("decode_range", no, yes, store);
+    case DecodeForm::kAccumulate:
+      // plain stores: the accumulator is read again by the next peer's call
+      if constexpr (FT != 0) return run("decode_accumulate", no, no, std::integral_constant<int, 1>{});
+      break;
+    case DecodeForm::kAccumulateFp32:
+      if constexpr (FT == 1 || FT == 2) return run("decode_accumulate", no, no, std::integral_constant<int, 2>{});
+      break;
   }
-  launch(std::false_type{});
-}
-
-// Range decode: words [first, first + count) of archive b
-// into c.out, where first = c.in.size(b) (the `first` table rides as the size
-// column of the input descriptor, which the full decode leaves empty) and
-// count = c.out.size(b).  maxRangeBlocks: the most 4096-word blocks any
-// member's range touches.  One chunk of 8 blocks per workgroup, as
-// capacityOnly: ranges are short, so the chunks run side by side; no
-// remaining-work priorities.  Plain (not streaming) stores: a range is read
-// right after it is fetched, and its edge rows are partial cache lines.
-template <int FT>
-void decodeRangeBatchDevice(const DecodeCall& c, uint32_t maxRangeBlocks) {
-  checkProbBits(c.pb);
-  if (c.nb == 0) return;
-  using Cfg = DecCfg<FT>;
-  const uint32_t lds = Cfg::ldsBytes(c.pb);
-  forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
-    prof::Scope p("decode_range", c.s);
-    dim3 g(std::max(1u, divUp(maxRangeBlocks, uint32_t(Cfg::kBlocksPerWG))), ny);
-    k_decode<FT, false, false, true><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
-                                                                   1u, c.outSuccess_dev, c.outSize_dev);
-    HIP_LAUNCH_CHECK();
-  });
-}
-
-// Decode-and-accumulate: acc[b][i] += word i of archive b,
-// c.out being the accumulators (capacities in accumulator words).  The full
-// decode's grid rule -- P chunks per workgroup from the resident-slot count of
-// the instance launched -- without remaining-work priorities, and plain
-// stores: the accumulator is read again by the next peer's call.
-template <int FT, int ACC>
-void decodeAccumulateBatchDevice(const DecodeCall& c) {
-  checkProbBits(c.pb);
-  if (c.nb == 0) return;
-  using Cfg = DecCfg<FT>;
-  constexpr uint32_t kMaxDecodeChunks = 8;  // as decodeBatchDevice
-  const uint32_t lds = Cfg::ldsBytes(c.pb);
-  const uint32_t chunks = std::max(1u, divUp(divUp(c.maxCapacity, kBlockSize), uint32_t(Cfg::kBlocksPerWG)));
-  const uint32_t slots = residentSlots(reinterpret_cast<const void*>(&k_decode<FT, false, false, false, ACC>),
-                                       dec::kThreads, lds);
-  forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
-    prof::Scope p("decode_accumulate", c.s);
-    const uint32_t P =
-        std::min(kMaxDecodeChunks, std::max(1u, uint32_t((uint64_t(chunks) * ny + slots / 2) / slots)));
-    dim3 g(divUp(chunks, P), ny);
-    k_decode<FT, false, false, false, ACC><<<g, dec::kThreads, lds, c.s>>>(kernargTable(c.tabs), c.in, c.out, y0, c.pb,
-                                                                          P, c.outSuccess_dev, c.outSize_dev);
-    HIP_LAUNCH_CHECK();
-  });
+  DG_CHECK(false, "decode form " << int(c.form) << " does not go with float type " << FT);
 }
 
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
@@ -560,6 +520,12 @@ static void checkOutAligned(const void* p, const char* what) {
            what << " must be 16-byte aligned (archives are written with 16 B stores)");
 }
 
+// Archive i of a range or accumulate call (the decoder reads the headers with
+// scalar loads, which drop the low two address bits; the full decoders do not
+// check this).
+static void checkArchiveAligned4(uint64_t address, uint32_t i) {
+  DG_CHECK(address % 4 == 0, "archive " << i << " must be 4-byte aligned");
+}
 
 // ---------------------------------------------------------------------------
 // batch tables of the pointer and split-size entry points.  `unit` is the
@@ -625,9 +591,7 @@ static BatchTables rangeBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb
   const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
   for (uint32_t i = 0; i < nb; ++i) {
     DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
-    // (the decoder reads the headers with scalar loads, which drop the low
-    // two address bits)
-    DG_CHECK(ip[i] % 4 == 0, "archive " << i << " must be 4-byte aligned");
+    checkArchiveAligned4(ip[i], i);
   }
   const SizeColumn cnt(count, nb), fst(first, nb);
   BatchTables b;
@@ -673,6 +637,16 @@ static DecodeCall decodeCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb,
   c.outSuccess_dev = outSuccess_dev;
   c.outSize_dev = outSize_dev;
   c.tabs = &b.t;
+  return c;
+}
+
+// ... of a rangeBatch, whose maxSize counts blocks
+static DecodeCall rangeCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
+                            uint8_t* outSuccess_dev, uint32_t* outSize_dev) {
+  DecodeCall c = decodeCall(res, s, nb, b, outSuccess_dev, outSize_dev);
+  c.form = DecodeForm::kRange;
+  c.maxCapacity = 0;
+  c.maxRangeBlocks = b.maxSize;
   return c;
 }
 
@@ -788,9 +762,9 @@ void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config, u
   DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
   if (numInBatch == 0) return;
   const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, 1);
-  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
+  DecodeCall c = rangeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
   c.pb = config.probBits;
-  decodeRangeBatchDevice<0>(c, b.maxSize);
+  decodeBatchDevice<0>(c);
 }
 
 // k_info over a device array of archive addresses (the byte codec has no
@@ -859,10 +833,11 @@ void floatCompressDescs(const FloatCompressConfig& config, CompressCall c) {
 FloatDecompressStatus floatDecompressDescs(const FloatDecompressConfig& config, DecodeCall c) {
   checkFloatConfig(config);
   c.pb = config.ansConfig.probBits;
+  const bool verify = c.form == DecodeForm::kFull && config.useChecksum;
   // streaming output stores unless the output is read back (checksum)
-  c.streamOut = c.streamOut && !config.useChecksum;
+  c.streamOut = c.streamOut && !verify;
   dispatchFloatType(config.floatType, [&](auto ft) { decodeBatchDevice<decltype(ft)::value>(c); });
-  return config.useChecksum ? verifiedStatus<FloatDecompressStatus>(c, true) : FloatDecompressStatus();
+  return verify ? verifiedStatus<FloatDecompressStatus>(c, true) : FloatDecompressStatus();
 }
 
 void floatCompress(StackDeviceMemory& res, const FloatCompressConfig& config, uint32_t numInBatch,
@@ -924,10 +899,7 @@ void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& c
   DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
   if (numInBatch == 0) return;
   const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, floatWordBytes(int(config.floatType)));
-  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
-  c.pb = config.ansConfig.probBits;
-  dispatchFloatType(config.floatType,
-                    [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, b.maxSize); });
+  floatDecompressDescs(config, rangeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
 }
 
 void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,
@@ -942,27 +914,11 @@ void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConf
            "accumulator type " << int(accType) << " does not go with float type " << int(config.floatType)
                                << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
   if (numInBatch == 0) return;
-  for (uint32_t i = 0; i < numInBatch; ++i)
-    // (the decoder reads the headers with scalar loads, which drop the low
-    // two address bits)
-    DG_CHECK(reinterpret_cast<uintptr_t>(in[i]) % 4 == 0, "archive " << i << " must be 4-byte aligned");
+  for (uint32_t i = 0; i < numInBatch; ++i) checkArchiveAligned4(reinterpret_cast<uintptr_t>(in[i]), i);
   const auto b = pointerBatch(res, stream, numInBatch, in, acc, accCapacity, false, floatWordBytes(int(accType)));
   DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
-  c.pb = config.ansConfig.probBits;
-  dispatchFloatType(config.floatType, [&](auto ft) {
-    constexpr int FT = decltype(ft)::value;
-    if constexpr (FT == 1 || FT == 2) {
-      if (wide) return decodeAccumulateBatchDevice<FT, 2>(c);
-    }
-    decodeAccumulateBatchDevice<FT, 1>(c);
-  });
-}
-
-void floatDecompressRangeDescs(const FloatDecompressConfig& config, DecodeCall c, uint32_t maxRangeBlocks) {
-  checkFloatConfig(config);
-  c.pb = config.ansConfig.probBits;
-  dispatchFloatType(config.floatType,
-                    [&](auto ft) { decodeRangeBatchDevice<decltype(ft)::value>(c, maxRangeBlocks); });
+  c.form = wide ? DecodeForm::kAccumulateFp32 : DecodeForm::kAccumulate;
+  floatDecompressDescs(config, c);
 }
 
 FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,

@@ -11,6 +11,7 @@
 
 #include "batch.h"
 #include "batch_tables.h"
+#include "decode_plan.h"
 #include "dietgpu/GpuFloatCodec.h"
 
 namespace dietgpu {
@@ -52,20 +53,31 @@ struct CompressCall {
   const uint32_t* sparseN = nullptr;
 };
 
-// One decode call: nb archives `in` into `out` (capacities: out.size(b), at
-// most maxCapacity units).
+// One decode call of the generic driver (codec.hip decodeBatchDevice): nb
+// archives `in` into `out`, in one of the forms of decode_plan.h.
+//  - full, accumulate: capacities out.size(b), at most maxCapacity units;
+//    an accumulate call's `out` are the accumulators, counted in their words.
+//  - range: words [in.size(b), + out.size(b)) of archive in.start(b) (the
+//    `first` column rides as the input descriptor's size column, which the
+//    other forms leave empty); both columns may be device arrays a previous
+//    kernel wrote.  maxRangeBlocks: the most 4096-word blocks a member's range
+//    touches.  maxCapacity is not read.
 struct DecodeCall {
   StackDeviceMemory& res;
   hipStream_t s;
+  DecodeForm form = DecodeForm::kFull;
   int pb = 0;
   uint32_t nb = 0;
   BatchDesc in, out;
   uint32_t maxCapacity = 0;
+  uint32_t maxRangeBlocks = 0;
   uint8_t* outSuccess_dev = nullptr;
   uint32_t* outSize_dev = nullptr;
   const DeviceTables* tabs = nullptr;
-  bool streamOut = true;      // streaming output stores (nobody re-reads it right away)
-  bool capacityOnly = false;  // maxCapacity may far exceed the archives' sizes
+  // full only: streaming output stores (nobody re-reads the output right away)
+  bool streamOut = true;
+  // full only: maxCapacity may far exceed the archives' sizes
+  bool capacityOnly = false;
 };
 
 // f(std::integral_constant<int, FT>{}) for the float type's FT (1 fp16,
@@ -111,16 +123,11 @@ void floatCompressDescs(const FloatCompressConfig& config, CompressCall c);
 template <int FT>
 bool persistentPreferred(uint32_t nb, uint32_t maxWords);
 
-// c.pb comes from the config; a checksummed call reads its output back, so
-// it never streams.
+// The dense float decode of a call in any form.  The float type and c.pb come
+// from the config, which is validated here.  A full call verifies the checksum
+// when the config asks for one (it then reads its output back, so it never
+// streams); the other forms cannot, and their callers refuse such a config.
 FloatDecompressStatus floatDecompressDescs(const FloatDecompressConfig& config, DecodeCall c);
-
-// The dense range decode on descriptors (codec.hip decodeRangeBatchDevice):
-// words [c.in.size(b), + c.out.size(b)) of float archive c.in.start(b) into
-// c.out, both size columns device arrays a previous kernel may have written.
-// maxRangeBlocks: the most 4096-word blocks a member's range touches.  The
-// float type and prob bits come from the (validated) config.
-void floatDecompressRangeDescs(const FloatDecompressConfig& config, DecodeCall c, uint32_t maxRangeBlocks);
 
 // Compare the checksums stored in the archives c.in with the XOR of the
 // first c.out.size(b) bytes of each decoded element; synchronises c.s.

@@ -112,37 +112,6 @@ __device__ __forceinline__ void ringEnsure(DStream& p, uint32_t lane, bool vec) 
   }
 }
 
-// One LIFO decode step (decodeOneWarp, ans/GpuANSDecode.cuh:55-105) of one
-// stream of a block pair.  hv: all-ones on lanes 32-63 (opaque to the
-// compiler).  Returns the table entry's low word (sym in bits 24-31).
-// kMask: lanes with !valid keep their state and do not read.
-template <bool kMask>
-__device__ __forceinline__ uint32_t decStep(DStream& p, bool valid, lp<const u32x2> lut,
-                                            uint32_t mask, int pb, uint32_t hv) {
-  const u32x2 e = lut[p.x & mask];
-  uint32_t xn = __umul24(e.x, p.x >> pb) + e.y;
-  if (kMask) xn = valid ? xn : p.x;
-  const bool rd = kMask ? (valid && xn < kMinState) : (xn < kMinState);
-  const uint64_t vote = ballot(rd);
-  const int32_t cLo = __popc(uint32_t(vote));
-  const int32_t cHi = __popc(uint32_t(vote >> 32));
-  // read index = ptr' + (#readers of my half below me); v_mbcnt over 64
-  // lanes already counts every low-half reader for lanes 32-63.
-  const int32_t baseLo = p.ptr[0] - cLo;
-  const int32_t diff = p.ptr[1] - p.ptr[0] - cHi;  // (ptr1 - cHi - cLo) - baseLo
-  p.ptr[0] = baseLo;
-  p.ptr[1] -= cHi;
-  const uint32_t vbase = uint32_t(baseLo) + (hv & uint32_t(diff));
-  const uint32_t idx = __builtin_amdgcn_mbcnt_hi(uint32_t(vote >> 32),
-                                                 __builtin_amdgcn_mbcnt_lo(uint32_t(vote), vbase));
-  const uint32_t v = p.ringLane[idx & (dec::kRing - 1)];  // harmless for non-readers
-  // x = rd ? (xn << 16 | v) : xn as one v_perm.  Feeding the word through an
-  // intrinsic (not a select) keeps the LDS read unconditional: a branch
-  // around it would split the step and serialise the independent chains.
-  p.x = __builtin_amdgcn_perm(xn, v, rd ? 0x05040100u : 0x07060504u);
-  return e.x;
-}
-
 // All chains of a wave, one step each, in three phases separated by
 // scheduling barriers: (A) every chain's table read, (B) every chain's state
 // update, ballot and ring read, (C) every chain's v_perm.  Without the

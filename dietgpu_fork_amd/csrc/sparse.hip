@@ -885,8 +885,9 @@ void sparseRangeT(const FloatDecompressConfig& config, const SparseRangeCall& c)
   dense.out = BatchDesc::strided(slices.data(), rowWords * sizeof(W), 0);
   dense.out.sizes = listCount.data();
   dense.outSuccess_dev = denseOk.data();
-  const uint32_t maxRangeBlocks = uint32_t((uint64_t(maxCount) + 1 + kBlockSize - 1) / kBlockSize) + 1;
-  floatDecompressRangeDescs(config, dense, maxRangeBlocks);
+  dense.form = DecodeForm::kRange;
+  dense.maxRangeBlocks = uint32_t((uint64_t(maxCount) + 1 + kBlockSize - 1) / kBlockSize) + 1;
+  floatDecompressDescs(config, dense);
   const BatchDesc outs = BatchDesc::pointers(t.u64[2], nullptr);
   const uint32_t chunkWaves = uint32_t((uint64_t(maxCount) + kChunkWords - 1) / kChunkWords) + 1;
   forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {

@@ -100,6 +100,14 @@ std::pair<uint64_t, uint64_t> totalAndMax(const std::vector<at::Tensor>& ts) {
   return {total, mx};
 }
 
+// The device of an operator's ts_in, a non-empty list of GPU tensors.
+int inputDevice(const std::vector<at::Tensor>& tsIn) {
+  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
+  const int dev = tsIn.front().get_device();
+  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  return dev;
+}
+
 void checkGpuTensor(const at::Tensor& t, int dev) {
   TORCH_CHECK(t.device().type() == at::kCUDA, "inputs must be GPU tensors");
   TORCH_CHECK(t.is_contiguous(), "inputs must be contiguous");
@@ -114,6 +122,30 @@ void checkSplitSum(uint64_t sum, const at::Tensor& t, bool asFloat, const char* 
   TORCH_CHECK(sum <= have, "the split sizes sum to ", sum, asFloat ? " words" : " bytes", " but ", name, " holds ",
               have);
 }
+
+// The split sizes of a split-size operator (argument `name`): a contiguous
+// CPU int32 tensor; take(i) checks entry i and adds it to the u32 column.
+struct SplitSizes {
+  const int32_t* sp;
+  int64_t n;
+  std::vector<uint32_t> sizes;
+  uint64_t sum = 0;
+  uint32_t mx = 0;
+  SplitSizes(const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_contiguous() && t.device().type() == at::kCPU && t.scalar_type() == at::kInt, name,
+                " must be a contiguous CPU int32 tensor");
+    sp = t.data_ptr<int32_t>();
+    n = t.numel();
+    sizes.resize(size_t(n));
+  }
+  void take(int64_t i) {
+    TORCH_CHECK(sp[i] > 0, "split sizes must be > 0");
+    sizes[size_t(i)] = uint32_t(sp[i]);
+    mx = std::max(mx, sizes[size_t(i)]);
+    sum += sizes[size_t(i)];
+  }
+  const uint32_t* data() const { return sizes.data(); }
+};
 
 // An archive on the device: contiguous uint8, 4-byte aligned (k_decode reads
 // the headers with scalar loads, which drop the low two address bits: the
@@ -283,9 +315,7 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compress_data(bool asFloat, const st
                                                           bool checksum, const std::optional<at::Tensor>& tempMem,
                                                           const std::optional<at::Tensor>& outCompressed,
                                                           const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
   auto res = makeStack(dev, tempMem);
   return compressRes(asFloat, res, tsIn, checksum, outCompressed, outSizes);
@@ -310,25 +340,18 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
     TORCH_CHECK(reinterpret_cast<uintptr_t>(tIn.data_ptr()) % 4 == 0,
                 "All splits should start on a 16 byte boundary; start pointer is not aligned");
   }
-  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt,
-              "t_in_split_sizes must be a contiguous CPU int32 tensor");
-  const int64_t n = tSplit.numel();
-  const int32_t* sp = tSplit.data_ptr<int32_t>();
-  std::vector<uint32_t> split(static_cast<size_t>(n));
-  uint32_t mx = 0;
-  uint64_t sum = 0;
+  SplitSizes split(tSplit, "t_in_split_sizes");
+  const int64_t n = split.n;
   for (int64_t i = 0; i < n; ++i) {
-    TORCH_CHECK(sp[i] > 0, "split sizes must be > 0");
-    split[size_t(i)] = uint32_t(sp[i]);
-    mx = std::max(mx, split[size_t(i)]);
-    sum += split[size_t(i)];
+    split.take(i);
     if (!asFloat && i != n - 1) {
-      TORCH_CHECK(sp[i] % 4 == 0,
+      TORCH_CHECK(split.sp[i] % 4 == 0,
                   "All splits should start on a 16 byte boundary; the size of an interior split is not a "
                   "multiple of 16 bytes");
     }
   }
-  checkSplitSum(sum, tIn, asFloat, "t_in");
+  checkSplitSum(split.sum, tIn, asFloat, "t_in");
+  const uint32_t mx = split.mx;
   const int64_t cols = asFloat ? int64_t(getMaxFloatCompressedSize(ft, mx)) : int64_t(getMaxCompressedSize(mx));
   const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, tIn);
   auto res = makeStack(dev, tempMem);
@@ -350,9 +373,7 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
 // DietGpu.cpp:472-526
 std::vector<at::Tensor> compress_data_simple(bool asFloat, const std::vector<at::Tensor>& tsIn, bool checksum,
                                              std::optional<int64_t> tempMem) {
-  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
   std::optional<at::Tensor> scratch;
   if (tempMem && *tempMem > 0) scratch = at::empty({*tempMem}, tsIn.front().options().dtype(at::kByte));
@@ -371,8 +392,10 @@ void checkOutDtype(const at::Tensor& t) {
               "float outputs must be float16, bfloat16, float32 or float64");
 }
 
-void checkStatusTensors(const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes, int64_t n,
-                        int dev) {
+// The device pointers of the optional out_status / out_decompressed_words
+// tensors (n entries on `dev`), null when absent.
+std::pair<uint8_t*, uint32_t*> statusPointers(const std::optional<at::Tensor>& status,
+                                              const std::optional<at::Tensor>& sizes, int64_t n, int dev) {
   if (status) {
     TORCH_CHECK(status->is_contiguous() && status->device().type() == at::kCUDA && status->scalar_type() == at::kByte,
                 "out_status must be a contiguous uint8 GPU tensor");
@@ -385,6 +408,45 @@ void checkStatusTensors(const std::optional<at::Tensor>& status, const std::opti
     TORCH_CHECK(sizes->numel() == n && sizes->get_device() == dev, "out_decompressed_words must have ", n,
                 " entries on the input device");
   }
+  return {status ? status->data_ptr<uint8_t>() : nullptr,
+          sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr};
+}
+
+// The member columns of a decode-side operator: archives tsIn[i] into the
+// destinations tsOut[i] (argument `outName`), whose capacities count words of
+// their dtype when asFloat and bytes otherwise.  perMember(i) follows member
+// i's checks.
+struct DecodeMembers {
+  std::vector<const void*> in;
+  std::vector<void*> out;
+  std::vector<uint32_t> cap;
+};
+template <typename F>
+DecodeMembers decodeMembers(const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsOut, bool asFloat,
+                            int dev, const char* outName, F&& perMember) {
+  const size_t n = tsIn.size();
+  DecodeMembers m{std::vector<const void*>(n), std::vector<void*>(n), std::vector<uint32_t>(n)};
+  for (size_t i = 0; i < n; ++i) {
+    const auto& ti = tsIn[i];
+    const auto& to = tsOut[i];
+    checkArchiveTensor(ti, dev);
+    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(), outName,
+                " must be contiguous GPU tensors on the input device");
+    if (asFloat) {
+      checkOutDtype(to);
+      // the config's float type is the first destination's and every
+      // capacity is counted in words of it
+      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (", outName,
+                  ") must share a dtype");
+    }
+    const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
+    TORCH_CHECK(c <= kU32Max);
+    perMember(i);
+    m.in[i] = ti.data_ptr();
+    m.out[i] = to.data_ptr();
+    m.cap[i] = uint32_t(c);
+  }
+  return m;
 }
 
 void raiseOnChecksum(bool asFloat, bool mismatch) {
@@ -399,40 +461,19 @@ int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at
                       const std::optional<at::Tensor>& sizes) {
   TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
   const int dev = tsIn.front().get_device();
-  std::vector<const void*> in(tsIn.size());
-  std::vector<void*> out(tsIn.size());
-  std::vector<uint32_t> cap(tsIn.size());
-  for (size_t i = 0; i < tsIn.size(); ++i) {
-    const auto& ti = tsIn[i];
-    const auto& to = tsOut[i];
-    checkArchiveTensor(ti, dev);
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
-                "ts_out must be contiguous GPU tensors on the input device");
-    if (asFloat) {
-      checkOutDtype(to);
-      // the config's float type is ts_out[0]'s and every capacity is counted
-      // in words of it
-      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (ts_out) must share a dtype");
-    }
-    const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
-    TORCH_CHECK(c <= kU32Max);
-    in[i] = ti.data_ptr();
-    out[i] = to.data_ptr();
-    cap[i] = uint32_t(c);
-  }
-  checkStatusTensors(status, sizes, int64_t(tsIn.size()), dev);
-  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
-  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
+  DecodeMembers m = decodeMembers(tsIn, tsOut, asFloat, dev, "ts_out", [](size_t) {});
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
   const hipStream_t s = currentStream(dev);
   if (asFloat) {
     const FloatDecompressConfig cfg(floatTypeOf(tsOut.front().scalar_type()), ANSCodecConfig(kDefaultPrecision),
                                     false, checksum);
-    const auto r = floatDecompress(res, cfg, uint32_t(tsIn.size()), in.data(), out.data(), cap.data(), st, sz, s);
+    const auto r =
+        floatDecompress(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(), st, sz, s);
     raiseOnChecksum(true, r.error != FloatDecompressError::None);
   } else {
     const ANSCodecConfig cfg(kDefaultPrecision, checksum);
-    const auto r = ansDecodeBatchPointer(res, cfg, uint32_t(tsIn.size()), in.data(), out.data(), cap.data(), st,
-                                         sz, s);
+    const auto r = ansDecodeBatchPointer(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(),
+                                         st, sz, s);
     raiseOnChecksum(false, r.error != ANSDecodeError::None);
   }
   return int64_t(res.getMaxMemoryUsage());
@@ -442,9 +483,7 @@ int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at
 int64_t decompress_data(bool asFloat, const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsOut,
                         bool checksum, const std::optional<at::Tensor>& tempMem,
                         const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
   auto res = makeStack(dev, tempMem);
   return decompressRes(asFloat, res, tsIn, tsOut, checksum, status, sizes);
@@ -458,47 +497,29 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
                               const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
                               const std::optional<at::Tensor>& sizes) {
   TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
   TORCH_CHECK(tFirst.is_contiguous() && tFirst.device().type() == at::kCPU && tFirst.scalar_type() == at::kLong,
               "t_first must be a contiguous CPU int64 tensor");
   TORCH_CHECK(tFirst.numel() == int64_t(tsIn.size()), "one t_first entry per compressed input");
   const int64_t* fp = tFirst.data_ptr<int64_t>();
-  std::vector<const void*> in(tsIn.size());
-  std::vector<void*> out(tsIn.size());
-  std::vector<uint32_t> first(tsIn.size()), count(tsIn.size());
-  for (size_t i = 0; i < tsIn.size(); ++i) {
-    const auto& ti = tsIn[i];
-    const auto& to = tsOut[i];
-    checkArchiveTensor(ti, dev);
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
-                "ts_out must be contiguous GPU tensors on the input device");
-    if (asFloat) {
-      checkOutDtype(to);
-      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (ts_out) must share a dtype");
-    }
-    const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
-    TORCH_CHECK(c <= kU32Max);
+  std::vector<uint32_t> first(tsIn.size());
+  // (the members' capacities are the ranges' counts)
+  DecodeMembers m = decodeMembers(tsIn, tsOut, asFloat, dev, "ts_out", [&](size_t i) {
     TORCH_CHECK(fp[i] >= 0 && uint64_t(fp[i]) <= kU32Max, "t_first[", i, "] = ", fp[i], " is outside [0, 2^32)");
-    in[i] = ti.data_ptr();
-    out[i] = to.data_ptr();
     first[i] = uint32_t(fp[i]);
-    count[i] = uint32_t(c);
-  }
-  checkStatusTensors(status, sizes, int64_t(tsIn.size()), dev);
-  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
-  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
+  });
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
   auto res = makeStack(dev, tempMem);
   const hipStream_t s = currentStream(dev);
   if (asFloat) {
     const FloatDecompressConfig cfg(floatTypeOf(tsOut.front().scalar_type()), ANSCodecConfig(kDefaultPrecision),
                                     false, false);
-    floatDecompressRange(res, cfg, uint32_t(tsIn.size()), in.data(), first.data(), count.data(), out.data(), st, sz,
-                         s);
+    floatDecompressRange(res, cfg, uint32_t(tsIn.size()), m.in.data(), first.data(), m.cap.data(), m.out.data(), st,
+                         sz, s);
   } else {
-    ansDecodeBatchRange(res, ANSCodecConfig(kDefaultPrecision, false), uint32_t(tsIn.size()), in.data(),
-                        first.data(), count.data(), out.data(), st, sz, s);
+    ansDecodeBatchRange(res, ANSCodecConfig(kDefaultPrecision, false), uint32_t(tsIn.size()), m.in.data(),
+                        first.data(), m.cap.data(), m.out.data(), st, sz, s);
   }
   return int64_t(res.getMaxMemoryUsage());
 }
@@ -521,33 +542,18 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
     checkOutDtype(ta);
     TORCH_CHECK(ta.scalar_type() == tsAcc.front().scalar_type(), "the accumulators (ts_acc) must share a dtype");
   }
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
-  std::vector<const void*> in(tsIn.size());
-  std::vector<void*> acc(tsIn.size());
-  std::vector<uint32_t> cap(tsIn.size());
-  for (size_t i = 0; i < tsIn.size(); ++i) {
-    const auto& ti = tsIn[i];
-    const auto& ta = tsAcc[i];
-    checkArchiveTensor(ti, dev);
-    TORCH_CHECK(ta.device().type() == at::kCUDA && ta.get_device() == dev && ta.is_contiguous(),
-                "ts_acc must be contiguous GPU tensors on the input device");
-    TORCH_CHECK(uint64_t(ta.numel()) <= kU32Max);
-    in[i] = ti.data_ptr();
-    acc[i] = ta.data_ptr();
-    cap[i] = uint32_t(ta.numel());
-  }
-  checkStatusTensors(status, sizes, int64_t(tsIn.size()), dev);
-  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
-  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
+  // (the dtype checks above come first; in the loop they pass again)
+  DecodeMembers m = decodeMembers(tsIn, tsAcc, /*asFloat=*/true, dev, "ts_acc", [](size_t) {});
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
   auto res = makeStack(dev, tempMem);
   const hipStream_t s = currentStream(dev);
   const FloatType accType = floatTypeOf(tsAcc.front().scalar_type());
   FloatType ft = accType;
   if (accType == FloatType::kFloat32) {
     at::Tensor type = at::zeros({1}, tsIn.front().options().dtype(at::kInt));
-    floatGetCompressedInfo(res, in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
+    floatGetCompressedInfo(res, m.in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
                            s);
     const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
     TORCH_CHECK(t0 != 4, "float32 accumulators take float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
@@ -556,7 +562,8 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
     if (t0 == 1 || t0 == 2) ft = FloatType(t0);
   }
   const FloatDecompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, false);
-  floatDecompressAccumulate(res, cfg, uint32_t(tsIn.size()), in.data(), acc.data(), cap.data(), accType, st, sz, s);
+  floatDecompressAccumulate(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(), accType, st, sz,
+                            s);
   return int64_t(res.getMaxMemoryUsage());
 }
 
@@ -564,34 +571,24 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
                                    const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
-  TORCH_CHECK(tSplit.is_contiguous() && tSplit.device().type() == at::kCPU && tSplit.scalar_type() == at::kInt,
-              "t_out_split_sizes must be a contiguous CPU int32 tensor");
-  const int64_t n = tSplit.numel();
+  SplitSizes split(tSplit, "t_out_split_sizes");
+  const int64_t n = split.n;
   TORCH_CHECK(n == int64_t(tsIn.size()), "one split size per compressed input");
-  const int32_t* sp = tSplit.data_ptr<int32_t>();
-  std::vector<uint32_t> split(static_cast<size_t>(n));
   std::vector<const void*> in(static_cast<size_t>(n));
-  uint64_t sum = 0;
   for (int64_t i = 0; i < n; ++i) {
     const auto& ti = tsIn[size_t(i)];
     checkArchiveTensor(ti, dev);
-    TORCH_CHECK(sp[i] > 0, "split sizes must be > 0");
-    split[size_t(i)] = uint32_t(sp[i]);
-    sum += split[size_t(i)];
+    split.take(i);
     in[size_t(i)] = ti.data_ptr();
   }
   TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev && tOut.is_contiguous(),
               "t_out must be a contiguous GPU tensor on the input device");
   if (asFloat) checkOutDtype(tOut);
-  checkSplitSum(sum, tOut, asFloat, "t_out");
-  checkStatusTensors(status, sizes, n, dev);
+  checkSplitSum(split.sum, tOut, asFloat, "t_out");
+  const auto [st, sz] = statusPointers(status, sizes, n, dev);
   auto res = makeStack(dev, tempMem);
-  auto* st = status ? status->data_ptr<uint8_t>() : nullptr;
-  auto* sz = sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr;
   const hipStream_t s = currentStream(dev);
   if (asFloat) {
     const FloatDecompressConfig cfg(floatTypeOf(tOut.scalar_type()), ANSCodecConfig(kDefaultPrecision), false,
@@ -609,9 +606,7 @@ int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& 
 // DietGpu.cpp:834-917
 std::vector<at::Tensor> decompress_data_simple(bool asFloat, const std::vector<at::Tensor>& tsIn, bool checksum,
                                                std::optional<int64_t> tempMem) {
-  TORCH_CHECK(!tsIn.empty(), "ts_in must not be empty");
-  const int dev = tsIn.front().get_device();
-  TORCH_CHECK(dev >= 0, "inputs must be GPU tensors");
+  const int dev = inputDevice(tsIn);
   c10::hip::HIPGuard guard(dev);
   for (const auto& t : tsIn) checkArchiveTensor(t, dev);  // (before k_info reads the headers)
   std::optional<at::Tensor> scratch;
