@@ -82,6 +82,8 @@ def _declare(L):
         "dietgpu_float_decompress_range": (c_int, [vp, c_int, c_int, c_u32, P, P, P, P, P, P, P]),
         "dietgpu_float_decompress_sparse_range": (c_int, [vp, c_int, c_int, c_u32, P, P, P, P, P, P, P]),
         "dietgpu_float_decompress_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
+        "dietgpu_ans_gather_rows": (c_int, [vp, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
+        "dietgpu_float_gather_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),
@@ -122,7 +124,8 @@ def testlib():
                "dietgpu_test_histogram": (c_int, [P, c_u32, P, c_u32, c_u32, P, P]),
                "dietgpu_test_enc_magic": (c_int, [P, P]),
                "dietgpu_test_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
-               "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P])}
+               "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
+               "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P])}
         for name, (res, args) in sig.items():
             f = getattr(T, name)
             f.restype = res

@@ -376,6 +376,67 @@ def gather_rows(archive, row_words, rows, dtype, out=None, prob_bits=10, ws=None
     return out
 
 
+def _row_stride(out, row_words):
+    """The stride in words between the rows of out [*lead, row_words], or None
+    when the last dimension is not contiguous or the rows lie at no one stride."""
+    if row_words != 1 and out.stride(-1) != 1:
+        return None
+    stride, inner = None, 1
+    for d in range(out.dim() - 2, -1, -1):
+        if out.size(d) != 1:
+            if stride is None:
+                stride = out.stride(d)
+            elif out.stride(d) != stride * inner:
+                return None
+        inner *= out.size(d)
+    return row_words if stride is None else stride
+
+
+def gather_rows_device(archive, row_words, idx, dtype, out=None, out_status=None, prob_bits=10, ws=None,
+                       check=False):
+    """Rows idx[...] of a [R, row_words] table stored as one dense float
+    archive (or, dtype torch.uint8, one byte archive) -> (out, ok), out
+    [*idx.shape, row_words] and ok a uint8 tensor of idx's shape: 1 where the
+    row lies inside the table and the archive matches dtype / prob_bits, 0
+    where not, and such a row of `out` is untouched.  idx is a contiguous CUDA
+    int32 or int64 tensor: the indices stay on the device, nothing is uploaded
+    or read back, and the call (one kernel launch on the current stream)
+    does not synchronise, so it can be captured in a graph and replayed on new
+    indices and new archive bytes.  A caller's `out` may be a view whose last
+    dimension is contiguous and whose rows lie at a constant stride.
+    check=True reads ok back and raises DietGpuError on any failing row."""
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype in (torch.int32, torch.int64)
+            and idx.is_contiguous()):
+        raise ValueError("gather_rows_device: idx must be a contiguous CUDA int32 or int64 tensor")
+    if dtype != torch.uint8 and dtype not in FLOAT_TYPE:
+        raise ValueError(f"gather_rows_device: unsupported dtype {dtype}")
+    row_words = int(row_words)
+    if row_words < 1:
+        raise ValueError("gather_rows_device: row_words must be at least 1")
+    shape = [*idx.shape, row_words]
+    out = out if out is not None else torch.empty(shape, dtype=dtype, device=idx.device)
+    if list(out.shape) != shape or out.dtype != dtype or out.device != idx.device:
+        raise ValueError(f"gather_rows_device: out must be a {dtype} tensor of shape {shape} on idx's device")
+    stride = _row_stride(out, row_words)
+    if stride is None or stride < row_words:
+        raise ValueError("gather_rows_device: out's last dimension must be contiguous and its rows must lie at "
+                         "a constant stride of at least row_words")
+    ok = out_status if out_status is not None else torch.empty(idx.shape, dtype=torch.uint8, device=idx.device)
+    if not (ok.dtype == torch.uint8 and ok.is_contiguous() and ok.shape == idx.shape and ok.device == idx.device):
+        raise ValueError("gather_rows_device: out_status must be a contiguous uint8 tensor of idx's shape")
+    ws = _ws(ws, idx.device)
+    tail = (archive.data_ptr(), row_words, idx.numel(), idx.data_ptr(), int(idx.dtype == torch.int64),
+            out.data_ptr(), stride, ok.data_ptr(), _s())
+    if dtype == torch.uint8:
+        N.check(N.lib().dietgpu_ans_gather_rows(ws.h, prob_bits, *tail))
+    else:
+        N.check(N.lib().dietgpu_float_gather_rows(ws.h, FLOAT_TYPE[dtype], prob_bits, *tail))
+    if check and not bool(ok.all()):
+        raise N.DietGpuError("gather_rows_device: a row lies outside the table, or the archive does not "
+                             "match dtype / prob_bits")
+    return out, ok
+
+
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
     return _pointer_compress(N.lib().dietgpu_float_compress_sparse, (ft, prob_bits, int(checksum)), ts,

@@ -334,6 +334,37 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int ft, int pb, uint
   });
 }
 
+// (the gather entry points check the flattened config and the row shape
+// before they look at the stack or any pointer)
+int dietgpu_ans_gather_rows(dietgpu_stack* res, int pb, const void* archive_dev, uint32_t row_words,
+                            uint32_t num_idx, const void* idx_dev, int idx_is_64, void* out_dev,
+                            uint64_t out_row_stride, uint8_t* succ, void* stream) {
+  return guarded([&] {
+    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    DG_CHECK(row_words >= 1, "rowWords must be at least 1");
+    DG_CHECK(out_row_stride >= row_words,
+             "outRowStrideWords (" << out_row_stride << ") must be at least rowWords (" << row_words << ")");
+    ansGatherRows(R(res), ANSCodecConfig(pb, false), archive_dev, row_words, num_idx, idx_dev, idx_is_64 != 0,
+                  out_dev, out_row_stride, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
+int dietgpu_float_gather_rows(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
+                              uint32_t num_idx, const void* idx_dev, int idx_is_64, void* out_dev,
+                              uint64_t out_row_stride, uint8_t* succ, void* stream) {
+  return guarded([&] {
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    DG_CHECK(row_words >= 1, "rowWords must be at least 1");
+    DG_CHECK(out_row_stride >= row_words,
+             "outRowStrideWords (" << out_row_stride << ") must be at least rowWords (" << row_words << ")");
+    floatGatherRows(R(res), cfg, archive_dev, row_words, num_idx, idx_dev, idx_is_64 != 0, out_dev, out_row_stride,
+                    succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

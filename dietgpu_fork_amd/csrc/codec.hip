@@ -24,6 +24,7 @@
 #include "dietgpu/GpuFloatCodec.h"
 #include "pcompress.h"
 #include "decode.h"
+#include "gather.h"
 #include "encode.h"
 #include "profile.h"
 
@@ -486,6 +487,41 @@ void decodeBatchDevice(const DecodeCall& c) {
   DG_CHECK(false, "decode form " << int(c.form) << " does not go with float type " << FT);
 }
 
+static void checkArchiveAligned4(uint64_t address, uint32_t i);
+
+// A row gather (k_gather, gather.h): rows idx_dev[0 .. numIdx)
+// of the [R, rowWords] table that the archive holds.  One launch of a
+// persistent grid (planGather, decode_plan.h); no host table, no upload, no
+// allocation and no read-back, so the call can be captured in a graph.  The
+// argument checks come before the device is touched.
+template <int FT>
+void gatherRowsDevice(int pb, const void* archive_dev, uint32_t rowWords, uint32_t numIdx, const void* idx_dev,
+                      bool idxIs64, void* out_dev, uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                      hipStream_t s) {
+  checkProbBits(pb);
+  DG_CHECK(rowWords >= 1, "rowWords must be at least 1");
+  DG_CHECK(outRowStrideWords >= rowWords,
+           "outRowStrideWords (" << outRowStrideWords << ") must be at least rowWords (" << rowWords << ")");
+  DG_CHECK(planGather(numIdx, rowWords, 1).valid,
+           "too many indices: numIdx (" << numIdx << ") times the " << gatherBlocksPerRow(rowWords)
+                                        << " blocks a row of " << rowWords << " words touches must be below 2^32");
+  if (numIdx == 0) return;
+  DG_CHECK(archive_dev && idx_dev && out_dev, "archive_dev, idx_dev and out_dev must not be null");
+  checkArchiveAligned4(reinterpret_cast<uintptr_t>(archive_dev), 0);
+  DG_CHECK(reinterpret_cast<uintptr_t>(idx_dev) % (idxIs64 ? 8 : 4) == 0, "idx_dev not aligned to its index size");
+  DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % sizeof(typename FloatTraits<FT>::WordT) == 0,
+           "out_dev not aligned to its word size");
+  const uint32_t lds = DecCfg<FT>::ldsBytes(pb);
+  const uint32_t slots = residentSlots(reinterpret_cast<const void*>(&k_gather<FT>), dec::kThreads, lds);
+  const GatherPlan plan = planGather(numIdx, rowWords, slots);
+  prof::Scope p("decode_gather", s);
+  k_gather<FT><<<plan.gridX, dec::kThreads, lds, s>>>(static_cast<const uint8_t*>(archive_dev), idx_dev,
+                                                      idxIs64 ? 1u : 0u, numIdx, rowWords, plan.K,
+                                                      static_cast<uint8_t*>(out_dev), outRowStrideWords, pb,
+                                                      outSuccess_dev);
+  HIP_LAUNCH_CHECK();
+}
+
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
 // (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112; the float
 // codec checksums `capacity` bytes, float words treated as bytes).  Host sync.
@@ -767,6 +803,15 @@ void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config, u
   decodeBatchDevice<0>(c);
 }
 
+void ansGatherRows(StackDeviceMemory& res, const ANSCodecConfig& config, const void* archive_dev,
+                   uint32_t rowWords, uint32_t numIdx, const void* idx_dev, bool idxIs64, void* out_dev,
+                   uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t stream) {
+  DG_CHECK(!config.useChecksum, "a row gather cannot verify a checksum (it covers the whole element)");
+  (void)res;  // nothing is allocated: the call can be captured in a graph
+  gatherRowsDevice<0>(config.probBits, archive_dev, rowWords, numIdx, idx_dev, idxIs64, out_dev, outRowStrideWords,
+                      outSuccess_dev, stream);
+}
+
 // k_info over a device array of archive addresses (the byte codec has no
 // type word)
 static void launchInfo(const void** in_dev, uint32_t nb, bool isFloat, uint32_t* outSizes_dev,
@@ -900,6 +945,18 @@ void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& c
   if (numInBatch == 0) return;
   const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, floatWordBytes(int(config.floatType)));
   floatDecompressDescs(config, rangeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
+}
+
+void floatGatherRows(StackDeviceMemory& res, const FloatDecompressConfig& config, const void* archive_dev,
+                     uint32_t rowWords, uint32_t numIdx, const void* idx_dev, bool idxIs64, void* out_dev,
+                     uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t stream) {
+  checkFloatConfig(config);
+  DG_CHECK(!config.useChecksum, "a row gather cannot verify a checksum (it covers the whole element)");
+  (void)res;  // nothing is allocated: the call can be captured in a graph
+  dispatchFloatType(config.floatType, [&](auto ft) {
+    gatherRowsDevice<decltype(ft)::value>(config.ansConfig.probBits, archive_dev, rowWords, numIdx, idx_dev, idxIs64,
+                                          out_dev, outRowStrideWords, outSuccess_dev, stream);
+  });
 }
 
 void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,

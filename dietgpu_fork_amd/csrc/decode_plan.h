@@ -2,7 +2,8 @@
 // launches per element, how many chunks each of them decodes, and whether
 // their waves run with remaining-work priorities.  Host only and free of HIP
 // headers, so that the rule -- performance policy, DESIGN.md 5.2 -- is stated
-// once and tested without a GPU (tests/test_decode_plan.py).
+// once and tested without a GPU (tests/test_decode_plan.py).  Below it the
+// grid rule of k_gather (gather.h; tests/test_gather_plan.py).
 #pragma once
 
 #include <algorithm>
@@ -53,6 +54,43 @@ inline DecodePlan planDecode(DecodeForm form, bool capacityOnly, uint32_t maxBlo
   // (c2 decode -2 %); across several generations they cost (c3 decode 2.02 ms
   // without, 2.32 ms with, same-box A/B).  Full decodes only.
   return {gridX, P, full && uint64_t(gridX) * ny <= slots};
+}
+
+// The grid rule of k_gather (gather.h): rows of rowWords words
+// of one element, each named by an index in device memory.
+struct GatherPlan {
+  bool valid;       // rowWords >= 1 and numIdx * K < 2^32
+  uint32_t K;       // tasks per index: the most 4096-word blocks a row touches
+  uint32_t groups;  // task groups (of kGatherTasksPerWG tasks)
+  uint32_t gridX;   // persistent workgroups; 0: nothing to launch
+};
+
+// a workgroup's 4 waves take a task per half-wave
+constexpr uint32_t kGatherTasksPerWG = 8;
+
+// A row that starts at word s touches divUp(s % 4096 + rowWords, 4096) blocks;
+// every start is a multiple of g = gcd(rowWords, 4096), so s % 4096 is at
+// most 4096 - g and some row attains K = divUp(4096 - g + rowWords, 4096).
+inline uint32_t gatherBlocksPerRow(uint32_t rowWords) {
+  uint64_t a = rowWords, b = 4096;
+  while (b) {
+    const uint64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  return uint32_t((4096 - a + rowWords + 4095) / 4096);
+}
+
+// slots: the workgroups of the launched instance resident on the device at
+// once.  One generation of them strides over the task groups, so that each
+// builds the decode table once.
+inline GatherPlan planGather(uint32_t numIdx, uint32_t rowWords, uint32_t slots) {
+  if (rowWords == 0) return {false, 0, 0, 0};
+  const uint32_t K = gatherBlocksPerRow(rowWords);
+  const uint64_t tasks = uint64_t(numIdx) * K;
+  if (tasks >= (1ull << 32)) return {false, K, 0, 0};
+  const uint32_t groups = uint32_t((tasks + kGatherTasksPerWG - 1) / kGatherTasksPerWG);
+  return {true, K, groups, std::min(std::max(1u, slots), groups)};
 }
 
 }  // namespace dietgpu

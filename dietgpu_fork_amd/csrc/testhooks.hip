@@ -158,6 +158,25 @@ int dietgpu_test_sparse_range_config(dietgpu_stack* res, int float_type, int use
   });
 }
 
+int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                               uint32_t row_words, uint32_t num_idx, const void* idx_dev, void* out,
+                               uint8_t* out_success_dev, void* stream) {
+  return guardedTest([&] {
+    using namespace dietgpu;
+    DG_CHECK(res && res->mem, "null dietgpu_stack");
+    DG_CHECK(float_type >= 0 && float_type <= 4, "float_type must be 0..4");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (float_type == 0) {
+      ansGatherRows(*res->mem, ANSCodecConfig(kANSDefaultProbBits, use_checksum != 0), in, row_words, num_idx,
+                    idx_dev, true, out, row_words, out_success_dev, s);
+    } else {
+      const FloatDecompressConfig cfg(FloatType(float_type), ANSCodecConfig(kANSDefaultProbBits), false,
+                                      use_checksum != 0);
+      floatGatherRows(*res->mem, cfg, in, row_words, num_idx, idx_dev, true, out, row_words, out_success_dev, s);
+    }
+  });
+}
+
 int dietgpu_test_enc_magic(uint32_t* magic_dev, void* stream) {
   return guardedTest([&] { dietgpu::testEncMagic(reinterpret_cast<hipStream_t>(stream), magic_dev); });
 }

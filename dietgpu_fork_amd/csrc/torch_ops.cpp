@@ -15,7 +15,9 @@
 // decompress_data_range, is not in the reference at all: it decodes a word
 // range of each archive (floatDecompressRange / ansDecodeBatchRange).  Nor is
 // the twelfth, decompress_data_accumulate: it adds each archive's element to
-// an accumulator tensor in place (floatDecompressAccumulate).
+// an accumulator tensor in place (floatDecompressAccumulate).  A thirteenth,
+// gather_rows, gathers rows of a table held by one archive, named by an index
+// tensor on the device (floatGatherRows / ansGatherRows).
 //
 // Argument checks the reference lacks (its DietGpu.cpp says "FIXME: total
 // range checking" where they belong); each raises before any temp-memory
@@ -567,6 +569,65 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
   return int64_t(res.getMaxMemoryUsage());
 }
 
+// Extension (no reference counterpart): rows t_idx[...] of the [R, row_words]
+// table that archive t_in holds, into t_out [*t_idx.shape, row_words]
+// (floatGatherRows / ansGatherRows).  t_idx is an int32 or int64 tensor on the
+// archive's device: the call reads nothing back and uploads nothing.  t_out
+// may be a view whose last dimension is contiguous and whose rows lie at a
+// constant stride.  out_status[i] = 1 iff row t_idx[i] lies inside the
+// element and the archive is valid; a failing row is left untouched.  The
+// checks that need no device come first.
+int64_t gather_rows(bool asFloat, const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx,
+                    const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
+                    const std::optional<at::Tensor>& status) {
+  TORCH_CHECK(rowWords >= 1 && uint64_t(rowWords) <= kU32Max, "row_words must be at least 1 (and below 2^32), not ",
+              rowWords);
+  TORCH_CHECK(tIdx.scalar_type() == at::kInt || tIdx.scalar_type() == at::kLong, "t_idx must be int32 or int64, not ",
+              tIdx.scalar_type());
+  if (asFloat) {
+    checkOutDtype(tOut);
+  } else {
+    TORCH_CHECK(tOut.scalar_type() == at::kByte, "t_out must be uint8 in byte mode, not ", tOut.scalar_type());
+  }
+  const int64_t k = tIdx.dim();
+  bool shapeOk = tOut.dim() == k + 1 && tOut.size(k) == rowWords;
+  for (int64_t d = 0; shapeOk && d < k; ++d) shapeOk = tOut.size(d) == tIdx.size(d);
+  TORCH_CHECK(shapeOk, "t_out must have the shape [*t_idx.shape, row_words] = [", tIdx.sizes(), ", ", rowWords,
+              "], not ", tOut.sizes());
+  // rows at one stride: leading dimension d strides over the rows inside it
+  TORCH_CHECK(rowWords == 1 || tOut.stride(k) == 1, "t_out's last dimension must be contiguous");
+  int64_t rowStride = -1, inner = 1;
+  for (int64_t d = k - 1; d >= 0; --d) {
+    if (tOut.size(d) != 1) {
+      if (rowStride < 0) rowStride = tOut.stride(d);
+      else TORCH_CHECK(tOut.stride(d) == rowStride * inner, "t_out's rows must lie at a constant stride");
+    }
+    inner *= tOut.size(d);
+  }
+  if (rowStride < 0) rowStride = rowWords;
+  TORCH_CHECK(rowStride >= rowWords, "t_out's rows must not overlap (row stride ", rowStride, " < row_words)");
+  TORCH_CHECK(uint64_t(tIdx.numel()) <= kU32Max, "too many indices");
+  TORCH_CHECK(tIdx.device().type() == at::kCUDA && tIdx.is_contiguous(),
+              "t_idx must be a contiguous GPU tensor (on the archive's device)");
+  const int dev = tIdx.get_device();
+  checkArchiveTensor(tIn, dev);
+  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
+  c10::hip::HIPGuard guard(dev);
+  const auto st = statusPointers(status, std::nullopt, tIdx.numel(), dev).first;
+  auto res = makeStack(dev, tempMem);
+  const hipStream_t s = currentStream(dev);
+  const bool is64 = tIdx.scalar_type() == at::kLong;
+  if (asFloat) {
+    const FloatDecompressConfig cfg(floatTypeOf(tOut.scalar_type()), ANSCodecConfig(kDefaultPrecision), false, false);
+    floatGatherRows(res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(tIdx.numel()), tIdx.data_ptr(), is64,
+                    tOut.data_ptr(), uint64_t(rowStride), st, s);
+  } else {
+    ansGatherRows(res, ANSCodecConfig(kDefaultPrecision, false), tIn.data_ptr(), uint32_t(rowWords),
+                  uint32_t(tIdx.numel()), tIdx.data_ptr(), is64, tOut.data_ptr(), uint64_t(rowStride), st, s);
+  }
+  return int64_t(res.getMaxMemoryUsage());
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -679,6 +740,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "decompress_data_accumulate(Tensor[] ts_in, Tensor[] ts_acc, Tensor? temp_mem=None, Tensor? out_status=None, "
       "Tensor? out_sizes=None) -> int");
+  m.def(
+      "gather_rows(bool compress_as_float, Tensor t_in, int row_words, Tensor t_idx, Tensor t_out, Tensor? "
+      "temp_mem=None, Tensor? out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -694,4 +758,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("decompress_data_simple", &dietgpu::decompress_data_simple);
   m.impl("decompress_data_range", &dietgpu::decompress_data_range);
   m.impl("decompress_data_accumulate", &dietgpu::decompress_data_accumulate);
+  m.impl("gather_rows", &dietgpu::gather_rows);
 }

@@ -8,7 +8,9 @@ with the same schemas, validation and return values).  An eleventh,
 ``decompress_data_range``, is an extension the reference does not have: it
 decodes a word range of each archive.  A twelfth,
 ``decompress_data_accumulate``, adds each archive's element to an accumulator
-tensor in place.  This module only loads that library
+tensor in place.  ``gather_rows`` (``MORE_OPS``) gathers rows of a table held
+by one archive, named by an index tensor on the device.  This module only
+loads that library
 and forwards ``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.
 """
 import os
@@ -35,6 +37,10 @@ OPS = (
     "decompress_data_accumulate",
 )
 
+# later extensions, kept apart from the twelve above: gather_rows gathers rows
+# of a table held by one archive, named by an index tensor on the device
+MORE_OPS = ("gather_rows",)
+
 _LOADED = False
 
 
@@ -53,7 +59,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS:
+    if name in OPS or name in MORE_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

@@ -115,4 +115,26 @@ void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config,
                          void** out, uint8_t* outSuccess_dev,
                          uint32_t* outSize_dev, hipStream_t stream);
 
+// Row gather with device-resident indices: the archive holds a table
+// [R, rowWords] of bytes, idx_dev numIdx row indices (int32, or int64 when
+// idxIs64) in device memory.
+//   out_dev[i * outRowStrideWords + j] = element[idx_dev[i] * rowWords + j],
+// 0 <= j < rowWords, 0 <= i < numIdx; nothing else is written, neither the
+// gap between rows of a wider stride nor any byte of a failing row.  Row i
+// succeeds iff the archive is valid for this config and 0 <= idx_dev[i] and
+// (idx_dev[i] + 1) * rowWords <= n, the element's size as its header states it
+// (compared in 64 bits); outSuccess_dev[i] (optional, numIdx bytes) = 1 or 0.
+// Indices may repeat.  rowWords >= 1, outRowStrideWords >= rowWords, numIdx
+// times the most blocks a row touches (divUp(4096 - gcd(rowWords, 4096) +
+// rowWords, 4096)) below 2^32; archive_dev 4-byte aligned (16-byte aligned
+// archives are read with vector loads).  config.useChecksum must be false, as
+// for a range.  One kernel launch: no host synchronisation, no host table, no
+// allocation (`res` is not used), so a call can be captured in a graph and
+// replayed on new indices and new archive bytes.
+void ansGatherRows(StackDeviceMemory& res, const ANSCodecConfig& config,
+                   const void* archive_dev, uint32_t rowWords, uint32_t numIdx,
+                   const void* idx_dev, bool idxIs64, void* out_dev,
+                   uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                   hipStream_t stream);
+
 } // namespace dietgpu

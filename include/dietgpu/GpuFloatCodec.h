@@ -188,4 +188,15 @@ void floatDecompressAccumulate(StackDeviceMemory& res,
                                uint8_t* outSuccess_dev, uint32_t* outSize_dev,
                                hipStream_t stream);
 
+// Row gather with device-resident indices from a dense float archive that
+// holds a table [R, rowWords] (see ansGatherRows, GpuANSCodec.h: the same
+// rules, in float words; out_dev word-aligned).  Sparse archives are not
+// gathered from here.
+void floatGatherRows(StackDeviceMemory& res,
+                     const FloatDecompressConfig& config,
+                     const void* archive_dev, uint32_t rowWords, uint32_t numIdx,
+                     const void* idx_dev, bool idxIs64, void* out_dev,
+                     uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                     hipStream_t stream);
+
 } // namespace dietgpu

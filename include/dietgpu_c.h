@@ -33,6 +33,8 @@
  *   checked against a whole element's checksum)
  *   dietgpu_float_decompress_sparse_range (the same of a sparse archive: a
  *   bitmap rank, then a range decode of the nonzero list's slice)
+ *   dietgpu_ans_gather_rows, dietgpu_float_gather_rows (rows of a table held
+ *   by one archive, named by indices in device memory; one launch)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -205,8 +207,27 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int float_type, int 
                                         uint8_t* out_success_dev, uint32_t* out_size_dev,
                                         void* stream);
 
+/* Row gather with device-resident indices (ansGatherRows / floatGatherRows,
+ * GpuANSCodec.h): the archive holds a table [R, row_words]; idx_dev holds
+ * num_idx row indices in device memory, int32 or (idx_is_64 != 0) int64.
+ * out_dev[i * out_row_stride_words + j] = element[idx_dev[i] * row_words + j];
+ * nothing else is written.  out_success_dev[i] (optional) = 1 iff the archive
+ * is valid and row idx_dev[i] lies inside the element, else 0 and the row is
+ * untouched.  One launch, no host synchronisation, no allocation: the call
+ * can be captured in a graph.  No checksum flag, as for a range. */
+int dietgpu_ans_gather_rows(dietgpu_stack* res, int prob_bits, const void* archive_dev,
+                            uint32_t row_words, uint32_t num_idx, const void* idx_dev,
+                            int idx_is_64, void* out_dev, uint64_t out_row_stride_words,
+                            uint8_t* out_success_dev, void* stream);
+int dietgpu_float_gather_rows(dietgpu_stack* res, int float_type, int prob_bits,
+                              const void* archive_dev, uint32_t row_words, uint32_t num_idx,
+                              const void* idx_dev, int idx_is_64, void* out_dev,
+                              uint64_t out_row_stride_words, uint8_t* out_success_dev,
+                              void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
- * named kernel family ("encode", "decode", "decode_range", "decode_accumulate", "hist", "coalesce") is bracketed
+ * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
+ * "decode_gather", "hist", "coalesce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);

@@ -57,6 +57,13 @@ int dietgpu_test_sparse_range_config(dietgpu_stack* res, int float_type, int use
                                      uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
                                      uint32_t* out_size_dev, void* stream);
 
+/* The same for the row gather's C++ entry points (floatGatherRows,
+ * ansGatherRows; float_type 0 = the byte codec): num_idx int64 indices at
+ * idx_dev, rows of row_words words at a stride of row_words. */
+int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                               uint32_t row_words, uint32_t num_idx, const void* idx_dev, void* out,
+                               uint8_t* out_success_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
