@@ -153,6 +153,82 @@ __device__ __forceinline__ void decStepAll(DStream* const (&p)[NC], const bool (
     p[c]->x = __builtin_amdgcn_perm(xn[c], v[c], rd[c] ? 0x05040100u : 0x07060504u);
 }
 
+// kUnroll steps of a wave's S chains, the steps between two ring checks:
+// steps tr0 + kUnroll - 1 down to tr0 of a segment; each step's symbols
+// (sym << 8) go to segLane[s][step * 32].
+// kMask: a partial segment, or a half that idles: step tBot + tr is a no-op
+// in a lane whose word (tBot + tr) * 32 + l lies at or past its block's uw.
+// (The ring check stays in the callers' loops: with ringEnsure inside this
+// function the compiler lays its refill branches out the other way round, and
+// the bf16 range decode measured 0.3 - 0.5 us slower,
+// profiles/decode_body_ab.json.)
+template <bool kMask, int S>
+__device__ __forceinline__ void decSteps(DStream* const (&chains)[S], lp<const u32x2> const (&lut)[S],
+                                         uint32_t mask, int pb, uint32_t hv, lp<uint16_t> const (&segLane)[S],
+                                         int tr0, int32_t tBot, uint32_t l, uint32_t uw) {
+#pragma unroll
+  for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
+    const int tr = tr0 + u;  // step within segment
+    bool vld[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) vld[s] = !kMask || uint32_t(tBot + tr) * 32 + l < uw;
+    uint32_t e0[S];
+    decStepAll<kMask, S>(chains, vld, lut, mask, pb, hv, e0);
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+      if (vld[s]) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
+  }
+}
+
+// ~0 in lanes 32-63, 0 in lanes 0-31: `hv & x` selects x for the wave's second
+// block.
+__device__ __forceinline__ uint32_t upperHalfMask(uint32_t lane) {
+  uint32_t hv = lane >= 32 ? ~0u : 0u;
+  asm volatile("" : "+v"(hv));  // keep `hv & x` a v_and (not a v_cndmask pair)
+  return hv;
+}
+
+// Bind stream d of a wave's block pair to half-stream pair hs of the
+// workgroup's rings and segment buffers; segLane: where this lane's symbol of
+// a segment's step 0 goes.
+__device__ __forceinline__ void bindStream(DStream& d, lp<uint16_t>& segLane, lp<uint16_t> ringAll,
+                                           lp<uint16_t> segAll, uint32_t hs, uint32_t hv, uint32_t l) {
+  d.ring = ringAll + hs * 2 * dec::kRing;
+  d.ringLane = d.ring + (hv & dec::kRing);
+  segLane = segAll + hs * 2 * dec::kSegWords + (hv & dec::kSegWords) + l;
+}
+
+// Open half hh of stream d: `data` the archive's compressed words, e the
+// blockWords entry of the half's block, has: whether the half has a block at
+// all (an idle half reads nothing).  Fills the ring from the block's top and
+// issues the first prefetch.  (Per half, the flag by value: one function for
+// both halves, their flags in an array, cost k_decode's byte range instance a
+// VGPR and moved the code of others, tools/kres.py.)
+__device__ __forceinline__ void openHalf(DStream& d, int hh, gp<const uint16_t> data, uint2 e, bool has,
+                                         uint32_t lane, bool vecIn) {
+  d.ptr[hh] = 0;
+  d.lo[hh] = 0;
+  d.data[hh] = data;
+  d.pf[hh] = u32x2{0, 0};
+  if (has) {
+    const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
+    const int32_t cw = int32_t(ex & 0xffffu);
+    d.ptr[hh] = cw;
+    d.data[hh] = data + ey;
+    const int32_t lo = cw > int32_t(dec::kRing) ? int32_t(roundUp(uint32_t(cw) - dec::kRing, dec::kWPL)) : 0;
+    d.lo[hh] = lo;
+    // initial fill of [lo, cw) (<= 512 words: two wave-wide passes).
+    // The last lane may copy up to 3 words past cw (the block's
+    // 8-word padding) into slots below lo + 512: never a live slot.
+#pragma unroll
+    for (int q = 0; q < int(dec::kRing / dec::kRefill); ++q) {
+      const int32_t a = lo + q * int32_t(dec::kRefill) + int32_t(dec::kWPL * lane);
+      if (a < cw) *(lp<u32x2>)(d.ring + hh * dec::kRing + (a & (dec::kRing - 1))) = ld4w(d.data[hh] + a, vecIn);
+    }
+    ringPrefetch(d, hh, lane, vecIn);
+  }
+}
+
 // Wave priority from the share of the wave's work still ahead (wave-uniform
 // q in [0, 3]): the SIMD arbiter otherwise favours the oldest waves, so waves
 // that started together finish up to ~35 % apart and the kernel ends on a
@@ -418,6 +494,71 @@ struct Join {
   }
 };
 
+// The symbols of a lane's 8-word chunk (q0 / q1: its 16 B of stream 0 / of the
+// last stream in the segment buffer) as Join::vec takes them.
+template <int S>
+__device__ __forceinline__ void loadChunkSyms(lp<const uint16_t> q0, lp<const uint16_t> q1, uint32_t (&sv)[4],
+                                              uint32_t (&sv1)[4]) {
+  const u32x4 a0 = *(lp<const u32x4>)q0;
+  sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
+  if constexpr (S == 2) {
+    const u32x4 b0 = *(lp<const u32x4>)q1;
+    sv1[0] = b0.x; sv1[1] = b0.y; sv1[2] = b0.z; sv1[3] = b0.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sv1[k] = 0;
+  }
+}
+
+// Range edge rule: words [k0, k1) of the cnt-word chunk at word i0 lie in
+// [rlo, rhi); false: none does.
+__device__ __forceinline__ bool clipChunk(uint32_t i0, uint32_t cnt, uint32_t rlo, uint32_t rhi, uint32_t& k0,
+                                          uint32_t& k1) {
+  k0 = i0 < rlo ? min(cnt, rlo - i0) : 0u;
+  k1 = rhi > i0 ? min(cnt, rhi - i0) : 0u;
+  return k0 < k1;
+}
+
+// Masked scalar join: words [k0, k1) of the chunk at word i0 go to o[i0 + k].
+template <class J>
+__device__ __forceinline__ void joinWords(gp<typename J::WordT> o, lp<const uint16_t> q0, lp<const uint16_t> q1,
+                                          gp<const uint8_t> raw, uint32_t n, uint32_t i0, uint32_t k0, uint32_t k1) {
+  for (uint32_t k = k0; k < k1; ++k) o[i0 + k] = J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
+}
+
+// The headers of the element at base: its size (returned), its S ANS
+// archives, and ok: whether they are a float archive of type FT (raw ANS for
+// FT 0) whose ANS archives hold n symbols each at precision pb.  (n returned
+// and ok by reference: the other way round grew k_decode's fp16 / bf16
+// instances by 32 bytes, tools/kres.py.)
+// (Every read here depends only on the headers: for an element whose size
+// word is 0 they all lie in its first 64 bytes.  The sparse range decode
+// relies on that for the zeroed 256 B element it passes for a member that is
+// no sparse archive, sparse.hip k_sparseRangePlan.)
+template <int FT>
+__device__ __forceinline__ uint32_t openArchive(gp<const uint8_t> base, int pb, bool& ok,
+                                                gp<const uint8_t> (&arch)[DecCfg<FT>::S]) {
+  constexpr int S = DecCfg<FT>::S;
+  gp<const uint32_t> fh = (gp<const uint32_t>)base;
+  uint32_t n;
+  if constexpr (FT == 0) {
+    n = fh[kAnsSize];
+    ok = fh[kAnsMagic] == kANSMagicVersion;
+  } else {
+    n = fh[kFloatSize];
+    ok = fh[kFloatMagic] == kFloatMagicVersion && (fh[kFloatType] & kTypeMask) == uint32_t(FT);
+  }
+  arch[0] = ansArchiveOf<FT>(base, n);
+  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[kFloatSecondAns];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
+    ok = ok && ah[kAnsMagic] == kANSMagicVersion && (ah[kAnsPrecision] & kTypeMask) == uint32_t(pb) &&
+         ah[kAnsSize] == n;
+  }
+  return n;
+}
+
 // 64-bit decode table of one archive: entry[slot] = {pdf | sym << 24,
 // slot - cdf[sym]} (packDecodeLookup, ans/GpuANSDecode.cuh:34-44, re-laid
 // out for v_mad_u32_u24).  scratch: >= 2 * 256 + 4 dwords of LDS.
@@ -520,30 +661,10 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   const uint32_t b = batchOffset + blockIdx.y;
   const uint32_t tid = threadIdx.x;
   gp<const uint8_t> base = startOf(in, b);
-  gp<const uint32_t> fh = (gp<const uint32_t>)base;
 
   gp<const uint8_t> arch[S];
-  uint32_t n;
   bool ok;
-  if constexpr (FT == 0) {
-    n = fh[kAnsSize];
-    ok = fh[kAnsMagic] == kANSMagicVersion;
-  } else {
-    n = fh[kFloatSize];
-    ok = fh[kFloatMagic] == kFloatMagicVersion && (fh[kFloatType] & kTypeMask) == uint32_t(FT);
-  }
-  arch[0] = ansArchiveOf<FT>(base, n);
-  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[kFloatSecondAns];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
-    ok = ok && ah[kAnsMagic] == kANSMagicVersion && (ah[kAnsPrecision] & kTypeMask) == uint32_t(pb) &&
-         ah[kAnsSize] == n;
-  }
-  // (Every read up to here depends only on the headers: for an element whose
-  // size word is 0 they all lie in its first 64 bytes.  The sparse range
-  // decode relies on that for the zeroed 256 B element it passes for a member
-  // that is no sparse archive, sparse.hip k_sparseRangePlan.)
+  const uint32_t n = openArchive<FT>(base, pb, ok, arch);
   // range form: words [rlo, rhi) of the element, blocks [blkFirst, blkEnd)
   uint32_t rlo = 0, rhi = 0;
   bool success;
@@ -574,8 +695,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   }
 
   const uint32_t w = readfirst(tid >> 6), lane = tid & 63, l = lane & 31;
-  uint32_t hv = lane >= 32 ? ~0u : 0u;
-  asm volatile("" : "+v"(hv));  // keep `hv & x` a v_and (not a v_cndmask pair)
+  const uint32_t hv = upperHalfMask(lane);
 
   const bool vecIn = (reinterpret_cast<uintptr_t>(base) & 15) == 0;
   gp<uint8_t> outB = startOf(out, b);
@@ -673,49 +793,15 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       gp<const uint16_t> data = AnsSections(arch[s], nBlocks).words;
-      DStream& d = st[s];
-      const uint32_t hs = w * S + s;  // half-stream pair index
-      d.ring = ringAll + hs * 2 * dec::kRing;
-      d.ringLane = d.ring + (hv & dec::kRing);
-      segLane[s] = segAll + hs * 2 * dec::kSegWords + (hv & dec::kSegWords) + l;
+      bindStream(st[s], segLane[s], ringAll, segAll, w * S + s, hv, l);
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const uint32_t bk = blk0 + hh;
-        d.ptr[hh] = 0;
-        d.lo[hh] = 0;
-        d.data[hh] = data;
-        d.pf[hh] = u32x2{0, 0};
-        if (bk < blkEnd) {
-          const uint2 e = bwE[s][hh];
-          const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
-          const int32_t cw = int32_t(ex & 0xffffu);
-          d.ptr[hh] = cw;
-          d.data[hh] = data + ey;
-          const int32_t lo =
-              cw > int32_t(dec::kRing) ? int32_t(roundUp(uint32_t(cw) - dec::kRing, dec::kWPL)) : 0;
-          d.lo[hh] = lo;
-          // initial fill of [lo, cw) (<= 512 words: two wave-wide passes).
-          // The last lane may copy up to 3 words past cw (the block's
-          // 8-word padding) into slots below lo + 512: never a live slot.
-#pragma unroll
-          for (int q = 0; q < int(dec::kRing / dec::kRefill); ++q) {
-            const int32_t a = lo + q * int32_t(dec::kRefill) + int32_t(dec::kWPL * lane);
-            if (a < cw)
-              *(lp<u32x2>)(d.ring + hh * dec::kRing + (a & (dec::kRing - 1))) = ld4w(d.data[hh] + a, vecIn);
-          }
-          ringPrefetch(d, hh, lane, vecIn);
-        }
-      }
-      d.x = x0[s];
+      for (int hh = 0; hh < 2; ++hh) openHalf(st[s], hh, data, bwE[s][hh], blk0 + hh < blkEnd, lane, vecIn);
+      st[s].x = x0[s];
     }
 
     DStream* chains[S];
-    bool allValid[S];
 #pragma unroll
-    for (int s = 0; s < S; ++s) {
-      chains[s] = &st[s];
-      allValid[s] = true;
-    }
+    for (int s = 0; s < S; ++s) chains[s] = &st[s];
 
     // kVec: 16 B aligned input and output (once per wave): full segments
     // then load and join unconditionally.
@@ -743,32 +829,20 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         // range form: words [k0, k1) of the chunk lie in the range
         uint32_t k0 = 0, k1 = cnt;
         if constexpr (RNG) {
-          k0 = i0 < rlo ? min(cnt, rlo - i0) : 0u;
-          k1 = rhi > i0 ? min(cnt, rhi - i0) : 0u;
-          if (k0 >= k1) return;
+          if (!clipChunk(i0, cnt, rlo, rhi, k0, k1)) return;
         }
         lp<const uint16_t> q0 = segLane[0] - l + off;
         lp<const uint16_t> q1 = segLane[S - 1] - l + off;
         if (kVec && cnt == dec::kChunk && wholeInRange(i0)) {
           uint32_t sv[4], sv1[4];
-          const u32x4 a0 = *(lp<const u32x4>)q0;
-          sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
-          if constexpr (S == 2) {
-            const u32x4 b0 = *(lp<const u32x4>)q1;
-            sv1[0] = b0.x; sv1[1] = b0.y; sv1[2] = b0.z; sv1[3] = b0.w;
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sv1[k] = 0;
-          }
+          loadChunkSyms<S>(q0, q1, sv, sv1);
           if constexpr (ACC) J::vecAcc(outB, i0, sv, sv1, rv, dv);
           else J::template vec<NT>(outB, i0, sv, sv1, rv);
         } else if constexpr (ACC) {
           gp<AccT> a = (gp<AccT>)outB + uint64_t(i0);
           for (uint32_t k = k0; k < k1; ++k) a[k] = J::sumOne(a[k], J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k));
         } else {
-          gp<WordT> o = (gp<WordT>)outB;
-          for (uint32_t k = k0; k < k1; ++k)
-            o[i0 + k] = J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
+          joinWords<J>((gp<WordT>)outB, q0, q1, raw, n, i0, k0, k1);
         }
       };
 
@@ -785,20 +859,8 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
 #pragma unroll
           for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, kVec);
-#pragma unroll
-          for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
-            const int tr = grp * int(dec::kUnroll) + u;
-            const uint32_t t = uint32_t(tBot + tr);
-            const uint32_t uw = lane >= 32 ? uwH[1] : uwH[0];
-            bool vld[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) vld[s] = t * 32 + l < uw;
-            uint32_t e0[S];
-            decStepAll<true, S>(chains, vld, lut, mask, pb, hv, e0);
-#pragma unroll
-            for (int s = 0; s < S; ++s)
-              if (vld[s]) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
-          }
+          decSteps<true, S>(chains, lut, mask, pb, hv, segLane, grp * int(dec::kUnroll), tBot, l,
+                            lane >= 32 ? uwH[1] : uwH[0]);
         }
         __builtin_amdgcn_wave_barrier();
         join(g, false, rvA, dvA);
@@ -815,14 +877,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
         for (int grp = int(dec::kSegSteps / dec::kUnroll) - 1; grp >= 0; --grp) {
 #pragma unroll
           for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, kVec);
-#pragma unroll
-          for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
-            const int tr = grp * int(dec::kUnroll) + u;  // step within segment
-            uint32_t e0[S];
-            decStepAll<false, S>(chains, allValid, lut, mask, pb, hv, e0);
-#pragma unroll
-            for (int s = 0; s < S; ++s) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
-          }
+          decSteps<false, S>(chains, lut, mask, pb, hv, segLane, grp * int(dec::kUnroll), 0, l, 0u);
         }
         __builtin_amdgcn_wave_barrier();
         join(g, true, cur, dcur);

@@ -1,9 +1,10 @@
 // Row gather kernel for gfx950: rows of a [R, rowWords]
 // table stored as one archive, each named by an index in device memory.
 //
-// A new outer loop around k_decode's block body (decode.h): buildLut64,
-// DStream and its ring, the phase-ordered step, Join<FT>::vec / one and the
-// range form's edge rules are used as they are.  What differs:
+// A new outer loop around k_decode's block body (decode.h): openArchive,
+// buildLut64, bindStream / openHalf, ringEnsure, decSteps, the chunk join (loadChunkSyms,
+// Join<FT>::vec, joinWords) and the range form's edge rule (clipChunk) are
+// k_decode's own.  What this file holds is what differs:
 //  * one persistent grid: a workgroup validates the headers and builds the
 //    decode table once, then strides over groups of 8 tasks;
 //  * a task (the j-th block of the row that index i names) belongs to a
@@ -12,7 +13,8 @@
 //    destination are wave-uniform per half, as uwH[2] and DStream::ptr[2] are
 //    in k_decode; lanes select theirs by their half;
 //  * the indices of the next pass are read a pass ahead; nothing comes from
-//    the host but the kernel arguments.
+//    the host but the kernel arguments;
+//  * a status per row, not per element.
 #pragma once
 
 #include "decode.h"
@@ -41,27 +43,11 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 
   const uint32_t tid = threadIdx.x;
   gp<const uint8_t> base = G(archive);
-  gp<const uint32_t> fh = (gp<const uint32_t>)base;
 
   // the headers, once per workgroup (k_decode's checks)
   gp<const uint8_t> arch[S];
-  uint32_t n;
   bool ok;
-  if constexpr (FT == 0) {
-    n = fh[kAnsSize];
-    ok = fh[kAnsMagic] == kANSMagicVersion;
-  } else {
-    n = fh[kFloatSize];
-    ok = fh[kFloatMagic] == kFloatMagicVersion && (fh[kFloatType] & kTypeMask) == uint32_t(FT);
-  }
-  arch[0] = ansArchiveOf<FT>(base, n);
-  if constexpr (S == 2) arch[S - 1] = arch[0] + fh[kFloatSecondAns];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    gp<const uint32_t> ah = (gp<const uint32_t>)arch[s];
-    ok = ok && ah[kAnsMagic] == kANSMagicVersion && (ah[kAnsPrecision] & kTypeMask) == uint32_t(pb) &&
-         ah[kAnsSize] == n;
-  }
+  const uint32_t n = openArchive<FT>(base, pb, ok, arch);
   // whole rows of the element; 0: every index fails (the loop below then only
   // writes the statuses)
   const uint32_t nRows = ok ? n / rowWords : 0u;
@@ -70,8 +56,7 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
   const uint32_t groups = total / kGatherTasksPerWG + (total % kGatherTasksPerWG != 0);
 
   const uint32_t w = readfirst(tid >> 6), lane = tid & 63, l = lane & 31;
-  uint32_t hv = lane >= 32 ? ~0u : 0u;
-  asm volatile("" : "+v"(hv));  // keep `hv & x` a v_and (not a v_cndmask pair)
+  const uint32_t hv = upperHalfMask(lane);
   const bool vecIn = (reinterpret_cast<uintptr_t>(archive) & 15) == 0;
   gp<const uint8_t> raw = rawSectionOf(base);
   const uint32_t mask = (1u << pb) - 1;
@@ -169,46 +154,15 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
 
     DStream st[S];
     lp<uint16_t> segLane[S];
+    DStream* chains[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       gp<const uint16_t> data = AnsSections(arch[s], nBlocks).words;
-      DStream& d = st[s];
-      const uint32_t hs = w * S + s;  // half-stream pair index
-      d.ring = ringAll + hs * 2 * dec::kRing;
-      d.ringLane = d.ring + (hv & dec::kRing);
-      segLane[s] = segAll + hs * 2 * dec::kSegWords + (hv & dec::kSegWords) + l;
+      bindStream(st[s], segLane[s], ringAll, segAll, w * S + s, hv, l);
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        d.ptr[hh] = 0;
-        d.lo[hh] = 0;
-        d.data[hh] = data;
-        d.pf[hh] = u32x2{0, 0};
-        if (uwH[hh]) {
-          const uint2 e = bwE[s][hh];
-          const uint32_t ex = readfirst(e.x), ey = readfirst(e.y);  // wave-uniform: SGPRs
-          const int32_t cw = int32_t(ex & 0xffffu);
-          d.ptr[hh] = cw;
-          d.data[hh] = data + ey;
-          const int32_t lo = cw > int32_t(dec::kRing) ? int32_t(roundUp(uint32_t(cw) - dec::kRing, dec::kWPL)) : 0;
-          d.lo[hh] = lo;
-          // initial fill of [lo, cw), as k_decode's
-#pragma unroll
-          for (int q = 0; q < int(dec::kRing / dec::kRefill); ++q) {
-            const int32_t a = lo + q * int32_t(dec::kRefill) + int32_t(dec::kWPL * lane);
-            if (a < cw) *(lp<u32x2>)(d.ring + hh * dec::kRing + (a & (dec::kRing - 1))) = ld4w(d.data[hh] + a, vecIn);
-          }
-          ringPrefetch(d, hh, lane, vecIn);
-        }
-      }
-      d.x = x0[s];
-    }
-
-    DStream* chains[S];
-    bool allValid[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
+      for (int hh = 0; hh < 2; ++hh) openHalf(st[s], hh, data, bwE[s][hh], uwH[hh] != 0, lane, vecIn);
+      st[s].x = x0[s];
       chains[s] = &st[s];
-      allValid[s] = true;
     }
 
     // whether this lane's chunk of segment g takes the vector join: whole
@@ -229,66 +183,28 @@ __global__ __launch_bounds__(dec::kThreads) __attribute__((amdgpu_num_sgpr(80), 
       uint32_t rv[R];
       const bool vc = vecChunk(g);
       if (FT != 0 && vc) J::load(rv, raw, n, i0);
-      if (full) {
+      const int32_t tBot = g * int32_t(dec::kSegSteps);
 #pragma unroll
-        for (int sg = int(dec::kSegSteps / dec::kUnroll) - 1; sg >= 0; --sg) {
+      for (int sg = int(dec::kSegSteps / dec::kUnroll) - 1; sg >= 0; --sg) {
 #pragma unroll
-          for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, vecIn);
-#pragma unroll
-          for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
-            const int tr = sg * int(dec::kUnroll) + u;  // step within segment
-            uint32_t e0[S];
-            decStepAll<false, S>(chains, allValid, lut, mask, pb, hv, e0);
-#pragma unroll
-            for (int s = 0; s < S; ++s) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
-          }
-        }
-      } else {
+        for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, vecIn);
         // a partial segment, or a half that idles: masked steps
-        const int32_t tBot = g * int32_t(dec::kSegSteps);
-#pragma unroll
-        for (int sg = int(dec::kSegSteps / dec::kUnroll) - 1; sg >= 0; --sg) {
-#pragma unroll
-          for (int s = 0; s < S; ++s) ringEnsure(st[s], lane, vecIn);
-#pragma unroll
-          for (int u = int(dec::kUnroll) - 1; u >= 0; --u) {
-            const int tr = sg * int(dec::kUnroll) + u;
-            const uint32_t t = uint32_t(tBot + tr);
-            bool vld[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) vld[s] = t * 32 + l < uwM;
-            uint32_t e0[S];
-            decStepAll<true, S>(chains, vld, lut, mask, pb, hv, e0);
-#pragma unroll
-            for (int s = 0; s < S; ++s)
-              if (vld[s]) segLane[s][tr * 32] = uint16_t(e0[s] >> 16);
-          }
-        }
+        if (full) decSteps<false, S>(chains, lut, mask, pb, hv, segLane, sg * int(dec::kUnroll), 0, l, 0u);
+        else decSteps<true, S>(chains, lut, mask, pb, hv, segLane, sg * int(dec::kUnroll), tBot, l, uwM);
       }
       __builtin_amdgcn_wave_barrier();
       // join: words [k0, k1) of the chunk lie in the block and in the row
       if (c0 < uwM) {
-        const uint32_t cnt = min(dec::kChunk, uwM - c0);
-        const uint32_t k0 = i0 < rloM ? min(cnt, rloM - i0) : 0u;
-        const uint32_t k1 = rhiM > i0 ? min(cnt, rhiM - i0) : 0u;
-        if (k0 < k1) {
+        uint32_t k0, k1;
+        if (clipChunk(i0, min(dec::kChunk, uwM - c0), rloM, rhiM, k0, k1)) {
           lp<const uint16_t> q0 = segLane[0] - l + off;
           lp<const uint16_t> q1 = segLane[S - 1] - l + off;
           if (vc) {
             uint32_t sv[4], sv1[4];
-            const u32x4 a0 = *(lp<const u32x4>)q0;
-            sv[0] = a0.x; sv[1] = a0.y; sv[2] = a0.z; sv[3] = a0.w;
-            if constexpr (S == 2) {
-              const u32x4 b0 = *(lp<const u32x4>)q1;
-              sv1[0] = b0.x; sv1[1] = b0.y; sv1[2] = b0.z; sv1[3] = b0.w;
-            } else {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) sv1[k] = 0;
-            }
+            loadChunkSyms<S>(q0, q1, sv, sv1);
             J::template vec<false>(outB, i0, sv, sv1, rv);
           } else {
-            gp<WordT> o = (gp<WordT>)outB;
-            for (uint32_t k = k0; k < k1; ++k) o[i0 + k] = J::one(q0[k] >> 8, q1[k] >> 8, raw, n, i0 + k);
+            joinWords<J>((gp<WordT>)outB, q0, q1, raw, n, i0, k0, k1);
           }
         }
       }

@@ -309,6 +309,76 @@ __global__ __launch_bounds__(kThreads) void k_sparseGather(BatchDesc in, uint32_
 
 // Decompression works on 1024-word chunks (16 bitmap words, one wave).
 constexpr uint32_t kChunkWords = 1024;
+constexpr uint32_t kChunkRows = kChunkWords / 64;  // 64-word rows, one bitmap word each
+
+// The set bits of chunk c of the bitmap bm of an N-word element: the popcount
+// of its 128 bitmap bytes, bits at or past N cut (the bitmap's padding is the
+// reference's uninitialised bytes); 0 for a chunk at or past N.  Words are
+// counted from the chunk's start, which cannot wrap (c < 2^22 + 256).  The
+// 128 B read may run past the padded bitmap into the dense archive that
+// follows it (>= 576 B), never past the archive.
+__device__ __forceinline__ uint32_t chunkPopcount(gp<const uint8_t> bm, uint32_t c, uint32_t n) {
+  if (uint64_t(c) * kChunkWords >= n) return 0;
+  const uint32_t left = n - c * kChunkWords;  // the element's words from the chunk's start on
+  gp<const uint64_t> bw = (gp<const uint64_t>)bm + uint64_t(c) * kChunkRows;
+  uint64_t v[kChunkRows];
+#pragma unroll
+  for (uint32_t k = 0; k < kChunkRows; ++k) v[k] = left > 64 * k ? bw[k] : 0ull;
+  uint32_t cnt = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kChunkRows; ++k) {
+    uint64_t m = v[k];
+    const uint32_t rem = left - 64 * k;  // (used only when the word was loaded)
+    if (left > 64 * k && rem < 64) m = maskToBitmap(m) & ((1ull << rem) - 1);  // element order, tail cut
+    cnt += uint32_t(__popcll(m));
+  }
+  return cnt;
+}
+
+// gap: x[N-1] is read from idx[N-2] + 1 (fill_in_nonzeros :139-144), one list
+// slot further than its rank, when bit N-2 of the bitmap is clear.
+__device__ __forceinline__ bool gapBit(gp<const uint8_t> bm, uint32_t n) {
+  return n >= 2 && ((bm[(n - 2) / 8] >> (7 - (n - 2) % 8)) & 1) == 0;
+}
+
+// This lane's share of the totals of the counting workgroups before g (tot:
+// the archive's blockTot entries): one load per lane up to 64 workgroups,
+// i.e. 16 M words.  waveSum of the shares is the list offset of chunk 256 g.
+__device__ __forceinline__ uint32_t totalsShare(gp<const uint32_t> tot, uint32_t g, uint32_t lane) {
+  uint32_t part = 0;
+  for (uint32_t k0 = 0; k0 < g; k0 += 64) part += k0 + lane < g ? tot[k0 + lane] : 0u;
+  return part;
+}
+
+// Chunk c's list offset (wave-uniform c): its count prefix within its counting
+// workgroup (pre: the archive's chunkPre entries) plus the totals of the
+// earlier workgroups.
+__device__ __forceinline__ uint32_t chunkListOffset(gp<const uint32_t> pre, gp<const uint32_t> tot, uint32_t c,
+                                                    uint32_t lane) {
+  return readfirst(pre[c]) + waveSum(totalsShare(tot, c / kThreads, lane));
+}
+
+// A chunk's 16 rows of 64 words, one wave: mv holds the rows' bitmap words in
+// lanes 0-15, base is the chunk's list offset.  For each row the mask comes
+// to SGPRs (readlane), each lane's list index is the running offset + v_mbcnt
+// of the mask (+ 1 for word N-1 behind a gap), and all 16 rows' list gathers
+// are issued back to back (their addresses depend only on the bitmap) for the
+// caller's 16 row stores.  v[j] = word i0 + 64 j + lane of the element, 0
+// where its bit is clear or wanted(i) is false (that word is not read).
+template <class W, class Wanted>
+__device__ __forceinline__ void expandRows(uint64_t mv, uint32_t base, uint32_t i0, uint32_t n, bool gap,
+                                           gp<const W> list, uint32_t lane, Wanted wanted, W (&v)[kChunkRows]) {
+#pragma unroll
+  for (uint32_t j = 0; j < kChunkRows; ++j) {
+    const uint64_t m = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv >> 32)), int(j)))) << 32) |
+                       uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv)), int(j)));
+    const uint32_t i = i0 + 64 * j + lane;
+    uint32_t src = base + mbcnt(m);
+    if (gap && i + 1 == n) src += 1;
+    v[j] = wanted(i) && ((m >> lane) & 1) ? list[src] : W(0);
+    base += uint32_t(__popcll(m));
+  }
+}
 
 // d1: one thread per chunk: the popcount of its 128 bitmap bytes (bits past
 // N masked: the bitmap's padding is the reference's uninitialised bytes),
@@ -318,9 +388,7 @@ constexpr uint32_t kChunkWords = 1024;
 // (ceil(chunks / 256), batch).  The expansion adds the earlier workgroups'
 // totals itself (k_sparseExpand), so no scan launch or cross-workgroup
 // hand-off follows (a separate one-workgroup-per-element scan launch: 1 x 15M
-// fp32 decompress 5.8 us more).  A chunk's 128 B read may run past the padded
-// bitmap into the dense archive that follows it (>= 576 B), never past the
-// archive.
+// fp32 decompress 5.8 us more).
 __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_t batchOffset,
                                                            uint32_t chunksPerElem, uint32_t blocksPerElem,
                                                            uint64_t* __restrict__ densePtrs,
@@ -336,21 +404,7 @@ __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_
     densePtrs[b] = reinterpret_cast<uint64_t>(in.start(b) + sparsePrefixBytes(n));
     sizes[b] = n;
   }
-  uint32_t cnt = 0;
-  const uint32_t i0 = c * kChunkWords;
-  if (c < chunksPerElem && i0 < n) {
-    gp<const uint64_t> bm = (gp<const uint64_t>)(a + kSparseHeaderBytes) + uint64_t(c) * (kChunkWords / 64);
-    uint64_t v[kChunkWords / 64];
-#pragma unroll
-    for (uint32_t k = 0; k < kChunkWords / 64; ++k) v[k] = i0 + 64 * k < n ? bm[k] : 0ull;
-#pragma unroll
-    for (uint32_t k = 0; k < kChunkWords / 64; ++k) {
-      const uint32_t e = i0 + 64 * k;
-      uint64_t m = v[k];
-      if (e < n && n - e < 64) m = maskToBitmap(m) & ((1ull << (n - e)) - 1);  // element order, tail cut
-      cnt += uint32_t(__popcll(m));
-    }
-  }
+  const uint32_t cnt = c < chunksPerElem ? chunkPopcount(a + kSparseHeaderBytes, c, n) : 0u;
   uint32_t total = 0;
   const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
   if (c < chunksPerElem) chunkPre[uint64_t(b) * chunksPerElem + c] = excl;
@@ -360,13 +414,11 @@ __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_
 // d3: expand the decoded nonzero list into the output (fill_in_nonzeros
 // :95-144).  One wave per 1024-word chunk (grid (ceil(chunks / 4), batch)),
 // no LDS and no barrier: lanes 0-15 load the chunk's 16 bitmap words
-// beside its list offset (the scanned chunk count), then for each 64-word
-// row the row's mask comes to SGPRs (readlane), each lane's list index is
-// offset + v_mbcnt of the mask, and all 16 rows' list gathers are issued
-// back to back (their addresses depend only on the bitmap) before the 16
-// row stores.  (The tile-per-workgroup kernel it replaces summed every
-// earlier tile's count per tile and staged through LDS: 5 x 15M fp32 at
-// 50 % zeros 176 us, fp64 430 us.)
+// beside its list offset (the scanned chunk count, loaded in the bitmap's
+// round trip), then expandRows and the 16 row stores.  (The
+// tile-per-workgroup kernel it replaces summed every earlier tile's count per
+// tile and staged through LDS: 5 x 15M fp32 at 50 % zeros 176 us, fp64
+// 430 us.)
 template <int FT>
 __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDesc out, uint32_t batchOffset,
                                                            uint32_t chunksPerElem, uint32_t blocksPerElem,
@@ -377,7 +429,6 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
                                                            uint8_t* __restrict__ outSuccess,
                                                            uint32_t* __restrict__ outSize) {
   using W = WordOf<FT>;
-  constexpr uint32_t kRows = kChunkWords / 64;
   const uint32_t b = batchOffset + blockIdx.y;
   const uint32_t n = sizes[b];
   const bool ok = denseOk[b] != 0 && out.size(b) >= n;
@@ -391,38 +442,20 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   if (!ok || c >= chunksPerElem || i0 >= n) return;
   gp<const uint8_t> bm = (gp<const uint8_t>)in.start(b) + kSparseHeaderBytes;
   uint64_t mv = 0;
-  if (lane < kRows && i0 + 64 * lane < n) {
+  if (lane < kChunkRows && i0 + 64 * lane < n) {
     mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
     const uint32_t rem = n - (i0 + 64 * lane);
     if (rem < 64) mv &= (1ull << rem) - 1;
   }
-  // the chunk's list offset: its count prefix within its k_sparseChunks
-  // workgroup plus the totals of the element's earlier workgroups, loaded
-  // in the bitmap's round trip (one load per lane up to 64 workgroups, i.e.
-  // 16 M words)
-  const uint32_t g = c / kThreads;
-  uint32_t part = 0;
-  for (uint32_t k0 = 0; k0 < g; k0 += 64)
-    part += k0 + lane < g ? G(blockTot)[uint64_t(b) * blocksPerElem + k0 + lane] : 0u;
-  uint32_t base = readfirst(G(chunkPre)[uint64_t(b) * chunksPerElem + c]) + waveSum(part);
-  // x[n-1] is read from idx[n-2] + 1 (fill_in_nonzeros :139-144): only the
-  // chunk holding word n-1 looks
-  const bool gap = n >= 2 && n - 1 - i0 < kChunkWords && ((bm[(n - 2) / 8] >> (7 - (n - 2) % 8)) & 1) == 0;
-  gp<const W> list = (gp<const W>)lists.start(b);
-  W v[kRows];
-#pragma unroll
-  for (uint32_t j = 0; j < kRows; ++j) {
-    const uint64_t m = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv >> 32)), int(j)))) << 32) |
-                       uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv)), int(j)));
-    const uint32_t i = i0 + 64 * j + lane;
-    uint32_t src = base + mbcnt(m);
-    if (gap && i + 1 == n) src += 1;
-    v[j] = (m >> lane) & 1 ? list[src] : W(0);
-    base += uint32_t(__popcll(m));
-  }
+  const uint32_t base = chunkListOffset(G(chunkPre) + uint64_t(b) * chunksPerElem,
+                                        G(blockTot) + uint64_t(b) * blocksPerElem, c, lane);
+  // only the chunk holding word n-1 looks
+  const bool gap = n - 1 - i0 < kChunkWords && gapBit(bm, n);
+  W v[kChunkRows];
+  expandRows(mv, base, i0, n, gap, (gp<const W>)lists.start(b), lane, [](uint32_t) { return true; }, v);
   gp<W> y = (gp<W>)out.start(b);
 #pragma unroll
-  for (uint32_t j = 0; j < kRows; ++j) {
+  for (uint32_t j = 0; j < kChunkRows; ++j) {
     const uint32_t i = i0 + 64 * j + lane;
     // streaming: nothing here re-reads the output
     if (i < n) __builtin_nontemporal_store(v[j], y + i);
@@ -624,21 +657,7 @@ __global__ __launch_bounds__(kThreads) void k_sparseRangeChunks(SparseRangeTabs 
   const uint32_t n = sparseSizeOf(a, hdrOk);
   if (uint64_t(blockIdx.x) * kThreads * kChunkWords >= n) return;
   const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  uint32_t cnt = 0;
-  const uint32_t i0 = c * kChunkWords;  // (c < 2^22 + 256: no wrap)
-  if (c < nChunks && uint64_t(c) * kChunkWords < n) {
-    gp<const uint64_t> bm = (gp<const uint64_t>)(a + kSparseHeaderBytes) + uint64_t(c) * (kChunkWords / 64);
-    uint64_t v[kChunkWords / 64];
-#pragma unroll
-    for (uint32_t k = 0; k < kChunkWords / 64; ++k) v[k] = n - i0 > 64 * k ? bm[k] : 0ull;
-#pragma unroll
-    for (uint32_t k = 0; k < kChunkWords / 64; ++k) {
-      uint64_t m = v[k];
-      const uint32_t rem = n - i0 - 64 * k;  // (used only when the word was loaded)
-      if (n - i0 > 64 * k && rem < 64) m = maskToBitmap(m) & ((1ull << rem) - 1);  // element order, tail cut
-      cnt += uint32_t(__popcll(m));
-    }
-  }
+  const uint32_t cnt = c < nChunks ? chunkPopcount(a + kSparseHeaderBytes, c, n) : 0u;
   uint32_t total = 0;
   const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
   const uint64_t g = uint64_t(g0) + blockIdx.x;
@@ -655,9 +674,7 @@ __device__ __forceinline__ uint32_t rankShare(gp<const uint8_t> bm, gp<const uin
                                               gp<const uint32_t> blockTot, uint32_t i, uint32_t lane) {
   const uint32_t c = (i - 1) / kChunkWords;
   const uint32_t within = i - c * kChunkWords;  // 1 .. 1024 words of chunk c lie below i
-  const uint32_t g = c / kThreads;
-  uint32_t part = 0;
-  for (uint32_t k0 = 0; k0 < g; k0 += 64) part += k0 + lane < g ? blockTot[k0 + lane] : 0u;
+  uint32_t part = totalsShare(blockTot, c / kThreads, lane);
   if (lane == 16) part += chunkPre[c];
   if (lane < kChunkWords / 64 && 64 * lane < within) {
     uint64_t m = maskToBitmap(*(gp<const uint64_t>)(bm + uint64_t(c) * (kChunkWords / 8) + 8 * lane));
@@ -699,7 +716,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
     gp<const uint8_t> bm = a + kSparseHeaderBytes;
     gp<const uint32_t> pre = G(chunkPre) + uint64_t(uint32_t(info)) * kThreads;
     gp<const uint32_t> tot = G(blockTot) + uint32_t(info);
-    gap = n >= 2 && ((bm[(n - 2) / 8] >> (7 - (n - 2) % 8)) & 1) == 0;
+    gap = gapBit(bm, n);
     const uint32_t s0 = first ? rankShare(bm, pre, tot, first, lane) : 0u;
     const uint32_t s1 = rankShare(bm, pre, tot, end, lane);
     lf = waveSum(s0);
@@ -714,13 +731,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
   }
 }
 
-// r4: expand the decoded list slices into the outputs, built like
-// k_sparseExpand: one wave per 1024-word chunk the range touches (grid
+// r4: expand the decoded list slices into the outputs, k_sparseExpand's body
+// (expandRows): one wave per 1024-word chunk the range touches (grid
 // (ceil((ceil(maxCount / 1024) + 1) / 4), members): a range's start inside a
-// chunk is arbitrary), 16 bitmap words in lanes 0-15, a row's mask per
-// readlane, list index = the chunk's rank - listFirst + v_mbcnt (modulo 2^32:
-// the first chunk's rank lies at or below listFirst), every gather issued
-// before the stores; no LDS, no barrier.  Rows are masked to [first, end);
+// chunk is arbitrary), 16 bitmap words in lanes 0-15, list offset = the
+// chunk's rank - listFirst (modulo 2^32: the first chunk's rank lies at or
+// below listFirst); no LDS, no barrier.  Rows are masked to [first, end);
 // word i goes to out[i - first] with plain stores (the destination is not
 // row-aligned and is read right after).  Members that failed return before
 // any index is formed: for the others every index lies in [0, listCount) by
@@ -734,7 +750,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
     const uint8_t* __restrict__ flags, BatchDesc lists, const uint8_t* __restrict__ denseOk,
     uint8_t* __restrict__ outSuccess, uint32_t* __restrict__ outSize) {
   using W = WordOf<FT>;
-  constexpr uint32_t kRows = kChunkWords / 64;
   const uint32_t b = batchOffset + blockIdx.y;
   const uint32_t count = BatchDesc::tableAt(t.count, b);
   const uint32_t fl = flags[b];
@@ -755,38 +770,26 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
   gp<const uint8_t> a = (gp<const uint8_t>)reinterpret_cast<const uint8_t*>(BatchDesc::tableAt(t.archPtr, slot));
   gp<const uint8_t> bm = a + kSparseHeaderBytes;
   uint64_t mv = 0;
-  if (lane < kRows && 64 * lane < end - i0) mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
-  // the chunk's rank, as k_sparseExpand sums it, less the slice's start
-  gp<const uint32_t> tot = G(blockTot) + uint32_t(info);
-  const uint32_t g = c / kThreads;
-  uint32_t part = 0;
-  for (uint32_t k0 = 0; k0 < g; k0 += 64) part += k0 + lane < g ? tot[k0 + lane] : 0u;
-  uint32_t base = readfirst(G(chunkPre)[uint64_t(uint32_t(info)) * kThreads + c]) + waveSum(part) -
-                  BatchDesc::tableAt(listFirst, b);
+  if (lane < kChunkRows && 64 * lane < end - i0) mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
+  // the chunk's rank less the slice's start
+  const uint32_t base = chunkListOffset(G(chunkPre) + uint64_t(uint32_t(info)) * kThreads,
+                                        G(blockTot) + uint32_t(info), c, lane) -
+                        BatchDesc::tableAt(listFirst, b);
   // x[N-1] is read one slot further when x[N-2] == 0: only a range that ends
   // at N reaches it
   const uint32_t n = ((gp<const uint32_t>)a)[kSparseSize];
   const bool gap = (fl & 2) != 0;
-  gp<const W> list = (gp<const W>)lists.start(b);
-  W v[kRows];
-#pragma unroll
-  for (uint32_t j = 0; j < kRows; ++j) {
-    const uint64_t m = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv >> 32)), int(j)))) << 32) |
-                       uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv)), int(j)));
-    const uint32_t i = i0 + 64 * j + lane;
-    uint32_t src = base + mbcnt(m);
-    if (gap && i + 1 == n) src += 1;
-    // (i0 + 1023 may wrap past 2^32 - 1 in the last chunk of a 2^32-word
-    // element: compare offsets from i0, which do not)
-    const bool in = i - i0 < end - i0 && i >= first;
-    v[j] = in && ((m >> lane) & 1) ? list[src] : W(0);
-    base += uint32_t(__popcll(m));
-  }
+  // rows are masked to [first, end).  (i0 + 1023 may wrap past 2^32 - 1 in
+  // the last chunk of a 2^32-word element: compare offsets from i0, which do
+  // not)
+  auto inRange = [&](uint32_t i) __attribute__((always_inline)) { return i - i0 < end - i0 && i >= first; };
+  W v[kChunkRows];
+  expandRows(mv, base, i0, n, gap, (gp<const W>)lists.start(b), lane, inRange, v);
   gp<W> y = (gp<W>)out.start(b);
 #pragma unroll
-  for (uint32_t j = 0; j < kRows; ++j) {
+  for (uint32_t j = 0; j < kChunkRows; ++j) {
     const uint32_t i = i0 + 64 * j + lane;
-    if (i - i0 < end - i0 && i >= first) y[i - first] = v[j];
+    if (inRange(i)) y[i - first] = v[j];
   }
 }
 
