@@ -125,7 +125,8 @@ def testlib():
                "dietgpu_test_enc_magic": (c_int, [P, P]),
                "dietgpu_test_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
-               "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P])}
+               "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
+               "dietgpu_test_compress_plan": (c_int, [c_int, c_u32, c_u32, c_int, c_int, c_int, P])}
         for name, (res, args) in sig.items():
             f = getattr(T, name)
             f.restype = res

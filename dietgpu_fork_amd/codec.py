@@ -55,6 +55,32 @@ def test_enc_magic(device="cuda"):
     return m.cpu().to(torch.int64) & 0xffffffff
 
 
+# csrc/compress_plan.h: Refused, HistKernel, Normalise
+PLAN_REFUSED = ("", "two-segments", "user-hist", "unaligned", "forced", "too-large", "size-rule")
+PLAN_HIST = ("plain", "checksum", "rows")
+PLAN_NORMALISE = ("caller", "prologue", "in-hist", "in-reduce", "kernel")
+_PLAN_FIELDS = ("single_pass", "refused", "team", "too_many_items", "rounds", "teams_per_round", "xcd", "grid",
+                "max_r", "items", "chunk_words", "chunks", "groups", "run_hist", "raw_ck", "hist", "normalise",
+                "encode_wgs", "encode_runs", "coalesce_from_flags")
+
+
+def test_compress_plan(ft, nb, max_size, checksum=False, user_hist=False, aligned16=True):
+    """Test hook (libdietgpu_testhooks.so): the plan (dietgpu_test_plan, as a
+    dict with the enumerations named) the dense compress driver computes on
+    this device in the current compress-path mode for nb elements of at most
+    max_size bytes (ft 0) or words (ft 1..4)."""
+    import ctypes
+
+    out = (ctypes.c_uint32 * len(_PLAN_FIELDS))()
+    N.test_check(N.testlib().dietgpu_test_compress_plan(int(ft), int(nb), int(max_size), int(checksum),
+                                                        int(user_hist), int(aligned16), out))
+    plan = dict(zip(_PLAN_FIELDS, out))
+    plan["refused"] = PLAN_REFUSED[plan["refused"]]
+    plan["hist"] = PLAN_HIST[plan["hist"]]
+    plan["normalise"] = PLAN_NORMALISE[plan["normalise"]]
+    return plan
+
+
 def max_compressed_size(nbytes):
     return N.size_or_raise(N.lib().dietgpu_get_max_compressed_size(int(nbytes)))
 

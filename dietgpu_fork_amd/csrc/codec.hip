@@ -6,10 +6,10 @@
 //
 // Launch sequence per call (all stream-ordered, no host sync unless a
 // checksum has to be verified):
-//   compress:   k_pcompress (single pass, compressPersistent) when
-//               encodeBatchDevice's rule prefers it, else
-//               k_hist -> k_normalize -> k_encode (+ k_coalesce for fp64)
-//               (compressThreeKernel)
+//   compress:   k_pcompress (single pass, compressPersistent) or
+//               k_hist -> a normalisation route -> k_encode (+ k_coalesce
+//               for fp64) (compressThreeKernel), as planCompress
+//               (compress_plan.h) decides: DESIGN.md 5.1c
 //   decompress: k_decode (table build + rANS decode + float join fused)
 #include <algorithm>
 #include <cstdlib>
@@ -31,41 +31,18 @@
 namespace dietgpu {
 
 namespace {
-// k_hist chunk (words): 4 K .. 64 K words, halved while the batch has fewer
-// than 2,048 chunks -- for single-segment formats only down to 16 K words
-// once there are 512: a k_hist workgroup zeroes and sums 32 KB of LDS
-// counters, which 4 K- or 8 K-word chunks do not amortise (1 x 16M bf16
-// compress 41.6 -> 37.0 us, fp32 48.2 -> 46.3 us, same box; 1e8-word
-// elements keep their 32 K-word chunks, 64 K measured slower).  fp64's two
-// 16-column counter sets keep the 2,048 rule.
-uint32_t histChunkWords(uint32_t nb, uint32_t maxSize, int segs) {
-  uint32_t chunk = 64 * 1024;
-  auto enough = [&](uint32_t c) {
-    const uint64_t total = uint64_t(nb) * divUp(std::max(maxSize, 1u), c);
-    return total >= 2048 || (segs == 1 && c <= 16 * 1024 && total >= 512);
-  };
-  while (chunk > 4096 && !enough(chunk)) chunk /= 2;
-  while (divUp(maxSize, chunk) > 4096) chunk *= 2;
-  return chunk;
+// workgroups of `kernel` resident on the whole device `dev` at once
+uint32_t occupancySlots(int dev, const void* kernel, int threads, uint32_t dynLds) {
+  int cus = 0, perCU = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, dynLds));
+  return uint32_t(std::max(1, cus) * std::max(1, perCU));
 }
 
-// workgroups of `kernel` resident on the whole device at once (cached per
-// device, kernel and LDS size)
+// ... of the current device (cached per device, kernel and LDS size)
 uint32_t residentSlots(const void* kernel, int threads, uint32_t dynLds) {
-  return cachedPerDevice<uint32_t>(std::make_tuple(kernel, threads, dynLds), [&](int dev) {
-    int cus = 0, perCU = 0;
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, dynLds));
-    return uint32_t(std::max(1, cus) * std::max(1, perCU));
-  });
-}
-
-uint32_t residentCUs() {
-  return cachedPerDevice<uint32_t>(0, [](int dev) {
-    int cus = 0;
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return uint32_t(std::max(1, cus));
-  });
+  return cachedPerDevice<uint32_t>(std::make_tuple(kernel, threads, dynLds),
+                                   [&](int dev) { return occupancySlots(dev, kernel, threads, dynLds); });
 }
 
 void checkProbBits(int pb) {
@@ -115,64 +92,56 @@ static void launchChecksum(const BatchDesc& in, uint32_t y0, uint32_t ny, uint32
   HIP_LAUNCH_CHECK();
 }
 
-// Single-pass compression (k_pcompress, pcompress.h) for single-segment
-// formats without a caller-supplied histogram, elements of at most
-// pc::kMaxTeam items (1 MiB of symbols).  One generation of resident
-// workgroups pulls items off the work queue.
-// Teams of k_pcompress for nb elements of maxWords: team size, teams per
-// round (XCD-aligned when that fits, see compressPersistent) and whether
-// they are XCD-aligned.  team == 0: the elements are too large.
-struct PersistentPlan {
-  uint32_t team = 0, teamsPerRound = 0, rounds = 0;
-  bool xcd = false;
-};
-
+// What the compress rule needs to know of the device: the resident workgroups
+// of k_pcompress (its instances have the same resources: one occupancy query)
+// and of k_encode's prologue instance, and the CUs (cached per device).
 template <int FT>
-PersistentPlan planPersistent(uint32_t nb, uint32_t maxWords) {
-  PersistentPlan p;
-  const uint32_t team = std::max(1u, divUp(divUp(maxWords, kBlockSize), pc::kBlocksPerItem));
-  if (team > pc::kMaxTeam || nb == 0) return p;
-  // (the instances have the same resources: one occupancy query)
-  const uint32_t slots = residentSlots(reinterpret_cast<const void*>(&k_pcompress<FT, false, true>), pc::kThreads, 0);
-  // rounds of whole teams, balanced: R rounds of ceil(nb / R) teams
-  const uint32_t maxTeams = std::max(1u, slots / team);
-  p.team = team;
-  p.rounds = divUp(nb, maxTeams);
-  p.teamsPerRound = divUp(nb, p.rounds);
-  // XCD-aligned teams (kXcd, pcompress.h) whenever the teams per round round
-  // up to a multiple of 8 within the resident grid (never more rounds; a
-  // batch of fewer than 8 elements gets idle teams that exit at once), so
-  // the partial histograms stay in one L2.  Otherwise (e.g. 33 elements of
-  // 31 items in 1,024 slots) the team members span XCDs and the partials go
-  // out write-through.
-  p.xcd = roundUp(p.teamsPerRound, 8) <= maxTeams;
-  if (p.xcd) p.teamsPerRound = roundUp(p.teamsPerRound, 8);
-  return p;
+CompressShape deviceShape() {
+  return cachedPerDevice<CompressShape>(0, [](int dev) {
+    CompressShape sh;
+    int cus = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    sh.cus = uint32_t(std::max(1, cus));
+    if constexpr (FloatTraits<FT>::kSegs == 1)
+      sh.pcompressSlots =
+          occupancySlots(dev, reinterpret_cast<const void*>(&k_pcompress<FT, false, true>), pc::kThreads, 0);
+    sh.encodeProSlots = occupancySlots(dev, reinterpret_cast<const void*>(&k_encode<FT, true>), enc::kThreads, 0);
+    return sh;
+  });
 }
 
-// Whether the single-pass compressor beats the three-kernel path (k_hist ->
-// k_encode with prologue normalisation) for a batch.  At most 256 items, or
-// one round whose teams cannot be XCD-aligned, leave most of the chip idle
-// while a team's members wait on each other's partial histograms; there the
-// chip-wide histogram pass plus the encoder are faster (round 5, bf16:
-// 1 x 1e6 words 30.7 -> 22.9 us, 8 x 524288 26.9 -> 25.1 us, 33 x 1e6
-// 48.9 -> 46.9 us; 16 x 1e6, 496 items, stays single-pass: 33.5 against
-// 37.1 us).
-// (dietgpu_set_compress_path overrides the rule: test hook.)
+// The plan (compress_plan.h) of a compress call on the
+// current device, in the current compressPath() mode.
 template <int FT>
-bool persistentPreferred(uint32_t nb, uint32_t maxWords) {
-  const int mode = compressPath();
-  if (mode == 2) return false;
-  const PersistentPlan p = planPersistent<FT>(nb, maxWords);
-  if (p.team == 0) return false;
-  if (mode == 1) return true;
-  if (uint64_t(p.team) * nb <= 256) return false;
-  return !(p.rounds == 1 && !p.xcd);
+CompressPlan planCall(uint32_t nb, uint32_t maxSize, bool useChecksum, bool userHist, const PartialHist* pre,
+                      bool inAligned16) {
+  CompressShape sh = deviceShape<FT>();
+  sh.segs = FloatTraits<FT>::kSegs;
+  sh.byteCodec = FT == 0;
+  sh.nb = nb;
+  sh.maxSize = maxSize;
+  sh.useChecksum = useChecksum;
+  sh.userHist = userHist;
+  sh.pre = !pre ? PreHist::kNone : pre->table ? PreHist::kRowsAndTable : PreHist::kRows;
+  sh.preRows = pre ? pre->nRows : 0;
+  sh.inAligned16 = inAligned16;
+  sh.mode = compressPath();
+  return planCompress(sh);
 }
-template bool persistentPreferred<1>(uint32_t, uint32_t);
-template bool persistentPreferred<2>(uint32_t, uint32_t);
-template bool persistentPreferred<3>(uint32_t, uint32_t);
 
+CompressPlan planCompressCall(int ft, uint32_t nb, uint32_t maxSize, bool useChecksum, bool userHist,
+                              bool inAligned16) {
+  DG_CHECK(ft >= 0 && ft <= 4 && nb >= 1, "float type 0..4 and at least one element");
+  DG_CHECK(!userHist || ft == 0, "only the byte codec takes a histogram");
+  if (ft == 0) return planCall<0>(nb, maxSize, useChecksum, userHist, nullptr, inAligned16);
+  return dispatchFloatType(FloatType(ft), [&](auto t) {
+    return planCall<decltype(t)::value>(nb, maxSize, useChecksum, false, nullptr, inAligned16);
+  });
+}
+
+// Single-pass compression (k_pcompress, pcompress.h): one generation of
+// resident workgroups, plan.teamsPerRound teams of plan.team, pulls items off
+// the work queue.
 template <int FT, bool kCk, bool kXcd>
 void launchPersistent(uint32_t grid, hipStream_t s, const DeviceTables* tabs, const BatchDesc& in,
                       const BatchDesc& out, const PCompArgs& a) {
@@ -181,35 +150,23 @@ void launchPersistent(uint32_t grid, hipStream_t s, const DeviceTables* tabs, co
 }
 
 template <int FT, bool kCk>
-bool compressPersistent(const CompressCall& c) {
+void compressPersistent(const CompressCall& c, const CompressPlan& plan) {
   StackDeviceMemory& res = c.res;
   const hipStream_t s = c.s;
   const uint32_t nb = c.nb;
   const bool floatCk = FT != 0 && c.useChecksum;
-  const PersistentPlan plan = planPersistent<FT>(nb, c.maxSize);
-  const uint32_t team = plan.team;
-  if (team == 0) return false;
-  const uint64_t items64 = uint64_t(team) * nb;
-  DG_CHECK(items64 < (1ull << 30), "batch too large for one compress call");
-  const uint32_t items = uint32_t(items64);
-  const bool xcdTeams = plan.xcd;
-  const uint32_t grid = plan.teamsPerRound * team;
+  DG_CHECK(!plan.tooManyItems, "batch too large for one compress call");
 
-  auto slotMem = res.alloc<uint8_t>(s, size_t(grid) * pc::kBlocksPerItem * kSlotDataBytes);
-  auto ck = res.alloc<uint32_t>(s, floatCk ? nb : 1);
+  auto slotMem = res.alloc<uint8_t>(s, size_t(plan.spillSlots) * kSlotDataBytes);
+  auto ck = res.alloc<uint32_t>(s, plan.floatCkWords);
   DeviceDescs dd(res, s, floatCk ? c.tabs : nullptr, nb);  // k_checksum's view
   // epoch-tagged state in this stream's persistent arena (no per-call
   // zeroing), one region per kind of word: the dequeue counters (at a fixed
   // place: a call zeroes the next call's), the look-back flags, the tagged
   // partial histograms then the tagged partial byte checksums, the per-team
-  // element log.  A team takes at most maxR rounds (pcompress.h, "Teams and
-  // elements"): twice the static share bounds the log while leaving the
-  // teams below it room for every element.
-  const size_t partBytes = size_t(items) * kNumSymbols * 4;
-  const uint32_t teams = grid / team;
-  const uint32_t maxR = 2 * divUp(nb, teams) + 2;
-  const size_t regions[kSyncRegions] = {16, size_t(items) * 8, partBytes + (kCk ? size_t(items) * 4 : 0),
-                                        size_t(teams) * maxR * 8, 0};
+  // element log.
+  const size_t regions[kSyncRegions] = {kSyncCounterBytes, size_t(plan.flagBytes), size_t(plan.partialBytes),
+                                        size_t(plan.logBytes), 0};
   SyncLease lease(res, s, regions, /*dequeue=*/true);
   if (floatCk) {
     zeroAsync(ck.data(), sizeof(uint32_t) * nb, s);
@@ -219,35 +176,35 @@ bool compressPersistent(const CompressCall& c) {
   a.ctr = static_cast<uint64_t*>(lease.base[kSyncCounters]);
   a.flags = static_cast<uint64_t*>(lease.base[kSyncFlags]);
   a.part = static_cast<uint32_t*>(lease.base[kSyncPartials]);
-  a.partCk = kCk ? a.part + size_t(items) * kNumSymbols : nullptr;
+  a.partCk = kCk ? a.part + size_t(plan.items) * kNumSymbols : nullptr;
   a.elog = static_cast<uint64_t*>(lease.base[kSyncLog]);
-  a.maxR = maxR;
-  a.slotSpan = std::max(1u, residentCUs());
+  a.maxR = plan.maxR;
+  a.slotSpan = plan.slotSpan;
   a.err = deviceErrorWord();
   a.slots = slotMem.data();
   a.ckIn = floatCk ? ck.data() : nullptr;
   a.outSize = c.outSize_dev;
   a.sparseN = c.sparseN;
-  a.items = items;
-  a.team = team;
+  a.items = plan.items;
+  a.team = plan.team;
   a.nb = nb;
-  a.grid = grid;
-  a.teams = teams;  // (the kernel divides by nothing but `team`, once per workgroup)
+  a.grid = plan.grid;
+  a.teams = plan.teamsPerRound;  // (the kernel divides by nothing but `team`, once per workgroup)
   a.epoch = lease.epoch;
   a.spinCap = spinCap();
   a.fallbackTicks = barrierBudgetTicks();
   a.pb = c.pb;
   a.useChecksum = c.useChecksum;
   prof::Scope p("compress", s);
-  if (xcdTeams) launchPersistent<FT, kCk, true>(grid, s, c.tabs, c.in, c.out, a);
-  else launchPersistent<FT, kCk, false>(grid, s, c.tabs, c.in, c.out, a);
-  return true;
+  if (plan.xcd) launchPersistent<FT, kCk, true>(plan.grid, s, c.tabs, c.in, c.out, a);
+  else launchPersistent<FT, kCk, false>(plan.grid, s, c.tabs, c.in, c.out, a);
 }
 
 // The three-kernel path: k_hist -> (k_histReduce / k_normalize) -> k_encode
-// (+ k_coalesce for fp64), on plain device tables.
+// (+ k_coalesce for fp64), on plain device tables.  plan.normalise names the
+// route from the histograms to the encode tables.
 template <int FT>
-void compressThreeKernel(const CompressCall& c) {
+void compressThreeKernel(const CompressCall& c, const CompressPlan& plan) {
   StackDeviceMemory& res = c.res;
   const hipStream_t s = c.s;
   const uint32_t nb = c.nb, maxSize = c.maxSize;
@@ -256,69 +213,33 @@ void compressThreeKernel(const CompressCall& c) {
   const PartialHist* const pre = c.pre;
   constexpr int kSegs = FloatTraits<FT>::kSegs;
   constexpr bool kFused = kSegs == 1;  // k_encode writes the archive itself
-  const uint32_t MB = divUp(maxSize, kBlockSize);
-  const bool userHist = FT == 0 && c.hist_dev != nullptr;
-  const bool preHist = FT != 0 && pre != nullptr;  // partial rows counted by the caller
-  const bool preNorm = preHist && pre->table != nullptr;  // ... and normalised
-  const uint32_t chunkWords = histChunkWords(nb, maxSize, kSegs);
-  const uint32_t chunks = preHist ? std::max(1u, pre->nRows) : std::max(1u, divUp(maxSize, chunkWords));
-  const bool runHist = !preHist && (!userHist || useChecksum);
-  const bool rawCk = FT == 0 && useChecksum;
-  const uint32_t nW = std::max(1u, divUp(MB, EncCfg<FT>::kBlocksPerWG));
+  const uint32_t MB = std::max(plan.maxBlocks, 1u);
+  const uint32_t chunks = plan.chunks, groups = plan.groups, nW = plan.encodeWGs;
+  const bool rawCk = plan.rawCk;
+  const Normalise route = plan.normalise;
+  const bool reduce2 = route == Normalise::kInReduce;  // first-level sums (k_histReduce)
   DeviceDescs dd(res, s, c.tabs, nb);
   const BatchDesc in = dd.map(c.in), out = dd.map(c.out);
 
-  // Prologue normalisation (k_encode<.., kPro>, encode.h proNormalize):
-  // when the encode grid is at most two generations of resident workgroups,
-  // k_hist accumulates P = proRowsOf(chunks) rows per (segment, element) with
-  // atomics (in the sync arena) and every encode workgroup normalises its
-  // element itself, instead of a k_histReduce / k_normalize launch.  Not for
-  // byte archives with a checksum (their partial checksums are summed by the
-  // normalisation kernels) nor for caller-supplied histograms, and only while
-  // the rows (double-buffered in the stream's arena, which never shrinks)
-  // stay within kProRowsBudget.
-  constexpr size_t kProRowsBudget = 32ull << 20;
-  const size_t proRowsBytes = size_t(kSegs) * nb * proRowsOf(chunks) * kNumSymbols * 4;
-  const bool pro = runHist && !userHist && !rawCk && MB > 0 && proRowsBytes <= kProRowsBudget &&
-                   uint64_t(nb) * nW <= 2ull * residentSlots(reinterpret_cast<const void*>(&k_encode<FT, true>),
-                                                             enc::kThreads, 0);
-  auto partHist = res.alloc<uint32_t>(s, runHist && !pro ? size_t(kSegs) * nb * chunks * kNumSymbols : 1);
-  auto partCk = res.alloc<uint32_t>(s, rawCk ? size_t(nb) * chunks : 1);
-  const uint32_t* chunkRows = preHist ? pre->rows : partHist.data();
-  // first-level sums when elements have many chunks (k_histReduce)
-  const uint32_t groups = divUp(chunks, kReduceRows);
-  const bool reduce2 = (runHist || preHist) && !preNorm && !pro && chunks > kReduceRows;
-  auto groupHist = res.alloc<uint32_t>(s, reduce2 ? size_t(kSegs) * nb * groups * kNumSymbols : 1);
-  auto groupCk = res.alloc<uint32_t>(s, reduce2 && rawCk ? size_t(nb) * groups : 1);
-  auto ck = res.alloc<uint32_t>(s, nb);
-  auto tableMem = res.alloc<uint4>(s, preNorm ? 1 : size_t(kSegs) * nb * kNumSymbols);
-  auto pdfMem = res.alloc<uint16_t>(s, preNorm ? 1 : size_t(kSegs) * nb * kNumSymbols);
+  auto partHist = res.alloc<uint32_t>(s, plan.partHist);
+  auto partCk = res.alloc<uint32_t>(s, plan.partCk);
+  const uint32_t* chunkRows = pre ? pre->rows : partHist.data();
+  auto groupHist = res.alloc<uint32_t>(s, plan.groupHist);
+  auto groupCk = res.alloc<uint32_t>(s, plan.groupCk);
+  auto ck = res.alloc<uint32_t>(s, plan.ck);
+  auto tableMem = res.alloc<uint4>(s, plan.table);
+  auto pdfMem = res.alloc<uint16_t>(s, plan.pdf);
+  const bool preNorm = route == Normalise::kCaller;
   const uint4* table = preNorm ? pre->table : tableMem.data();
   const uint16_t* pdf = preNorm ? pre->pdf : pdfMem.data();
-  auto slots = res.alloc<uint8_t>(s, size_t(kSegs) * nb * std::max(MB, 1u) * kSlotBytes);
-  auto cw = res.alloc<uint32_t>(s, kFused ? 1 : size_t(kSegs) * nb * std::max(MB, 1u));
-  // the normalisation runs in the last workgroup of the kernel that writes
-  // an element's final partial rows (k_histReduce, or a k_hist of at most
-  // 4096 workgroups), saving the k_normalize launch.  Each of those
-  // workgroups pays a wait for its rows' write-through stores and a counter
-  // round trip: with many (c3's k_hist: 65,536) that costs more than the
-  // launch (c3 hist 0.74 -> 1.09 ms), so k_normalize runs there.
-  const bool finalInHist = !reduce2 && !pro && runHist && uint64_t(chunks) * nb <= 4096;
-  // k_encode's look-back flags (one per segment, element and encode
-  // workgroup, epoch-tagged, never zeroed; fp64's end as the prefixes
-  // k_coalesce reads), the last-arrival counters and (pro) the histogram
-  // rows, in this stream's sync arena
-  const size_t regions[kSyncRegions] = {0, size_t(kSegs) * nb * nW * 8, 0, 0, size_t(nb) * kSegs * 4, 0};
-  SyncLease lease(res, s, regions, false, pro ? proRowsBytes : 0);
-  // fp64 (two segments): k_encode's per-segment look-back leaves each
-  // workgroup's prefix in its flag for k_coalesce, whose per-workgroup sums
-  // over every earlier block are otherwise quadratic in the blocks (1e8
-  // words: coalesce 129 us).  Below kCoalFlagBlocks blocks per element the
-  // sums are cheaper than the look-back's hand-offs (16.7M words: compress
-  // +1.5 us with it).
-  constexpr uint32_t kCoalFlagBlocks = 8192;
-  uint64_t* const flagsFor = (kFused || MB > kCoalFlagBlocks) ? static_cast<uint64_t*>(lease.base[kSyncFlags])
-                                                                : nullptr;
+  auto slots = res.alloc<uint8_t>(s, size_t(plan.slots) * kSlotBytes);
+  auto cw = res.alloc<uint32_t>(s, plan.cw);
+  // k_encode's look-back flags, the last-arrival counters and (kPrologue) the
+  // histogram rows, in this stream's sync arena
+  const size_t regions[kSyncRegions] = {0, size_t(plan.lookbackBytes), 0, 0, size_t(plan.arriveBytes), 0};
+  SyncLease lease(res, s, regions, false, size_t(plan.rowsBytes));
+  uint64_t* const flagsFor = plan.coalesceFromFlags ? static_cast<uint64_t*>(lease.base[kSyncFlags]) : nullptr;
+  const bool userHist = FT == 0 && c.hist_dev != nullptr;
   NormArgs na;
   na.in = in;
   na.hist = userHist ? c.hist_dev : (reduce2 ? groupHist.data() : chunkRows);
@@ -330,6 +251,7 @@ void compressThreeKernel(const CompressCall& c) {
   na.ckRows = reduce2 ? groups : chunks;
   na.ckOut = ck.data();
   na.arrive = nullptr;
+  // the last arrival of k_hist or k_histReduce normalises
   NormArgs naFinal = na;
   naFinal.arrive = static_cast<uint32_t*>(lease.base[kSyncArrive]);
 
@@ -338,53 +260,54 @@ void compressThreeKernel(const CompressCall& c) {
   }
   // histogram -> (normalise) -> encode per slice of elements
   forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
-    if (runHist) {
+    if (plan.runHist) {
       prof::Scope p("hist", s);
       dim3 g(chunks, ny);
-      const NormArgs& nh = finalInHist ? naFinal : na;
-      if (pro) {
-        k_hist<FT, false, true><<<g, kThreads, 0, s>>>(in, y0, nb, chunkWords, chunks,
-                                                       static_cast<uint32_t*>(lease.rows[0]), nullptr, na,
-                                                       static_cast<uint32_t*>(lease.rows[1]));
-      } else if (rawCk) {
-        k_hist<FT, true><<<g, kThreads, 0, s>>>(in, y0, nb, chunkWords, chunks, partHist.data(),
-                                                partCk.data(), nh);
-      } else {
-        k_hist<FT, false><<<g, kThreads, 0, s>>>(in, y0, nb, chunkWords, chunks, partHist.data(),
-                                                 nullptr, nh);
+      const NormArgs& nh = route == Normalise::kInHist ? naFinal : na;
+      switch (plan.hist) {
+        case HistKernel::kRows:
+          k_hist<FT, false, true><<<g, kThreads, 0, s>>>(in, y0, nb, plan.chunkWords, chunks,
+                                                         static_cast<uint32_t*>(lease.rows[0]), nullptr, na,
+                                                         static_cast<uint32_t*>(lease.rows[1]));
+          break;
+        case HistKernel::kChecksum:
+          k_hist<FT, true><<<g, kThreads, 0, s>>>(in, y0, nb, plan.chunkWords, chunks, partHist.data(),
+                                                  partCk.data(), nh);
+          break;
+        case HistKernel::kPlain:
+          k_hist<FT, false><<<g, kThreads, 0, s>>>(in, y0, nb, plan.chunkWords, chunks, partHist.data(),
+                                                   nullptr, nh);
+          break;
       }
       HIP_LAUNCH_CHECK();
     }
     if (FT != 0 && useChecksum) launchChecksum(in, y0, ny, maxSize, ck.data(), s);
-    if (reduce2) {
+    if (route == Normalise::kInReduce) {
       prof::Scope p("normalize", s);
       dim3 g(groups, ny, kSegs);
       k_histReduce<<<g, kThreads, 0, s>>>(y0, nb, chunks, groups, chunkRows, rawCk ? partCk.data() : nullptr,
                                           groupHist.data(), rawCk ? groupCk.data() : nullptr, naFinal, kSegs);
       HIP_LAUNCH_CHECK();
-    }
-    if (!reduce2 && !finalInHist && !preNorm && !pro) {
+    } else if (route == Normalise::kKernel) {
       prof::Scope p("normalize", s);
       dim3 g(ny, kSegs);
       k_normalize<<<g, kThreads, 0, s>>>(na, y0, nb);
       HIP_LAUNCH_CHECK();
     }
-    if (MB > 0 || kFused) {
+    if (plan.encodeRuns) {
       prof::Scope p("encode", s);
       dim3 g(nW, ny);
       EncTail tail{pdf, ck.data(), c.outSize_dev, flagsFor, nW, pb, useChecksum, spinCap(), deviceErrorWord(),
                    c.sparseN};
       tail.epoch = lease.epoch;
       tail.skew = dispatchSkew();
-      if (pro) {
+      if (route == Normalise::kPrologue) {
         tail.rows = static_cast<const uint32_t*>(lease.rows[0]);
-        tail.rowsPer = proRowsOf(chunks);
+        tail.rowsPer = plan.rowsPer;
         tail.pdfOut = pdfMem.data();
-        k_encode<FT, true><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
-                                                       slots.data(), cw.data(), tail);
+        k_encode<FT, true><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, MB, table, slots.data(), cw.data(), tail);
       } else {
-        k_encode<FT><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), table,
-                                                 slots.data(), cw.data(), tail);
+        k_encode<FT><<<g, enc::kThreads, 0, s>>>(in, out, y0, nb, MB, table, slots.data(), cw.data(), tail);
       }
       HIP_LAUNCH_CHECK();
     }
@@ -394,36 +317,32 @@ void compressThreeKernel(const CompressCall& c) {
       // segments' 4,096 blocks each; 32 gave 256 and a latency-bound copy:
       // coalesce 28.4 -> 16 us at 8, 15.0 at 4, 19.2 at 16, same box)
       const uint32_t bpw = 4;
-      dim3 g(std::max(1u, divUp(MB, bpw)), ny, kSegs);
+      dim3 g(std::max(1u, divUp(plan.maxBlocks, bpw)), ny, kSegs);
       CoalPrefix cp;
       cp.flags = flagsFor;
       cp.nW = nW;
       cp.encBlocks = EncCfg<FT>::kBlocksPerWG;
       cp.epoch = lease.epoch;
       cp.err = deviceErrorWord();
-      k_coalesce<FT><<<g, kThreads, 0, s>>>(in, out, y0, nb, std::max(MB, 1u), bpw, slots.data(),
-                                            cw.data(), pdf, pb, useChecksum, ck.data(),
-                                            c.outSize_dev, c.sparseN, cp);
+      k_coalesce<FT><<<g, kThreads, 0, s>>>(in, out, y0, nb, MB, bpw, slots.data(), cw.data(), pdf, pb,
+                                            useChecksum, ck.data(), c.outSize_dev, c.sparseN, cp);
       HIP_LAUNCH_CHECK();
     }
   });
 }
 
+// One compress call: planCompress (compress_plan.h) picks the compressor.
 template <int FT>
 void encodeBatchDevice(const CompressCall& c) {
   checkProbBits(c.pb);
   if (c.nb == 0) return;
+  const CompressPlan plan =
+      planCall<FT>(c.nb, c.maxSize, c.useChecksum, FT == 0 && c.hist_dev != nullptr, c.pre, c.inAligned16);
+  if (!plan.singlePass) return compressThreeKernel<FT>(c, plan);
   if constexpr (FloatTraits<FT>::kSegs == 1) {
-    const bool userHist = FT == 0 && c.hist_dev != nullptr;
-    const bool rawCk = FT == 0 && c.useChecksum;
-    // (byte archives with a checksum stay single-pass: the three-kernel path
-    // has no prologue normalisation for them)
-    if (!userHist && c.inAligned16 &&
-        ((rawCk && compressPath() != 2) || persistentPreferred<FT>(c.nb, c.maxSize))) {
-      if (rawCk ? compressPersistent<FT, FT == 0>(c) : compressPersistent<FT, false>(c)) return;
-    }
+    if (plan.rawCk) compressPersistent<FT, FT == 0>(c, plan);
+    else compressPersistent<FT, false>(c, plan);
   }
-  compressThreeKernel<FT>(c);
 }
 
 // One decode call in any form (DecodeCall, codec_internal.h): the form picks

@@ -11,6 +11,7 @@
 
 #include "batch.h"
 #include "batch_tables.h"
+#include "compress_plan.h"
 #include "decode_plan.h"
 #include "dietgpu/GpuFloatCodec.h"
 
@@ -117,11 +118,11 @@ V cachedPerDevice(const K& key, Q&& query) {
 // c.pb / c.useChecksum come from the config.
 void floatCompressDescs(const FloatCompressConfig& config, CompressCall c);
 
-// Whether encodeBatchDevice compresses nb 16 B-aligned elements of at most
-// maxWords words of a single-segment format (FT 0-3) with the single-pass
-// compressor (k_pcompress) rather than the three-kernel path.
-template <int FT>
-bool persistentPreferred(uint32_t nb, uint32_t maxWords);
+// The plan (compress_plan.h) that encodeBatchDevice follows for nb elements of
+// at most maxSize units of float type ft (0: the byte codec) on the current
+// device, in the current compressPath() mode, with no PartialHist.
+CompressPlan planCompressCall(int ft, uint32_t nb, uint32_t maxSize, bool useChecksum, bool userHist,
+                              bool inAligned16);
 
 // The dense float decode of a call in any form.  The float type and c.pb come
 // from the config, which is validated here.  A full call verifies the checksum

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "archive.h"
+#include "compress_plan.h"
 #include "sync_arena.h"
 
 namespace dietgpu {
@@ -24,6 +25,7 @@ namespace dietgpu {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr uint32_t kSlotBytes = kStateBytesPerBlock + kSlotDataBytes;
+static_assert(cplan::kBlockWords == kBlockSize && cplan::kSymbols == kNumSymbols, "compress_plan.h restates them");
 
 // Bit-exact restatement of normalizeProbabilitiesFromHistogram
 // (ans/GpuANSStatistics.cuh:178-366) -- float32 quantisation, the diff > 0
@@ -319,17 +321,10 @@ static __global__ __launch_bounds__(kThreads) void k_normalize(NormArgs a, uint3
 // lanes l and l + 16 of a wave half share a column.
 // ---------------------------------------------------------------------------
 constexpr int kHistCols = 32;
-// kRows (small three-kernel grids, k_encode's prologue normalisation):
-// chunk c adds its counts with atomics into row c % P of [segs][nb][P][256],
-// P = proRowsOf(chunks) = min(chunks, kProRows) (this call's zeroed buffer of
-// the sync arena), so the encoder sums P rows instead of a k_histReduce /
-// k_normalize launch summing thousands; zero bins add nothing.  Sized by the
-// chunk count, so a batch of many one-chunk elements holds one row per
-// element and segment, not 64.  `zeroNext`: the same layout in the other
-// buffer, zeroed here for the next call (SyncLease::rows).
-constexpr uint32_t kProRows = 64;
-__host__ __device__ constexpr uint32_t proRowsOf(uint32_t chunks) { return chunks < kProRows ? chunks : kProRows; }
-
+// kRows (small three-kernel grids, k_encode's prologue normalisation; kProRows
+// and proRowsOf: compress_plan.h): chunk c adds its counts with atomics into
+// row c % P of [segs][nb][P][256], P = proRowsOf(chunks).  `zeroNext`: the same
+// layout in the other buffer, zeroed here for the next call (SyncLease::rows).
 template <int FT, bool kChecksum, bool kRows = false>
 __global__ __launch_bounds__(kThreads) void k_hist(BatchDesc in, uint32_t batchOffset,
                                                    uint32_t numInBatch, uint32_t chunkWords,
@@ -466,9 +461,9 @@ __global__ __launch_bounds__(kThreads) void k_hist(BatchDesc in, uint32_t batchO
 // many chunks (few large elements: one 128 MiB fp64 tensor is 2048 chunks,
 // which k_normalize's single workgroup would sum serially for ~0.3 ms).
 // grid (groups, batch, segments): workgroup g sums chunks [64g, 64g + 64) of
-// its (element, segment) row, and the byte-checksum partials likewise.
+// its (element, segment) row (kReduceRows, compress_plan.h), and the
+// byte-checksum partials likewise.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kReduceRows = 64;
 
 static __global__ __launch_bounds__(kThreads) void k_histReduce(
     uint32_t batchOffset, uint32_t numInBatch, uint32_t chunksPerElem, uint32_t groups,
@@ -535,6 +530,7 @@ struct EncCfg {
   static constexpr int S = FloatTraits<FT>::kSegs;
   static constexpr int kBlocksPerWave = 2;
   static constexpr int kBlocksPerWG = enc::kWaves * kBlocksPerWave;
+  static_assert(kBlocksPerWG == kEncBlocksPerWG, "compress_plan.h sizes k_encode's grid");
   // 16-byte input vectors per lane per block per segment (32 lanes x V x 16 B
   // = 512 words)
   static constexpr int V = int(enc::kSegWords * sizeof(WordT) / (32 * 16));

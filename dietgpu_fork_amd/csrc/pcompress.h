@@ -91,7 +91,7 @@ namespace dietgpu {
 namespace pc {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kBlocksPerItem = 2 * kWaves;           // one block pair per wave
+static_assert(kBlocksPerItem == 2 * kWaves, "one block pair per wave (compress_plan.h)");
 constexpr uint32_t kSteps = kBlockSize / kLanesPerBlock;  // 128 steps per block
 constexpr uint32_t kSegSteps = 16;
 constexpr uint32_t kSegWords = kSegSteps * kLanesPerBlock;  // 512 symbols
@@ -101,9 +101,6 @@ constexpr uint32_t kRing = 1024;  // u16 words per block ring (a typical block's
 // enc::kUnroll steps (<= 128 new words per block), so a block holds at most
 // kSpill + 127 < kRing unflushed words; most blocks never spill
 constexpr uint32_t kSpill = kRing - 128;
-// Largest team summed by every member (a 1 MiB-symbol element): its partials
-// are one sc1 load per member and bin.
-constexpr uint32_t kMaxTeam = 32;
 // histogram: u32 counters, 12 columns (l % 12 of a 32-lane half) per bin,
 // rows padded to 13: two or three lanes of a half share a column where 8
 // columns had four, so hot bins serialise less (c2 compress 143.5 -> 141.5

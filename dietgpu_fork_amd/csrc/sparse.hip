@@ -488,8 +488,8 @@ void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, c
   // compress 85 -> 75 us).  It lengthens every tile's workgroup, so with
   // more elements the separate k_hist over the compacted lists is faster
   // (5 x 15M: 155 us against 170).
-  bool countHist = nb == 1;
-  if constexpr (FT != 4) countHist = countHist && !persistentPreferred<FT>(nb, maxN);
+  const bool countHist =
+      nb == 1 && !planCompressCall(FT, nb, maxN, config.useChecksum, false, /*inAligned16=*/true).singlePass;
   constexpr int kSegs = FloatTraits<FT>::kSegs;
   const uint32_t G = tiles;
   const uint32_t R = std::min(tiles, kReduceRows);

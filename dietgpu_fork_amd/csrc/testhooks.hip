@@ -4,7 +4,9 @@
 // holds compute units, so tests can run the compressor while another kernel
 // occupies part of the chip (pcompress.h, "Forward progress"); and the byte
 // histogram of the three-kernel compressor's first pass exposed on its own,
-// as the reference's ANSStatisticsTest.cu:44-95 exercises ansHistogramBatch.
+// as the reference's ANSStatisticsTest.cu:44-95 exercises ansHistogramBatch;
+// the C++ entry points with configurations the C ABI cannot express; the
+// compress plan (compress_plan.h) as the dense driver computes it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include <string>
 
 #include "capi_internal.h"
+#include "codec_internal.h"
 #include "common.h"
 #include "dietgpu/GpuFloatCodec.h"
 #include "dietgpu/StackDeviceMemory.h"
@@ -174,6 +177,36 @@ int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_check
                                       use_checksum != 0);
       floatGatherRows(*res->mem, cfg, in, row_words, num_idx, idx_dev, true, out, row_words, out_success_dev, s);
     }
+  });
+}
+
+int dietgpu_test_compress_plan(int float_type, uint32_t nb, uint32_t max_size, int checksum, int user_hist,
+                               int aligned16, dietgpu_test_plan* out) {
+  return guardedTest([&] {
+    DG_CHECK(out, "null plan");
+    const dietgpu::CompressPlan p =
+        dietgpu::planCompressCall(float_type, nb, max_size, checksum != 0, user_hist != 0, aligned16 != 0);
+    *out = dietgpu_test_plan{};
+    out->single_pass = p.singlePass;
+    out->refused = uint32_t(p.refused);
+    out->team = p.team;
+    out->too_many_items = p.tooManyItems;
+    out->rounds = p.rounds;
+    out->teams_per_round = p.teamsPerRound;
+    out->xcd = p.xcd;
+    out->grid = p.grid;
+    out->max_r = p.maxR;
+    out->items = p.items;
+    out->chunk_words = p.chunkWords;
+    out->chunks = p.chunks;
+    out->groups = p.groups;
+    out->run_hist = p.runHist;
+    out->raw_ck = p.rawCk;
+    out->hist = uint32_t(p.hist);
+    out->normalise = uint32_t(p.normalise);
+    out->encode_wgs = p.encodeWGs;
+    out->encode_runs = p.encodeRuns;
+    out->coalesce_from_flags = p.coalesceFromFlags;
   });
 }
 

@@ -64,6 +64,31 @@ int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_check
                                uint32_t row_words, uint32_t num_idx, const void* idx_dev, void* out,
                                uint8_t* out_success_dev, void* stream);
 
+/* The compress plan (csrc/compress_plan.h) of a dense compress call with no
+ * caller-counted rows: which compressor takes the batch and what it launches.
+ * Enumerations as in that header. */
+typedef struct dietgpu_test_plan {
+  uint32_t single_pass; /* 1: k_pcompress; 0: k_hist -> k_encode */
+  uint32_t refused;     /* Refused: why not single-pass (0 when it is) */
+  uint32_t team;        /* k_pcompress items of the largest element */
+  /* single-pass (zero otherwise) */
+  uint32_t too_many_items; /* the call is refused */
+  uint32_t rounds, teams_per_round, xcd, grid, max_r, items;
+  /* three kernels (zero otherwise) */
+  uint32_t chunk_words, chunks, groups;
+  uint32_t run_hist;  /* k_hist launches per slice of elements: 0 or 1 */
+  uint32_t raw_ck;
+  uint32_t hist;      /* HistKernel */
+  uint32_t normalise; /* Normalise (kKernel, not zero, when single-pass) */
+  uint32_t encode_wgs, encode_runs, coalesce_from_flags;
+} dietgpu_test_plan;
+
+/* out = the plan the dense compress driver computes on the current device, in
+ * the current dietgpu_set_compress_path mode, for nb >= 1 elements of at most
+ * max_size bytes (float_type 0, the byte codec) or words (1..4). */
+int dietgpu_test_compress_plan(int float_type, uint32_t nb, uint32_t max_size, int checksum, int user_hist,
+                               int aligned16, dietgpu_test_plan* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -372,7 +372,7 @@ VARS = {
               """  uint32_t q;
   asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD"
       : "=v"(q) : "v"(e.w), "v"(__umulhi(x, e.y)));""")],
-    "pc128": [(P, "constexpr uint32_t kMaxTeam = 32;", "constexpr uint32_t kMaxTeam = 128;")],
+    "pc128": [("compress_plan.h", "constexpr uint32_t kMaxTeam = 32;", "constexpr uint32_t kMaxTeam = 128;")],
     "bpw4": [("codec.hip", "      const uint32_t bpw = 8;", "      const uint32_t bpw = 4;")],
     # sparse count diagnostics (timing only: archives wrong)
     "sp_noga": [(SP, "      if (sum)\n        __hip_atomic_fetch_add(G(histRows)", "      if (sum == 0xFFFFFFFFu)\n        __hip_atomic_fetch_add(G(histRows)")],
