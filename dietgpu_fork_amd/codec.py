@@ -279,23 +279,30 @@ def float_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None):
     `ft` names the archives' type and defaults to the accumulators'.  One
     accumulator dtype per call; accumulators of two members must not overlap.
     A failing member's accumulator is untouched.  No checksum is verified."""
+    ft, acc_ft = _accumulate_types("float_decompress_accumulate", archives, accs, ft)
+    return _pointer_decode(N.lib().dietgpu_float_decompress_accumulate, (ft, prob_bits), archives, accs, ws,
+                           tail=(acc_ft,))
+
+
+def _accumulate_types(who, archives, accs, ft):
+    """The argument checks of the accumulate wrappers, before the library is
+    touched -> (the archives' float type, the accumulators')."""
     nb = len(archives)
     if len(accs) != nb:
         raise ValueError("archives and accs must have one entry per member")
     if nb == 0:
-        raise ValueError("float_decompress_accumulate: empty batch")
+        raise ValueError(f"{who}: empty batch")
     if any(a.dtype != accs[0].dtype for a in accs):
-        raise ValueError("float_decompress_accumulate: the accumulators must share a dtype")
+        raise ValueError(f"{who}: the accumulators must share a dtype")
     if accs[0].dtype not in FLOAT_TYPE:
-        raise ValueError(f"float_decompress_accumulate: unsupported accumulator dtype {accs[0].dtype}")
+        raise ValueError(f"{who}: unsupported accumulator dtype {accs[0].dtype}")
     if any(not a.is_contiguous() for a in accs):
-        raise ValueError("float_decompress_accumulate: the accumulators must be contiguous")
+        raise ValueError(f"{who}: the accumulators must be contiguous")
     acc_ft = FLOAT_TYPE[accs[0].dtype]
     ft = ft or acc_ft
     if not (acc_ft == ft or (ft in (1, 2) and acc_ft == 3)):
-        raise ValueError(f"float_decompress_accumulate: accumulator type {acc_ft} does not go with float type {ft}")
-    return _pointer_decode(N.lib().dietgpu_float_decompress_accumulate, (ft, prob_bits), archives, accs, ws,
-                           tail=(acc_ft,))
+        raise ValueError(f"{who}: accumulator type {acc_ft} does not go with float type {ft}")
+    return ft, acc_ft
 
 
 # ---------------------------------------------------------------- range ----
@@ -473,6 +480,19 @@ def sparse_decompress(archives, outs, ft=None, prob_bits=10, checksum=False, ws=
     ft = ft or FLOAT_TYPE[outs[0].dtype]
     return _pointer_decode(N.lib().dietgpu_float_decompress_sparse, (ft, prob_bits, int(checksum)), archives, outs,
                            ws)
+
+
+def sparse_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None):
+    """accs[i][j] += word j of the element sparse float archive archives[i]
+    (16-byte aligned) encodes, for every j whose word is not +0.0 bitwise
+    (k_sparseExpand's accumulate form) -> (ok, sz) as sparse_decompress.  The
+    other accumulator words are neither read nor written: an accumulator word
+    of -0.0 under a zero word stays -0.0, where float_decompress_accumulate's
+    -0.0 + (+0.0) gives +0.0.  Dtype rules, arguments and checks as
+    float_decompress_accumulate; sz is the element's size for every member."""
+    ft, acc_ft = _accumulate_types("sparse_decompress_accumulate", archives, accs, ft)
+    return _pointer_decode(N.lib().dietgpu_float_decompress_sparse_accumulate, (ft, prob_bits), archives, accs, ws,
+                           tail=(acc_ft,))
 
 
 def profile(on=True):

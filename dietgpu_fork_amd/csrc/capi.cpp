@@ -334,6 +334,21 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int ft, int pb, uint
   });
 }
 
+int dietgpu_float_decompress_sparse_accumulate(dietgpu_stack* res, int ft, int pb, uint32_t nb, const void** in,
+                                               void** acc, const uint32_t* cap, int acc_type, uint8_t* succ,
+                                               uint32_t* sizes, void* stream) {
+  return guarded([&] {
+    // (the same order of checks as dietgpu_float_decompress_accumulate)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    DG_CHECK(acc_type == ft || ((ft == 1 || ft == 2) && acc_type == 3),
+             "acc_type " << acc_type << " does not go with float_type " << ft
+                         << " (float_type itself, or 3 for float_type 1 / 2)");
+    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    floatDecompressSparseAccumulate(R(res), cfg, nb, in, acc, cap, FloatType(acc_type), succ, sizes, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 // (the gather entry points check the flattened config and the row shape
 // before they look at the stack or any pointer)
 int dietgpu_ans_gather_rows(dietgpu_stack* res, int pb, const void* archive_dev, uint32_t row_words,

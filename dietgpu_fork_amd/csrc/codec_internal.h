@@ -54,7 +54,8 @@ struct CompressCall {
   const uint32_t* sparseN = nullptr;
 };
 
-// One decode call of the generic driver (codec.hip decodeBatchDevice): nb
+// One decode call of the generic driver (codec.hip decodeBatchDevice) or of
+// the sparse one (sparse.hip sparseDecompressT: full and accumulate): nb
 // archives `in` into `out`, in one of the forms of decode_plan.h.
 //  - full, accumulate: capacities out.size(b), at most maxCapacity units;
 //    an accumulate call's `out` are the accumulators, counted in their words.

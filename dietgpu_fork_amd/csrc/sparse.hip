@@ -18,7 +18,11 @@
 // chain dominates.)  A word range of an element is read without the rest
 // (floatDecompressSparseRange, an extension): the same chunk counts give the
 // rank of the range's ends, i.e. its slice of the nonzero list; the dense
-// range decode reads that slice and k_sparseExpandRange expands it.
+// range decode reads that slice and k_sparseExpandRange expands it.  An
+// element is added to an accumulator without a temporary
+// (floatDecompressSparseAccumulate, an extension): k_sparseExpand<FT, ACC>
+// adds the nonzero words where the full decode stores them and touches no
+// other accumulator word.
 //
 // Wire format: 16 B header {u32 N, 12 B zero}, bitmap
 // ceil(N/8) bytes (bit 7 of byte k <-> element 8k) padded to 16, then a dense
@@ -365,9 +369,13 @@ __device__ __forceinline__ uint32_t chunkListOffset(gp<const uint32_t> pre, gp<c
 // are issued back to back (their addresses depend only on the bitmap) for the
 // caller's 16 row stores.  v[j] = word i0 + 64 j + lane of the element, 0
 // where its bit is clear or wanted(i) is false (that word is not read).
-template <class W, class Wanted>
+// row(j, i, set) follows row j's gather at once (set: the word's bitmap bit),
+// so what it loads is in flight with the 16 gathers (the accumulate forms'
+// accumulator words).
+template <class W, class Wanted, class Row>
 __device__ __forceinline__ void expandRows(uint64_t mv, uint32_t base, uint32_t i0, uint32_t n, bool gap,
-                                           gp<const W> list, uint32_t lane, Wanted wanted, W (&v)[kChunkRows]) {
+                                           gp<const W> list, uint32_t lane, Wanted wanted, W (&v)[kChunkRows],
+                                           Row row) {
 #pragma unroll
   for (uint32_t j = 0; j < kChunkRows; ++j) {
     const uint64_t m = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mv >> 32)), int(j)))) << 32) |
@@ -376,7 +384,28 @@ __device__ __forceinline__ void expandRows(uint64_t mv, uint32_t base, uint32_t 
     uint32_t src = base + mbcnt(m);
     if (gap && i + 1 == n) src += 1;
     v[j] = wanted(i) && ((m >> lane) & 1) ? list[src] : W(0);
+    row(j, i, ((m >> lane) & 1) != 0);
     base += uint32_t(__popcll(m));
+  }
+}
+
+template <class W, class Wanted>
+__device__ __forceinline__ void expandRows(uint64_t mv, uint32_t base, uint32_t i0, uint32_t n, bool gap,
+                                           gp<const W> list, uint32_t lane, Wanted wanted, W (&v)[kChunkRows]) {
+  expandRows(mv, base, i0, n, gap, list, lane, wanted, v, [](uint32_t, uint32_t, bool) {});
+}
+
+// x is in its register from here on: a loaded value has arrived, and nothing
+// computed from it moves above this point (an empty asm the compiler cannot
+// see through; no instruction is emitted).
+template <class T>
+__device__ __forceinline__ void landed(T& x) {
+  if constexpr (sizeof(T) == 8) {
+    asm volatile("" : "+v"(x));
+  } else {
+    uint32_t t = x;
+    asm volatile("" : "+v"(t));
+    x = T(t);
   }
 }
 
@@ -419,7 +448,17 @@ __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_
 // tile-per-workgroup kernel it replaces summed every earlier tile's count per
 // tile and staged through LDS: 5 x 15M fp32 at 50 % zeros 176 us, fp64
 // 430 us.)
-template <int FT>
+//
+// ACC (Join<FT, ACC>'s, decode.h): 0 stores the expanded
+// words; 1 / 2 add them to the accumulators `out`, acc[i] = sumOne(acc[i],
+// x[i]) for every i < n whose bitmap bit is set.  A word whose bit is clear
+// is +0.0 and its accumulator word is neither read nor written (it keeps its
+// bits where IEEE a + (+0.0) would turn -0.0 into +0.0 or quiet a NaN).  The
+// 16 accumulator loads, masked like the gathers, are issued between them
+// (expandRows' row hook), so all 32 are in flight before the first add; the
+// stores are masked by the bit and plain (the next peer's call reads the
+// accumulator again).
+template <int FT, int ACC = 0>
 __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDesc out, uint32_t batchOffset,
                                                            uint32_t chunksPerElem, uint32_t blocksPerElem,
                                                            const uint32_t* __restrict__ sizes,
@@ -452,13 +491,40 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   // only the chunk holding word n-1 looks
   const bool gap = n - 1 - i0 < kChunkWords && gapBit(bm, n);
   W v[kChunkRows];
-  expandRows(mv, base, i0, n, gap, (gp<const W>)lists.start(b), lane, [](uint32_t) { return true; }, v);
-  gp<W> y = (gp<W>)out.start(b);
+  if constexpr (ACC == 0) {
+    expandRows(mv, base, i0, n, gap, (gp<const W>)lists.start(b), lane, [](uint32_t) { return true; }, v);
+    gp<W> y = (gp<W>)out.start(b);
 #pragma unroll
-  for (uint32_t j = 0; j < kChunkRows; ++j) {
-    const uint32_t i = i0 + 64 * j + lane;
-    // streaming: nothing here re-reads the output
-    if (i < n) __builtin_nontemporal_store(v[j], y + i);
+    for (uint32_t j = 0; j < kChunkRows; ++j) {
+      const uint32_t i = i0 + 64 * j + lane;
+      // streaming: nothing here re-reads the output
+      if (i < n) __builtin_nontemporal_store(v[j], y + i);
+    }
+  } else {
+    using J = Join<FT, ACC>;  // (its static_assert: ACC 2 for fp16 / bf16 only)
+    using A = typename J::AccT;
+    gp<A> y = (gp<A>)out.start(b);
+    A a[kChunkRows];
+    uint32_t taken16 = 0;  // bit j: this lane's word of row j has its bitmap bit set
+    // (mv holds no bit at or past n; the loads and stores test i < n all the same)
+    expandRows(mv, base, i0, n, gap, (gp<const W>)lists.start(b), lane, [&](uint32_t i) { return i < n; }, v,
+               [&](uint32_t j, uint32_t i, bool set) __attribute__((always_inline)) {
+                 const bool taken = set && i < n;
+                 a[j] = taken ? y[i] : A(0);
+                 taken16 |= (taken ? 1u : 0u) << j;
+               });
+    // One wait for the 32 loads here, where the wave has converged.  Left to
+    // the masked store blocks below, the compiler widened a bf16 word inside
+    // its masked load block (a wait per row), and every store block waited
+    // for vmcnt(0), i.e. for the previous row's store as well.
+#pragma unroll
+    for (uint32_t j = 0; j < kChunkRows; ++j) {
+      landed(v[j]);
+      landed(a[j]);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kChunkRows; ++j)
+      if ((taken16 >> j) & 1) y[i0 + 64 * j + lane] = J::sumOne(a[j], v[j]);
   }
 }
 
@@ -551,10 +617,17 @@ void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, c
   floatCompressDescs(config, dense);
 }
 
+// c.form: kFull (c.out are the outputs), or kAccumulate / kAccumulateFp32
+// (c.out are the accumulators, capacities in their words; the
+// nonzero list is decoded into the scratch rows as in a full call and added
+// by k_sparseExpand<FT, ACC>; no checksum is verified, so nothing here waits
+// for the stream).
 template <int FT>
 FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, const DecodeCall& c) {
   StackDeviceMemory& res = c.res;
   const hipStream_t s = c.s;
+  const bool full = c.form == DecodeForm::kFull;
+  const char* family = full ? "sparse" : "sparse_accumulate";
   const uint32_t nb = c.nb, maxCap = c.maxCapacity;
   const uint32_t chunks = std::max(1u, divUp(maxCap, kChunkWords));
   const uint32_t cblocks = divUp(chunks, kThreads);  // k_sparseChunks workgroups per element
@@ -566,7 +639,7 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   auto chunkPre = res.alloc<uint32_t>(s, size_t(nb) * chunks);
   auto blockTot = res.alloc<uint32_t>(s, size_t(nb) * cblocks);
   forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
-    prof::Scope p("sparse", s);
+    prof::Scope p(family, s);
     k_sparseChunks<<<dim3(cblocks, ny), kThreads, 0, s>>>(c.in, y0, chunks, cblocks, densePtrs.data(), sizes.data(),
                                                           chunkPre.data(), blockTot.data());
     HIP_LAUNCH_CHECK();
@@ -585,7 +658,7 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   cfg.useChecksum = false;
   floatDecompressDescs(cfg, dense);
   FloatDecompressStatus status;
-  if (config.useChecksum) {
+  if (full && config.useChecksum) {
     // verify the dense archive's checksum over the bytes it was computed on
     // (the first listLen bytes of the nonzero list)
     auto denseLen = res.alloc<uint32_t>(s, nb);
@@ -594,13 +667,24 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
     dense.out.sizes = denseLen.data();
     status = verifiedStatus<FloatDecompressStatus>(dense, true);
   }
-  forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
-    prof::Scope p("sparse", s);
-    k_sparseExpand<FT><<<dim3(divUp(chunks, kWaves), ny), kThreads, 0, s>>>(
-        c.in, c.out, y0, chunks, cblocks, sizes.data(), chunkPre.data(), blockTot.data(), lists, denseOk.data(),
-        c.outSuccess_dev, c.outSize_dev);
-    HIP_LAUNCH_CHECK();
-  });
+  auto expand = [&](auto acc) {
+    forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
+      prof::Scope p(family, s);
+      k_sparseExpand<FT, decltype(acc)::value><<<dim3(divUp(chunks, kWaves), ny), kThreads, 0, s>>>(
+          c.in, c.out, y0, chunks, cblocks, sizes.data(), chunkPre.data(), blockTot.data(), lists, denseOk.data(),
+          c.outSuccess_dev, c.outSize_dev);
+      HIP_LAUNCH_CHECK();
+    });
+  };
+  if (full) {
+    expand(std::integral_constant<int, 0>{});
+  } else if (c.form == DecodeForm::kAccumulate) {
+    expand(std::integral_constant<int, 1>{});
+  } else {
+    DG_CHECK(c.form == DecodeForm::kAccumulateFp32 && (FT == 1 || FT == 2),
+             "sparse decode: an fp32 accumulator goes with fp16 / bf16 archives only");
+    if constexpr (FT == 1 || FT == 2) expand(std::integral_constant<int, 2>{});
+  }
   return status;
 }
 
@@ -967,6 +1051,44 @@ FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
   c.outSize_dev = outSize_dev;
   return dispatchFloatType(config.floatType,
                            [&](auto f) { return sparseDecompressT<decltype(f)::value>(config, c); });
+}
+
+// Sparse decode-and-accumulate.  As below, every host check
+// precedes the first allocation, upload or launch.
+void floatDecompressSparseAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config,
+                                     uint32_t numInBatch, const void** in, void** acc,
+                                     const uint32_t* accCapacity, FloatType accType, uint8_t* outSuccess_dev,
+                                     uint32_t* outSize_dev, hipStream_t stream) {
+  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
+  const int ft = int(config.floatType);
+  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
+  DG_CHECK(!config.useChecksum,
+           "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded words)");
+  const bool half = config.floatType == FloatType::kFloat16 || config.floatType == FloatType::kBFloat16;
+  const bool wide = half && accType == FloatType::kFloat32;
+  DG_CHECK(accType == config.floatType || wide,
+           "accumulator type " << int(accType) << " does not go with float type " << ft
+                               << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
+  if (numInBatch == 0) return;
+  const uint32_t aws = floatWordBytes(int(accType));
+  const auto ip = addressColumn(in, numInBatch), op = addressColumn(acc, numInBatch);
+  for (uint32_t i = 0; i < numInBatch; ++i) {
+    DG_CHECK(op[i] % aws == 0, "accumulator " << i << " not aligned to its word size");
+    // (the compressor requires it of its output; the bitmap is read as u64)
+    DG_CHECK(ip[i] % 16 == 0, "sparse archive " << i << " must be 16-byte aligned");
+  }
+  const SizeColumn cap(accCapacity, numInBatch);
+  const auto t = uploadTables(res, stream, {&ip, &op}, cap.sizes, true);
+  const DeviceDescs dd(res, stream, &t, numInBatch);
+  DecodeCall c{res, stream};
+  c.form = wide ? DecodeForm::kAccumulateFp32 : DecodeForm::kAccumulate;
+  c.nb = numInBatch;
+  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], nullptr)));
+  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], t.u32)));
+  c.maxCapacity = cap.maxSize;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  dispatchFloatType(config.floatType, [&](auto f) { sparseDecompressT<decltype(f)::value>(config, c); });
 }
 
 // Every host check precedes the first allocation, upload or launch.

@@ -72,6 +72,73 @@ class GpuFloatCodec:
         if not bool((status != 0).all()):
             raise RuntimeError("compressed collective: an archive failed to decode")
 
+    def info(self, archive):
+        """(numel, dtype) of the element `archive` encodes."""
+        return _archive_info(archive)
+
+
+class GpuSparseFloatCodec:
+    """The sparse float codec on the local GPU (codec.sparse_compress /
+    sparse_decompress / sparse_decompress_accumulate: bitmap + the dense codec
+    on the nonzero words) for the compressed collectives, for tensors that are
+    mostly exact zeros (MoE, embedding or pruned gradients).  Lossless like
+    GpuFloatCodec, so the moving collectives return the same bits.
+
+    In the reducing collectives the zero words of a peer's tensor are skipped,
+    not added: element i of the result is round((...(own + x_r1) + ...)) over
+    the peers whose word i is nonzero (bitwise, so a peer's -0.0 is added), in
+    the documented order.  That equals GpuFloatCodec's result except where the
+    running sum is -0.0 and a peer's word is +0.0: the dense sum turns +0.0
+    there, this one stays -0.0 (and a signalling NaN in the running sum is
+    quieted by the dense add only)."""
+
+    def __init__(self, prob_bits=10, workspace_bytes=256 << 20):
+        self.prob_bits = prob_bits
+        self.workspace_bytes = workspace_bytes
+        self._ws = {}
+
+    def _workspace(self, device):
+        from . import codec
+
+        if device not in self._ws:
+            self._ws[device] = codec.Workspace(self.workspace_bytes, device)
+        return self._ws[device]
+
+    def compress(self, tensors):
+        from . import codec
+
+        return codec.sparse_compress(tensors, prob_bits=self.prob_bits, ws=self._workspace(tensors[0].device))
+
+    @staticmethod
+    def _raise_on_failure(ok):
+        if not bool((ok != 0).all()):
+            raise RuntimeError("compressed collective: an archive failed to decode")
+
+    def decompress(self, archives, outs):
+        from . import codec
+
+        ok, _ = codec.sparse_decompress(archives, outs, prob_bits=self.prob_bits, ws=self._workspace(outs[0].device))
+        self._raise_on_failure(ok)
+
+    def accumulate(self, archives, accs):
+        """accs[i] += the element archives[i] encodes, at its nonzero words only
+        (k_sparseExpand's accumulate form); dtypes as GpuFloatCodec.accumulate."""
+        from . import codec
+
+        # (a float32 accumulator serves three archive types: the header tells)
+        ft = self.info(archives[0])[1] if accs[0].dtype == torch.float32 else accs[0].dtype
+        ok, _ = codec.sparse_decompress_accumulate(archives, accs, ft=codec.FLOAT_TYPE[ft], prob_bits=self.prob_bits,
+                                                   ws=self._workspace(accs[0].device))
+        self._raise_on_failure(ok)
+
+    def info(self, archive):
+        """(numel, dtype) of the element a sparse float archive encodes: numel
+        from the sparse header, dtype from the dense header behind the bitmap
+        (two small reads on the host)."""
+        n = int(archive[:4].cpu().numpy().view("<u4")[0])
+        at = 16 + (((n + 7) // 8 + 15) // 16) * 16
+        return n, _archive_info(archive[at:at + 32])[1]
+
 
 def _check_sizes(sizes, what):
     """Archive sizes seen by every rank: 0 marks an element whose compression
@@ -225,11 +292,16 @@ def reduce_archives(own, archives, codec, acc_dtype=None):
     the tensors' dtype.  One codec.accumulate call per peer; no decoded
     temporary.  The accumulator starts as `own` converted to acc_dtype, not as
     +0.0: with no archives the result is `own` bit for bit (-0.0 included).
-    own=None: the first archive's element takes the place of `own`."""
+    own=None: the first archive's element takes the place of `own` (its numel
+    and dtype come from codec.info(archive), or from a dense float header when
+    the codec has no info).
+    With GpuSparseFloatCodec a peer's zero words are skipped: the sum runs
+    over the peers whose word is nonzero, which is the same value except that
+    a running sum of -0.0 stays -0.0 where a peer holds +0.0."""
     if own is None:
         if not archives:
             raise ValueError("reduce_archives: nothing to reduce")
-        n, dtype = _archive_info(archives[0])
+        n, dtype = getattr(codec, "info", _archive_info)(archives[0])
         own = torch.empty(n, dtype=dtype, device=archives[0].device)
         codec.decompress([archives[0]], [own])
         archives = archives[1:]
@@ -252,6 +324,10 @@ def reduce_scatter_compressed(tensors, group=None, codec=None, acc_dtype=None):
     other ranks ascending, every add done in acc_dtype (reduce_archives).  The
     order is fixed, so the result is deterministic and reproducible; it is not
     the order of RCCL's ring, so it is not bit-equal to dist.reduce_scatter.
+    With codec=GpuSparseFloatCodec() the archives are sparse and a peer's zero
+    words are skipped: element i is that sum over the peers whose word i is
+    nonzero, equal to the dense codec's result except that a running sum of
+    -0.0 stays -0.0 where a peer's word is +0.0.
 
     The W - 1 outgoing tensors are compressed in one batch; one all-gather
     exchanges the whole (source, destination) table of (numel, archive size),
@@ -305,7 +381,8 @@ def all_reduce_compressed(tensor, group=None, codec=None, acc_dtype=None):
     there (rank j's own value first, the other ranks ascending, in acc_dtype,
     rounded once), and the lossless all-gather hands every rank the same
     bits.  Shards may be empty (numel < W).  Returns a tensor of the input's
-    shape."""
+    shape.  codec=GpuSparseFloatCodec(): both steps move sparse archives, and
+    the reduction skips the peers' zero words (reduce_scatter_compressed)."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size(group)
     flat = tensor.contiguous().view(-1)

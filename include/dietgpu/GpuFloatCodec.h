@@ -188,6 +188,33 @@ void floatDecompressAccumulate(StackDeviceMemory& res,
                                uint8_t* outSuccess_dev, uint32_t* outSize_dev,
                                hipStream_t stream);
 
+// Sparse decode-and-accumulate: acc[b][i] = acc[b][i] + x[i] for every i < n
+// whose bit is set in the bitmap of sparse float archive in[b] (x: the n-word
+// element it encodes; a word is "set" iff it is not +0.0 bitwise, so -0.0 is
+// added).  Every other accumulator word is neither read nor written: the
+// expansion adds where floatDecompressSparse stores, with no temporary and no
+// traffic for the zeros.  accType and the sums follow floatDecompressAccumulate
+// (config.floatType, or kFloat32 for kFloat16 / kBFloat16; anything else
+// throws; each sum correctly rounded in the accumulator's type).
+// Deviation from the dense form: a clear bit stands for +0.0, and IEEE
+// a + (+0.0) differs from a for a = -0.0 (the sum is +0.0) and for a
+// signalling NaN (it is quieted); here such accumulator words keep their
+// bits.  in[b] 16-byte aligned, acc[b] aligned to the accumulator's word,
+// accCapacity[b] in accumulator words.  Status as floatDecompressSparse:
+// outSuccess_dev[b] = 1 iff the dense part is valid for this config and
+// accCapacity[b] >= n; outSize_dev[b] = n always (it comes from the sparse
+// header).  A failing member's accumulator is neither read nor written, and
+// nothing outside the set positions of acc[b][0 .. n) ever is.  Overlapping
+// accumulators are the caller's error.  config.useChecksum must be false, for
+// floatDecompressAccumulate's reason (archives written with a checksum decode
+// normally).  No host synchronisation, no allocation outside `res`.
+void floatDecompressSparseAccumulate(StackDeviceMemory& res,
+                                     const FloatDecompressConfig& config,
+                                     uint32_t numInBatch, const void** in,
+                                     void** acc, const uint32_t* accCapacity,
+                                     FloatType accType, uint8_t* outSuccess_dev,
+                                     uint32_t* outSize_dev, hipStream_t stream);
+
 // Row gather with device-resident indices from a dense float archive that
 // holds a table [R, rowWords] (see ansGatherRows, GpuANSCodec.h: the same
 // rules, in float words; out_dev word-aligned).  Sparse archives are not

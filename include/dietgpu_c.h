@@ -207,6 +207,20 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int float_type, int 
                                         uint8_t* out_success_dev, uint32_t* out_size_dev,
                                         void* stream);
 
+/* ... of sparse float archives (floatDecompressSparseAccumulate,
+ * GpuFloatCodec.h; in[b] 16-byte aligned): acc[b][i] += word i of the element
+ * for every i whose bitmap bit is set, i.e. whose word is not +0.0 bitwise.
+ * The other accumulator words are neither read nor written, so an
+ * accumulator word of -0.0 (or a signalling NaN) under a zero word keeps its
+ * bits, where the dense form's a + (+0.0) would not.  Same arguments;
+ * out_success_dev[b] = 1 iff the dense part is valid and acc_capacity[b] >= n,
+ * out_size_dev[b] = n always (dietgpu_float_decompress_sparse's status). */
+int dietgpu_float_decompress_sparse_accumulate(dietgpu_stack* res, int float_type, int prob_bits,
+                                               uint32_t num_in_batch, const void** in, void** acc,
+                                               const uint32_t* acc_capacity, int acc_type,
+                                               uint8_t* out_success_dev, uint32_t* out_size_dev,
+                                               void* stream);
+
 /* Row gather with device-resident indices (ansGatherRows / floatGatherRows,
  * GpuANSCodec.h): the archive holds a table [R, row_words]; idx_dev holds
  * num_idx row indices in device memory, int32 or (idx_is_64 != 0) int64.
@@ -227,7 +241,7 @@ int dietgpu_float_gather_rows(dietgpu_stack* res, int float_type, int prob_bits,
 
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "hist", "coalesce") is bracketed
+ * "decode_gather", "hist", "coalesce", "sparse", "sparse_accumulate") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);

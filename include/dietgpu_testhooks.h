@@ -57,6 +57,14 @@ int dietgpu_test_sparse_range_config(dietgpu_stack* res, int float_type, int use
                                      uint32_t first, uint32_t count, void* out, uint8_t* out_success_dev,
                                      uint32_t* out_size_dev, void* stream);
 
+/* Calls floatDecompressSparseAccumulate for one member with `use_checksum`
+ * set in its config and any acc_type (FloatType values; the C ABI refuses a
+ * bad pair itself and carries no checksum flag).  DIETGPU_ERR_INVALID when the
+ * entry point throws, DIETGPU_OK after an accumulate. */
+int dietgpu_test_sparse_accumulate_config(dietgpu_stack* res, int float_type, int use_checksum, int acc_type,
+                                          const void* in, void* acc, uint32_t acc_capacity,
+                                          uint8_t* out_success_dev, uint32_t* out_size_dev, void* stream);
+
 /* The same for the row gather's C++ entry points (floatGatherRows,
  * ansGatherRows; float_type 0 = the byte codec): num_idx int64 indices at
  * idx_dev, rows of row_words words at a stride of row_words. */
