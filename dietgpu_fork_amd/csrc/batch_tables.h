@@ -122,6 +122,62 @@ struct SplitColumns : SizeColumn {
   }
 };
 
+inline void checkOutAligned(const void* p, const char* what) {
+  DG_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0,
+           what << " must be 16-byte aligned (archives are written with 16 B stores)");
+}
+
+// Archive i of a range or accumulate call: 4-byte aligned for a dense archive
+// (the decoder reads the headers with scalar loads, which drop the low two
+// address bits; the full decoders do not check this), 16-byte for a sparse one
+// (the compressor requires it of its output; the bitmap is read as u64).
+inline void checkArchiveAligned(uint64_t address, uint32_t i, uint32_t align) {
+  DG_CHECK(address % align == 0, "archive " << i << " must be " << align << "-byte aligned");
+}
+
+// The tables of a batch and the descriptors that refer to them.
+struct BatchTables {
+  DeviceTables t;
+  BatchDesc in, out;
+  BatchDesc out2;            // pointerBatch's extra column, if asked for
+  uint32_t maxSize = 0;      // the largest size (compress) or capacity (decode)
+  bool inAligned16 = false;  // compress: every input starts 16 B-aligned
+};
+
+// in[i] -> out[i]; `sizes` are the inputs' sizes (compress) or the outputs'
+// capacities (decode).  `unit` is the size of the codec's unit in bytes: 1 for
+// the byte codec, the word size for the float codec (whose pointers must be
+// aligned to it; 1 checks nothing).  out2Offset (the sparse compressor's): a
+// third address column, out[i] + out2Offset(sizes[i]), as BatchTables::out2.
+inline BatchTables pointerBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void** in, void** out,
+                                const uint32_t* sizes, bool compress, uint32_t unit,
+                                uint64_t (*out2Offset)(uint32_t) = nullptr) {
+  const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
+  for (uint32_t i = 0; i < nb; ++i) {
+    if (compress) {
+      DG_CHECK(ip[i] % unit == 0, "float input " << i << " not aligned to its word size");
+      checkOutAligned(out[i], "out[i]");
+    } else {
+      DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
+    }
+  }
+  const SizeColumn sz(sizes, nb);
+  BatchTables b;
+  if (out2Offset) {
+    std::vector<uint64_t> op2(nb);
+    for (uint32_t i = 0; i < nb; ++i) op2[i] = op[i] + out2Offset(sz.sizes[i]);
+    b.t = uploadTables(res, s, {&ip, &op, &op2}, sz.sizes, true);
+    b.out2 = b.t.tag(BatchDesc::pointers(b.t.u64[2], nullptr));
+  } else {
+    b.t = uploadTables(res, s, {&ip, &op}, sz.sizes, true);
+  }
+  b.in = b.t.tag(BatchDesc::pointers(b.t.u64[0], compress ? b.t.u32 : nullptr));
+  b.out = b.t.tag(BatchDesc::pointers(b.t.u64[1], compress ? nullptr : b.t.u32));
+  b.maxSize = sz.maxSize;
+  b.inAligned16 = allAligned16(ip);
+  return b;
+}
+
 // Device copy of inline tables for kernels without an InlineTable argument,
 // allocated in the calling driver's scope (the arena is LIFO) and only when
 // the tables are inline.  A one-element batch needs no copy at all: its

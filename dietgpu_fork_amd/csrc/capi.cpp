@@ -10,6 +10,7 @@
 #include "dietgpu/GpuANSCodec.h"
 #include "dietgpu/GpuFloatCodec.h"
 #include "dietgpu/StackDeviceMemory.h"
+#include "entry_checks.h"
 #include "profile.h"
 #include "sync_arena.h"
 
@@ -325,10 +326,8 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int ft, int pb, uint
     // (before the stack or any pointer is looked at: a bad pair is refused
     // whatever else the call holds)
     const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
-    DG_CHECK(acc_type == ft || ((ft == 1 || ft == 2) && acc_type == 3),
-             "acc_type " << acc_type << " does not go with float_type " << ft
-                         << " (float_type itself, or 3 for float_type 1 / 2)");
-    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    checkAccTypeC(ft, acc_type);
+    checkProbBits(pb);
     floatDecompressAccumulate(R(res), cfg, nb, in, acc, cap, FloatType(acc_type), succ, sizes, S(stream));
     return DIETGPU_OK;
   });
@@ -340,10 +339,8 @@ int dietgpu_float_decompress_sparse_accumulate(dietgpu_stack* res, int ft, int p
   return guarded([&] {
     // (the same order of checks as dietgpu_float_decompress_accumulate)
     const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
-    DG_CHECK(acc_type == ft || ((ft == 1 || ft == 2) && acc_type == 3),
-             "acc_type " << acc_type << " does not go with float_type " << ft
-                         << " (float_type itself, or 3 for float_type 1 / 2)");
-    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+    checkAccTypeC(ft, acc_type);
+    checkProbBits(pb);
     floatDecompressSparseAccumulate(R(res), cfg, nb, in, acc, cap, FloatType(acc_type), succ, sizes, S(stream));
     return DIETGPU_OK;
   });
@@ -355,10 +352,8 @@ int dietgpu_ans_gather_rows(dietgpu_stack* res, int pb, const void* archive_dev,
                             uint32_t num_idx, const void* idx_dev, int idx_is_64, void* out_dev,
                             uint64_t out_row_stride, uint8_t* succ, void* stream) {
   return guarded([&] {
-    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
-    DG_CHECK(row_words >= 1, "rowWords must be at least 1");
-    DG_CHECK(out_row_stride >= row_words,
-             "outRowStrideWords (" << out_row_stride << ") must be at least rowWords (" << row_words << ")");
+    checkProbBits(pb);
+    checkGatherRows(row_words, out_row_stride);
     ansGatherRows(R(res), ANSCodecConfig(pb, false), archive_dev, row_words, num_idx, idx_dev, idx_is_64 != 0,
                   out_dev, out_row_stride, succ, S(stream));
     return DIETGPU_OK;
@@ -370,10 +365,8 @@ int dietgpu_float_gather_rows(dietgpu_stack* res, int ft, int pb, const void* ar
                               uint64_t out_row_stride, uint8_t* succ, void* stream) {
   return guarded([&] {
     const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
-    DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
-    DG_CHECK(row_words >= 1, "rowWords must be at least 1");
-    DG_CHECK(out_row_stride >= row_words,
-             "outRowStrideWords (" << out_row_stride << ") must be at least rowWords (" << row_words << ")");
+    checkProbBits(pb);
+    checkGatherRows(row_words, out_row_stride);
     floatGatherRows(R(res), cfg, archive_dev, row_words, num_idx, idx_dev, idx_is_64 != 0, out_dev, out_row_stride,
                     succ, S(stream));
     return DIETGPU_OK;

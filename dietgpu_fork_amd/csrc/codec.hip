@@ -45,10 +45,6 @@ uint32_t residentSlots(const void* kernel, int threads, uint32_t dynLds) {
                                    [&](int dev) { return occupancySlots(dev, kernel, threads, dynLds); });
 }
 
-void checkProbBits(int pb) {
-  DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -406,8 +402,6 @@ void decodeBatchDevice(const DecodeCall& c) {
   DG_CHECK(false, "decode form " << int(c.form) << " does not go with float type " << FT);
 }
 
-static void checkArchiveAligned4(uint64_t address, uint32_t i);
-
 // A row gather (k_gather, gather.h): rows idx_dev[0 .. numIdx)
 // of the [R, rowWords] table that the archive holds.  One launch of a
 // persistent grid (planGather, decode_plan.h); no host table, no upload, no
@@ -418,15 +412,13 @@ void gatherRowsDevice(int pb, const void* archive_dev, uint32_t rowWords, uint32
                       bool idxIs64, void* out_dev, uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
                       hipStream_t s) {
   checkProbBits(pb);
-  DG_CHECK(rowWords >= 1, "rowWords must be at least 1");
-  DG_CHECK(outRowStrideWords >= rowWords,
-           "outRowStrideWords (" << outRowStrideWords << ") must be at least rowWords (" << rowWords << ")");
+  checkGatherRows(rowWords, outRowStrideWords);
   DG_CHECK(planGather(numIdx, rowWords, 1).valid,
            "too many indices: numIdx (" << numIdx << ") times the " << gatherBlocksPerRow(rowWords)
                                         << " blocks a row of " << rowWords << " words touches must be below 2^32");
   if (numIdx == 0) return;
   DG_CHECK(archive_dev && idx_dev && out_dev, "archive_dev, idx_dev and out_dev must not be null");
-  checkArchiveAligned4(reinterpret_cast<uintptr_t>(archive_dev), 0);
+  checkArchiveAligned(reinterpret_cast<uintptr_t>(archive_dev), 0, 4);
   DG_CHECK(reinterpret_cast<uintptr_t>(idx_dev) % (idxIs64 ? 8 : 4) == 0, "idx_dev not aligned to its index size");
   DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % sizeof(typename FloatTraits<FT>::WordT) == 0,
            "out_dev not aligned to its word size");
@@ -470,53 +462,12 @@ std::vector<std::pair<int, std::string>> verifyChecksums(const DecodeCall& c, bo
   return errs;
 }
 
-static void checkOutAligned(const void* p, const char* what) {
-  DG_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0,
-           what << " must be 16-byte aligned (archives are written with 16 B stores)");
-}
-
-// Archive i of a range or accumulate call (the decoder reads the headers with
-// scalar loads, which drop the low two address bits; the full decoders do not
-// check this).
-static void checkArchiveAligned4(uint64_t address, uint32_t i) {
-  DG_CHECK(address % 4 == 0, "archive " << i << " must be 4-byte aligned");
-}
-
 // ---------------------------------------------------------------------------
-// batch tables of the pointer and split-size entry points.  `unit` is the
-// size of the codec's unit in bytes: 1 for the byte codec, the word size for
-// the float codec (whose pointers must be aligned to it).
+// batch tables of the split-size and range entry points (the pointer ones':
+// pointerBatch, batch_tables.h).  `unit` is the size of the codec's unit in
+// bytes: 1 for the byte codec, the word size for the float codec (whose
+// pointers must be aligned to it).
 // ---------------------------------------------------------------------------
-struct BatchTables {
-  DeviceTables t;
-  BatchDesc in, out;
-  uint32_t maxSize = 0;      // the largest size (compress) or capacity (decode)
-  bool inAligned16 = false;  // compress: every input starts 16 B-aligned
-};
-
-// in[i] -> out[i]; `sizes` are the inputs' sizes (compress) or the outputs'
-// capacities (decode)
-static BatchTables pointerBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void** in, void** out,
-                                const uint32_t* sizes, bool compress, uint32_t unit) {
-  const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
-  for (uint32_t i = 0; i < nb; ++i) {
-    if (compress) {
-      DG_CHECK(ip[i] % unit == 0, "float input " << i << " not aligned to its word size");
-      checkOutAligned(out[i], "out[i]");
-    } else {
-      DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
-    }
-  }
-  const SizeColumn sz(sizes, nb);
-  BatchTables b;
-  b.t = uploadTables(res, s, {&ip, &op}, sz.sizes, true);
-  b.in = b.t.tag(BatchDesc::pointers(b.t.u64[0], compress ? b.t.u32 : nullptr));
-  b.out = b.t.tag(BatchDesc::pointers(b.t.u64[1], compress ? nullptr : b.t.u32));
-  b.maxSize = sz.maxSize;
-  b.inAligned16 = allAligned16(ip);
-  return b;
-}
-
 // Compress: the elements of `base` -> rows of out_dev.  Decode (archives
 // non-null): archives[i] -> the elements of `base`.
 static BatchTables splitBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const void* base,
@@ -546,7 +497,7 @@ static BatchTables rangeBatch(StackDeviceMemory& res, hipStream_t s, uint32_t nb
   const auto ip = addressColumn(in, nb), op = addressColumn(out, nb);
   for (uint32_t i = 0; i < nb; ++i) {
     DG_CHECK(op[i] % unit == 0, "float output " << i << " not aligned to its word size");
-    checkArchiveAligned4(ip[i], i);
+    checkArchiveAligned(ip[i], i, 4);
   }
   const SizeColumn cnt(count, nb), fst(first, nb);
   BatchTables b;
@@ -566,33 +517,6 @@ static void checkInteriorSplits(const uint32_t* splitSizes, uint32_t nb) {
   for (uint32_t i = 0; i + 1 < nb; ++i)
     DG_CHECK(splitSizes[i] % kANSRequiredAlignment == 0,
              "interior split sizes must be multiples of " << kANSRequiredAlignment);
-}
-
-// the calls of a batch built above
-static CompressCall compressCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
-                                 uint32_t* outSize_dev) {
-  CompressCall c{res, s};
-  c.nb = nb;
-  c.in = b.in;
-  c.maxSize = b.maxSize;
-  c.out = b.out;
-  c.outSize_dev = outSize_dev;
-  c.tabs = &b.t;
-  c.inAligned16 = b.inAligned16;
-  return c;
-}
-
-static DecodeCall decodeCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
-                             uint8_t* outSuccess_dev, uint32_t* outSize_dev) {
-  DecodeCall c{res, s};
-  c.nb = nb;
-  c.in = b.in;
-  c.out = b.out;
-  c.maxCapacity = b.maxSize;
-  c.outSuccess_dev = outSuccess_dev;
-  c.outSize_dev = outSize_dev;
-  c.tabs = &b.t;
-  return c;
 }
 
 // ... of a rangeBatch, whose maxSize counts blocks
@@ -714,7 +638,7 @@ ANSDecodeStatus ansDecodeBatchSplitSize(StackDeviceMemory& res, const ANSCodecCo
 void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config, uint32_t numInBatch,
                          const void** in, const uint32_t* first, const uint32_t* count, void** out,
                          uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
-  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  checkNoChecksum(config.useChecksum, PartialDecode::kRange);
   if (numInBatch == 0) return;
   const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, 1);
   DecodeCall c = rangeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
@@ -725,7 +649,7 @@ void ansDecodeBatchRange(StackDeviceMemory& res, const ANSCodecConfig& config, u
 void ansGatherRows(StackDeviceMemory& res, const ANSCodecConfig& config, const void* archive_dev,
                    uint32_t rowWords, uint32_t numIdx, const void* idx_dev, bool idxIs64, void* out_dev,
                    uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t stream) {
-  DG_CHECK(!config.useChecksum, "a row gather cannot verify a checksum (it covers the whole element)");
+  checkNoChecksum(config.useChecksum, PartialDecode::kGather);
   (void)res;  // nothing is allocated: the call can be captured in a graph
   gatherRowsDevice<0>(config.probBits, archive_dev, rowWords, numIdx, idx_dev, idxIs64, out_dev, outRowStrideWords,
                       outSuccess_dev, stream);
@@ -778,12 +702,6 @@ uint32_t getMaxFloatCompressedSize(FloatType ft, uint32_t size) {
   if (ft == FloatType::kFloat64) base += getMaxCompressedSize(size);
   DG_CHECK(base <= uint64_t(UINT32_MAX), "input too large: " << size << " float words");
   return uint32_t(base);
-}
-
-static void checkFloatConfig(const FloatCodecConfig& c) {
-  DG_CHECK(!c.ansConfig.useChecksum,
-           "ANS-level checksumming is not allowed in float mode (use FloatCodecConfig.useChecksum)");
-  DG_CHECK(c.floatType != FloatType::kUndefined && uint32_t(c.floatType) <= 4, "bad float type");
 }
 
 void floatCompressDescs(const FloatCompressConfig& config, CompressCall c) {
@@ -860,7 +778,7 @@ void floatDecompressRange(StackDeviceMemory& res, const FloatDecompressConfig& c
                           const void** in, const uint32_t* first, const uint32_t* count, void** out,
                           uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
   checkFloatConfig(config);
-  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  checkNoChecksum(config.useChecksum, PartialDecode::kRange);
   if (numInBatch == 0) return;
   const auto b = rangeBatch(res, stream, numInBatch, in, first, count, out, floatWordBytes(int(config.floatType)));
   floatDecompressDescs(config, rangeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev));
@@ -870,7 +788,7 @@ void floatGatherRows(StackDeviceMemory& res, const FloatDecompressConfig& config
                      uint32_t rowWords, uint32_t numIdx, const void* idx_dev, bool idxIs64, void* out_dev,
                      uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t stream) {
   checkFloatConfig(config);
-  DG_CHECK(!config.useChecksum, "a row gather cannot verify a checksum (it covers the whole element)");
+  checkNoChecksum(config.useChecksum, PartialDecode::kGather);
   (void)res;  // nothing is allocated: the call can be captured in a graph
   dispatchFloatType(config.floatType, [&](auto ft) {
     gatherRowsDevice<decltype(ft)::value>(config.ansConfig.probBits, archive_dev, rowWords, numIdx, idx_dev, idxIs64,
@@ -881,20 +799,8 @@ void floatGatherRows(StackDeviceMemory& res, const FloatDecompressConfig& config
 void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,
                                const void** in, void** acc, const uint32_t* accCapacity, FloatType accType,
                                uint8_t* outSuccess_dev, uint32_t* outSize_dev, hipStream_t stream) {
-  checkFloatConfig(config);
-  DG_CHECK(!config.useChecksum,
-           "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded words)");
-  const bool half = config.floatType == FloatType::kFloat16 || config.floatType == FloatType::kBFloat16;
-  const bool wide = half && accType == FloatType::kFloat32;
-  DG_CHECK(accType == config.floatType || wide,
-           "accumulator type " << int(accType) << " does not go with float type " << int(config.floatType)
-                               << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
-  if (numInBatch == 0) return;
-  for (uint32_t i = 0; i < numInBatch; ++i) checkArchiveAligned4(reinterpret_cast<uintptr_t>(in[i]), i);
-  const auto b = pointerBatch(res, stream, numInBatch, in, acc, accCapacity, false, floatWordBytes(int(accType)));
-  DecodeCall c = decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev);
-  c.form = wide ? DecodeForm::kAccumulateFp32 : DecodeForm::kAccumulate;
-  floatDecompressDescs(config, c);
+  accumulateEntry(res, config, numInBatch, in, acc, accCapacity, accType, outSuccess_dev, outSize_dev, stream, 4,
+                  [&](const DecodeCall& c) { floatDecompressDescs(config, c); });
 }
 
 FloatDecompressStatus floatDecompressSplitSize(StackDeviceMemory& res,

@@ -9,10 +9,12 @@
 #include <utility>
 #include <vector>
 
+#include "archive.h"
 #include "batch.h"
 #include "batch_tables.h"
 #include "compress_plan.h"
 #include "decode_plan.h"
+#include "entry_checks.h"
 #include "dietgpu/GpuFloatCodec.h"
 
 namespace dietgpu {
@@ -81,6 +83,52 @@ struct DecodeCall {
   // full only: maxCapacity may far exceed the archives' sizes
   bool capacityOnly = false;
 };
+
+// The calls of a batch built by batch_tables.h (b outlives the call).
+inline CompressCall compressCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
+                                 uint32_t* outSize_dev) {
+  CompressCall c{res, s};
+  c.nb = nb;
+  c.in = b.in;
+  c.maxSize = b.maxSize;
+  c.out = b.out;
+  c.outSize_dev = outSize_dev;
+  c.tabs = &b.t;
+  c.inAligned16 = b.inAligned16;
+  return c;
+}
+
+inline DecodeCall decodeCall(StackDeviceMemory& res, hipStream_t s, uint32_t nb, const BatchTables& b,
+                             uint8_t* outSuccess_dev, uint32_t* outSize_dev) {
+  DecodeCall c{res, s};
+  c.nb = nb;
+  c.in = b.in;
+  c.out = b.out;
+  c.maxCapacity = b.maxSize;
+  c.outSuccess_dev = outSuccess_dev;
+  c.outSize_dev = outSize_dev;
+  c.tabs = &b.t;
+  return c;
+}
+
+// The two decode-and-accumulate entry points: every
+// host check, before the first allocation, upload or launch, then
+// run(call) on the batch's DecodeCall.  archiveAlign: 4 dense, 16 sparse
+// (checkArchiveAligned).
+template <typename Run>
+void accumulateEntry(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t nb, const void** in,
+                     void** acc, const uint32_t* accCapacity, FloatType accType, uint8_t* outSuccess_dev,
+                     uint32_t* outSize_dev, hipStream_t stream, uint32_t archiveAlign, Run&& run) {
+  checkFloatConfig(config);
+  checkNoChecksum(config.useChecksum, PartialDecode::kAccumulate);
+  const DecodeForm form = accumulateForm(config.floatType, accType);
+  if (nb == 0) return;
+  for (uint32_t i = 0; i < nb; ++i) checkArchiveAligned(reinterpret_cast<uintptr_t>(in[i]), i, archiveAlign);
+  const auto b = pointerBatch(res, stream, nb, in, acc, accCapacity, false, floatWordBytes(int(accType)));
+  DecodeCall c = decodeCall(res, stream, nb, b, outSuccess_dev, outSize_dev);
+  c.form = form;
+  run(c);
+}
 
 // f(std::integral_constant<int, FT>{}) for the float type's FT (1 fp16,
 // 2 bf16, 3 fp32, 4 fp64; the type has been validated).

@@ -321,6 +321,22 @@ static __global__ __launch_bounds__(kThreads) void k_normalize(NormArgs a, uint3
 // lanes l and l + 16 of a wave half share a column.
 // ---------------------------------------------------------------------------
 constexpr int kHistCols = 32;
+
+// The end of the histogram-row protocol (SyncLease::rows, sync_arena.h), by the
+// 256 threads of a workgroup, thread t for bin t: `sum`, the bin's count in
+// slot `slot` (a k_hist chunk, a k_sparseCount tile) of element-and-segment
+// `es` = seg * nb + b, is added into row slot % nRows of `rows`
+// [segs][nb][nRows][256], and the first nRows slots zero the same row of the
+// other buffer, `zeroNext`, for the next call.  The arena records that buffer
+// as clean on the strength of this: every slot below nRows of a launch that
+// holds a rows lease comes here, with sum 0 if it has nothing to count.
+__device__ __forceinline__ void commitHistRow(uint32_t* __restrict__ rows, uint32_t* __restrict__ zeroNext,
+                                              uint64_t es, uint32_t slot, uint32_t nRows, uint32_t sum) {
+  const uint64_t at = (es * nRows + slot % nRows) * kNumSymbols + threadIdx.x;
+  if (sum) __hip_atomic_fetch_add(G(rows) + at, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (slot < nRows) G(zeroNext)[at] = 0;
+}
+
 // kRows (small three-kernel grids, k_encode's prologue normalisation; kProRows
 // and proRowsOf: compress_plan.h): chunk c adds its counts with atomics into
 // row c % P of [segs][nb][P][256], P = proRowsOf(chunks).  `zeroNext`: the same
@@ -424,11 +440,7 @@ __global__ __launch_bounds__(kThreads) void k_hist(BatchDesc in, uint32_t batchO
 #pragma unroll
     for (int k = 0; k < kHistCols; ++k) sum += hs[s][tid * kHistCols + ((k + tid) & (kHistCols - 1))];
     if constexpr (kRows) {
-      const uint32_t P = proRowsOf(chunksPerElem);
-      const uint64_t row = (uint64_t(s) * numInBatch + b) * P + c % P;
-      if (sum) __hip_atomic_fetch_add(G(partHist) + row * kNumSymbols + tid, sum, __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-      if (c < P) G(zeroNext)[row * kNumSymbols + tid] = 0;
+      commitHistRow(partHist, zeroNext, uint64_t(s) * numInBatch + b, c, proRowsOf(chunksPerElem), sum);
     } else {
       gp<uint32_t> dst = G(partHist) + ((uint64_t(s) * numInBatch + b) * chunksPerElem + c) * kNumSymbols + tid;
       if (na.arrive) stSc1(dst, sum);  // read by this launch's last arrival

@@ -1,0 +1,73 @@
+// The argument checks that more than one entry point makes: the C++ API of
+// the dense codecs (codec.hip) and of the sparse codec (sparse.hip), and the C
+// ABI (capi.cpp), which repeats the ones that must refuse a call before the
+// stack or any pointer is looked at.  Host only.
+#pragma once
+
+#include <cstdint>
+
+#include "common.h"
+#include "decode_plan.h"
+#include "dietgpu/GpuFloatCodec.h"
+
+namespace dietgpu {
+
+inline void checkProbBits(int pb) {
+  DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
+}
+
+inline void checkFloatConfig(const FloatCodecConfig& c) {
+  DG_CHECK(!c.ansConfig.useChecksum,
+           "ANS-level checksumming is not allowed in float mode (use FloatCodecConfig.useChecksum)");
+  DG_CHECK(c.floatType != FloatType::kUndefined && uint32_t(c.floatType) <= 4, "bad float type");
+}
+
+// The forms that decode part of an element, or add it to something: none can
+// verify the archive's checksum, and a config that asks for it is refused.
+enum class PartialDecode { kRange, kGather, kAccumulate };
+
+inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
+  switch (what) {
+    case PartialDecode::kRange:
+      DG_CHECK(!useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+      break;
+    case PartialDecode::kGather:
+      DG_CHECK(!useChecksum, "a row gather cannot verify a checksum (it covers the whole element)");
+      break;
+    case PartialDecode::kAccumulate:
+      DG_CHECK(!useChecksum,
+               "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded "
+               "words)");
+      break;
+  }
+}
+
+// An accumulator has the archive's own float type, or is fp32 for an fp16 /
+// bf16 archive (types as FloatType's values; anything else pairs with nothing).
+inline bool accumulatorPairs(int floatType, int accType) {
+  return floatType >= 1 && floatType <= 4 && (accType == floatType || (floatType <= 2 && accType == 3));
+}
+
+// ... as the C++ API refuses a bad pair, and the form of a good one
+inline DecodeForm accumulateForm(FloatType floatType, FloatType accType) {
+  DG_CHECK(accumulatorPairs(int(floatType), int(accType)),
+           "accumulator type " << int(accType) << " does not go with float type " << int(floatType)
+                               << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
+  return accType == floatType ? DecodeForm::kAccumulate : DecodeForm::kAccumulateFp32;
+}
+
+// ... and as the C ABI does, in its parameters' names
+inline void checkAccTypeC(int float_type, int acc_type) {
+  DG_CHECK(accumulatorPairs(float_type, acc_type),
+           "acc_type " << acc_type << " does not go with float_type " << float_type
+                       << " (float_type itself, or 3 for float_type 1 / 2)");
+}
+
+// The row shape of a gather: rows of rowWords words, outRowStrideWords apart.
+inline void checkGatherRows(uint32_t rowWords, uint64_t outRowStrideWords) {
+  DG_CHECK(rowWords >= 1, "rowWords must be at least 1");
+  DG_CHECK(outRowStrideWords >= rowWords,
+           "outRowStrideWords (" << outRowStrideWords << ") must be at least rowWords (" << rowWords << ")");
+}
+
+}  // namespace dietgpu

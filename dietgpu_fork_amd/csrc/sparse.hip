@@ -38,6 +38,7 @@
 #include "decode.h"
 #include "encode.h"
 #include "profile.h"
+#include "sparse_plan.h"
 #include "sync_arena.h"
 
 namespace dietgpu {
@@ -45,6 +46,12 @@ namespace dietgpu {
 namespace {
 
 constexpr uint32_t kTileWords = 4096;   // 4 waves x 16 steps x 64 lanes
+// Decompression works on 1024-word chunks (16 bitmap words, one wave).
+constexpr uint32_t kChunkWords = 1024;
+constexpr uint32_t kChunkRows = kChunkWords / 64;  // 64-word rows, one bitmap word each
+static_assert(kTileWords == splan::kTileWords && kChunkWords == splan::kChunkWords &&
+                  kThreads == splan::kThreads && kWaves == splan::kWaves && kBlockSize == cplan::kBlockWords,
+              "sparse_plan.h restates the kernels' constants");
 
 template <int FT>
 using WordOf = typename FloatTraits<FT>::WordT;
@@ -171,12 +178,7 @@ __device__ __forceinline__ void sparseCountTile(const BatchDesc& in, gp<uint8_t>
 #pragma unroll
       for (uint32_t k = 0; k < kCols; ++k) sum += hs[sg][tid * kCols + ((k + tid) & (kCols - 1))];
       // few adds per address: the tiles of an element spread over nRows rows
-      const uint64_t row = (uint64_t(sg) * numInBatch + b) * nRows + tile % nRows;
-      if (sum)
-        __hip_atomic_fetch_add(G(histRows) + row * kNumSymbols + tid, sum, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      // the same row of the arena's other buffer, zeroed for the next call
-      if (tile < nRows) G(zeroNext)[row * kNumSymbols + tid] = 0;
+      commitHistRow(histRows, zeroNext, uint64_t(sg) * numInBatch + b, tile, nRows, sum);
     }
   }
 }
@@ -197,8 +199,9 @@ __device__ __forceinline__ void sparseCountTile(const BatchDesc& in, gp<uint8_t>
 // added into row tile % nRows of [segments][nb][nRows][256] (PartialHist),
 // so the dense codec skips its histogram pass over the list.  The rows are
 // the stream's sync-arena row buffer (SyncLease::rows, zero on entry); the
-// first nRows tiles zero the same rows of the other buffer for the next call
-// (`zeroNext`), so no zeroing launch precedes this one (1 x 15M fp32: a
+// first nRows tiles, empty ones included, zero the same rows of the other
+// buffer for the next call (`zeroNext`; commitHistRow, encode.h), so no
+// zeroing launch precedes this one (1 x 15M fp32: a
 // 4.7 us k_zero of 64 KB before).  (Normalising in the element's last-arriving tile instead of the
 // dense codec's k_normalize launch made every tile pay a store drain and a
 // counter round trip: c4 1 x 15M fp32 compress 70 -> 95 us.)
@@ -227,6 +230,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
   const uint32_t t0 = tile * kTileWords;
   if (t0 >= n) {
     if (tid == 0) tileCounts[uint64_t(b) * tilesPerElem + tile] = 0;
+    // (an empty element's tile 0 among them: whoever holds a rows lease zeroes
+    // its rows of the other buffer, whatever the sizes)
+    if constexpr (kHist) {
+      for (int sg = 0; sg < kSegs; ++sg)
+        commitHistRow(histRows, zeroNext, uint64_t(sg) * numInBatch + b, tile, nRows, 0);
+    }
   } else {
     sparseCountTile<FT, kVec, kHist>(in, o, b, n, tile, numInBatch, tilesPerElem, tileCounts, staging, histRows,
                                      zeroNext, nRows, buf, hs, waveCnt);
@@ -311,16 +320,12 @@ __global__ __launch_bounds__(kThreads) void k_sparseGather(BatchDesc in, uint32_
   }
 }
 
-// Decompression works on 1024-word chunks (16 bitmap words, one wave).
-constexpr uint32_t kChunkWords = 1024;
-constexpr uint32_t kChunkRows = kChunkWords / 64;  // 64-word rows, one bitmap word each
-
 // The set bits of chunk c of the bitmap bm of an N-word element: the popcount
 // of its 128 bitmap bytes, bits at or past N cut (the bitmap's padding is the
 // reference's uninitialised bytes); 0 for a chunk at or past N.  Words are
-// counted from the chunk's start, which cannot wrap (c < 2^22 + 256).  The
-// 128 B read may run past the padded bitmap into the dense archive that
-// follows it (>= 576 B), never past the archive.
+// counted from the chunk's start, which cannot wrap (c < 2^22 + 256).  Only
+// the bitmap words that start below N are read, so the reads stay inside the
+// padded bitmap.
 __device__ __forceinline__ uint32_t chunkPopcount(gp<const uint8_t> bm, uint32_t c, uint32_t n) {
   if (uint64_t(c) * kChunkWords >= n) return 0;
   const uint32_t left = n - c * kChunkWords;  // the element's words from the chunk's start on
@@ -337,6 +342,35 @@ __device__ __forceinline__ uint32_t chunkPopcount(gp<const uint8_t> bm, uint32_t
     cnt += uint32_t(__popcll(m));
   }
   return cnt;
+}
+
+// One thread per chunk (d1 / r1): thread t counts chunk c (0 for c >= nChunks)
+// of the N-word element with bitmap bm, the workgroup scans its 256 counts,
+// and the chunk's exclusive prefix goes to *pre (this thread's chunkPre entry,
+// not written for c >= nChunks), the workgroup's total to *tot (its blockTot
+// entry).
+__device__ __forceinline__ void countAndScanChunks(gp<const uint8_t> bm, uint32_t c, uint32_t nChunks, uint32_t n,
+                                                   uint32_t* red, gp<uint32_t> pre, gp<uint32_t> tot) {
+  const uint32_t cnt = c < nChunks ? chunkPopcount(bm, c, n) : 0u;
+  uint32_t total = 0;
+  const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
+  if (c < nChunks) *pre = excl;
+  if (threadIdx.x == 0) *tot = total;
+}
+
+// Lane k < 16: bitmap word k of chunk c of the bitmap bm, in element order
+// (bit j <-> word 1024 c + 64 k + j of the element), the bits of words at or
+// past `limit` (counted from the chunk's start) cut; 0 in the other lanes and
+// for a bitmap word wholly at or past the limit, which is not read.
+__device__ __forceinline__ uint64_t chunkBitmapWord(gp<const uint8_t> bm, uint32_t c, uint32_t limit,
+                                                    uint32_t lane) {
+  uint64_t m = 0;
+  if (lane < kChunkRows && 64 * lane < limit) {
+    m = maskToBitmap(*(gp<const uint64_t>)(bm + uint64_t(c) * (kChunkWords / 8) + 8 * lane));
+    const uint32_t rem = limit - 64 * lane;
+    if (rem < 64) m &= (1ull << rem) - 1;
+  }
+  return m;
 }
 
 // gap: x[N-1] is read from idx[N-2] + 1 (fill_in_nonzeros :139-144), one list
@@ -433,11 +467,8 @@ __global__ __launch_bounds__(kThreads) void k_sparseChunks(BatchDesc in, uint32_
     densePtrs[b] = reinterpret_cast<uint64_t>(in.start(b) + sparsePrefixBytes(n));
     sizes[b] = n;
   }
-  const uint32_t cnt = c < chunksPerElem ? chunkPopcount(a + kSparseHeaderBytes, c, n) : 0u;
-  uint32_t total = 0;
-  const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
-  if (c < chunksPerElem) chunkPre[uint64_t(b) * chunksPerElem + c] = excl;
-  if (threadIdx.x == 0) blockTot[uint64_t(b) * blocksPerElem + blockIdx.x] = total;
+  countAndScanChunks(a + kSparseHeaderBytes, c, chunksPerElem, n, red, G(chunkPre) + uint64_t(b) * chunksPerElem + c,
+                     G(blockTot) + uint64_t(b) * blocksPerElem + blockIdx.x);
 }
 
 // d3: expand the decoded nonzero list into the output (fill_in_nonzeros
@@ -480,12 +511,7 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   const uint32_t i0 = c * kChunkWords;
   if (!ok || c >= chunksPerElem || i0 >= n) return;
   gp<const uint8_t> bm = (gp<const uint8_t>)in.start(b) + kSparseHeaderBytes;
-  uint64_t mv = 0;
-  if (lane < kChunkRows && i0 + 64 * lane < n) {
-    mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
-    const uint32_t rem = n - (i0 + 64 * lane);
-    if (rem < 64) mv &= (1ull << rem) - 1;
-  }
+  const uint64_t mv = chunkBitmapWord(bm, c, n - i0, lane);
   const uint32_t base = chunkListOffset(G(chunkPre) + uint64_t(b) * chunksPerElem,
                                         G(blockTot) + uint64_t(b) * blocksPerElem, c, lane);
   // only the chunk holding word n-1 looks
@@ -537,31 +563,26 @@ void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, c
   StackDeviceMemory& res = c.res;
   const hipStream_t s = c.s;
   const uint32_t nb = c.nb, maxN = c.maxSize;
-  const uint32_t tiles = std::max(1u, divUp(maxN, kTileWords));
-  auto tileCounts = res.alloc<uint32_t>(s, size_t(nb) * tiles);
+  constexpr int kSegs = FloatTraits<FT>::kSegs;
+  // the list's symbol histogram is counted here for a single element when the
+  // three-kernel dense path follows (planSparseCompress, sparse_plan.h): the
+  // dense codec then skips its histogram pass
+  const SparseCompressPlan plan = planSparseCompress(
+      kSegs, sizeof(WordOf<FT>), nb, maxN,
+      planCompressCall(FT, nb, maxN, config.useChecksum, false, /*inAligned16=*/true).singlePass);
+  const uint32_t tiles = plan.tiles, R = plan.rows;
+  const bool countHist = plan.countHist;
+  auto tileCounts = res.alloc<uint32_t>(s, plan.tileCounts);
   auto listLen = res.alloc<uint32_t>(s, nb);
   // per tile: its nonzeros in order, plus the n-2 quirk's slot
-  auto staging = res.alloc<WordOf<FT>>(s, size_t(nb) * tiles * (kTileWords + 1));
+  auto staging = res.alloc<WordOf<FT>>(s, plan.staging);
   // the compacted lists: 16 B-aligned rows of one arena allocation, lengths
   // on the device
-  const uint64_t listStride = uint64_t(roundUp(maxN, 16) + 16) * sizeof(WordOf<FT>);
-  auto list = res.alloc<uint8_t>(s, size_t(nb) * listStride);
-  BatchDesc lists = BatchDesc::strided(list.data(), listStride, 0);
+  auto list = res.alloc<uint8_t>(s, plan.listBytes);
+  BatchDesc lists = BatchDesc::strided(list.data(), plan.listStride, 0);
   lists.sizes = listLen.data();
-  // the list's symbol histogram, counted here for a single element when the
-  // three-kernel dense path follows (the single-pass compressor counts as it
-  // loads): the dense codec then skips its histogram pass (c4 1 x 15M fp32:
-  // compress 85 -> 75 us).  It lengthens every tile's workgroup, so with
-  // more elements the separate k_hist over the compacted lists is faster
-  // (5 x 15M: 155 us against 170).
-  const bool countHist =
-      nb == 1 && !planCompressCall(FT, nb, maxN, config.useChecksum, false, /*inAligned16=*/true).singlePass;
-  constexpr int kSegs = FloatTraits<FT>::kSegs;
-  const uint32_t G = tiles;
-  const uint32_t R = std::min(tiles, kReduceRows);
-  const size_t rowsBytes = countHist ? size_t(kSegs) * nb * R * kNumSymbols * 4 : 0;
-  auto table = res.alloc<uint4>(s, countHist ? size_t(kSegs) * nb * kNumSymbols : 1);
-  auto pdf = res.alloc<uint16_t>(s, countHist ? size_t(kSegs) * nb * kNumSymbols : 1);
+  auto table = res.alloc<uint4>(s, plan.tableEntries);
+  auto pdf = res.alloc<uint16_t>(s, plan.tableEntries);
   PartialHist pre{nullptr, R};
   pre.table = table.data();
   pre.pdf = pdf.data();
@@ -577,7 +598,7 @@ void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, c
     forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
       prof::Scope p("sparse", s);
       auto launch = [&](auto vecTag, auto histTag) {
-        k_sparseCount<FT, decltype(vecTag)::value, decltype(histTag)::value><<<dim3(G, ny), kThreads, 0, s>>>(
+        k_sparseCount<FT, decltype(vecTag)::value, decltype(histTag)::value><<<dim3(tiles, ny), kThreads, 0, s>>>(
             c.in, c.out, y0, nb, tiles, tileCounts.data(), staging.data(), histRows, zeroNext, R);
       };
       if (c.inAligned16) {
@@ -599,7 +620,7 @@ void sparseCompressT(const FloatCompressConfig& config, const CompressCall& c, c
     // other buffer for the next call).  The lease is the arena's newest
     // allocation and ends with this scope, before the dense codec takes its
     // own (the arena's mutex is not recursive).
-    SyncLease lease(res, s, kNoSyncRegions, false, rowsBytes);
+    SyncLease lease(res, s, kNoSyncRegions, false, plan.rowsBytes);
     pre.rows = static_cast<uint32_t*>(lease.rows[0]);
     launchAll(static_cast<uint32_t*>(lease.rows[0]), static_cast<uint32_t*>(lease.rows[1]));
   } else {
@@ -628,16 +649,15 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   const hipStream_t s = c.s;
   const bool full = c.form == DecodeForm::kFull;
   const char* family = full ? "sparse" : "sparse_accumulate";
-  const uint32_t nb = c.nb, maxCap = c.maxCapacity;
-  const uint32_t chunks = std::max(1u, divUp(maxCap, kChunkWords));
-  const uint32_t cblocks = divUp(chunks, kThreads);  // k_sparseChunks workgroups per element
+  const uint32_t nb = c.nb;
+  const SparseDecodePlan plan = planSparseDecode(sizeof(WordOf<FT>), nb, c.maxCapacity);
+  const uint32_t chunks = plan.chunks, cblocks = plan.cblocks;
   auto densePtrs = res.alloc<uint64_t>(s, nb);
   auto sizes = res.alloc<uint32_t>(s, nb);
   auto denseOk = res.alloc<uint8_t>(s, nb);
-  const uint64_t listStride = uint64_t(roundUp(maxCap, 16) + 16) * sizeof(WordOf<FT>);
-  auto list = res.alloc<uint8_t>(s, size_t(nb) * listStride);
-  auto chunkPre = res.alloc<uint32_t>(s, size_t(nb) * chunks);
-  auto blockTot = res.alloc<uint32_t>(s, size_t(nb) * cblocks);
+  auto list = res.alloc<uint8_t>(s, plan.listBytes);
+  auto chunkPre = res.alloc<uint32_t>(s, plan.chunkPre);
+  auto blockTot = res.alloc<uint32_t>(s, plan.blockTot);
   forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
     prof::Scope p(family, s);
     k_sparseChunks<<<dim3(cblocks, ny), kThreads, 0, s>>>(c.in, y0, chunks, cblocks, densePtrs.data(), sizes.data(),
@@ -648,8 +668,8 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   DecodeCall dense{res, s};
   dense.nb = nb;
   dense.in = BatchDesc::pointers(densePtrs.data(), nullptr);
-  dense.out = BatchDesc::strided(list.data(), listStride, maxCap + 1);
-  dense.maxCapacity = maxCap + 1;
+  dense.out = BatchDesc::strided(list.data(), plan.listStride, plan.denseCapacity);
+  dense.maxCapacity = plan.denseCapacity;
   dense.outSuccess_dev = denseOk.data();
   dense.streamOut = false;  // the expansion reads it
   dense.capacityOnly = true;
@@ -670,7 +690,7 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
   auto expand = [&](auto acc) {
     forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
       prof::Scope p(family, s);
-      k_sparseExpand<FT, decltype(acc)::value><<<dim3(divUp(chunks, kWaves), ny), kThreads, 0, s>>>(
+      k_sparseExpand<FT, decltype(acc)::value><<<dim3(plan.gridX, ny), kThreads, 0, s>>>(
           c.in, c.out, y0, chunks, cblocks, sizes.data(), chunkPre.data(), blockTot.data(), lists, denseOk.data(),
           c.outSuccess_dev, c.outSize_dev);
       HIP_LAUNCH_CHECK();
@@ -741,12 +761,9 @@ __global__ __launch_bounds__(kThreads) void k_sparseRangeChunks(SparseRangeTabs 
   const uint32_t n = sparseSizeOf(a, hdrOk);
   if (uint64_t(blockIdx.x) * kThreads * kChunkWords >= n) return;
   const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  const uint32_t cnt = c < nChunks ? chunkPopcount(a + kSparseHeaderBytes, c, n) : 0u;
-  uint32_t total = 0;
-  const uint32_t excl = blockExclusiveScan<kThreads>(cnt, red, &total);
   const uint64_t g = uint64_t(g0) + blockIdx.x;
-  if (c < nChunks) chunkPre[g * kThreads + threadIdx.x] = excl;
-  if (threadIdx.x == 0) blockTot[g] = total;
+  countAndScanChunks(a + kSparseHeaderBytes, c, nChunks, n, red, G(chunkPre) + g * kThreads + threadIdx.x,
+                     G(blockTot) + g);
 }
 
 // This lane's share of rank(i) of archive `bm` (its bitmap), 1 <= i <= N:
@@ -760,13 +777,7 @@ __device__ __forceinline__ uint32_t rankShare(gp<const uint8_t> bm, gp<const uin
   const uint32_t within = i - c * kChunkWords;  // 1 .. 1024 words of chunk c lie below i
   uint32_t part = totalsShare(blockTot, c / kThreads, lane);
   if (lane == 16) part += chunkPre[c];
-  if (lane < kChunkWords / 64 && 64 * lane < within) {
-    uint64_t m = maskToBitmap(*(gp<const uint64_t>)(bm + uint64_t(c) * (kChunkWords / 8) + 8 * lane));
-    const uint32_t rem = within - 64 * lane;
-    if (rem < 64) m &= (1ull << rem) - 1;
-    part += uint32_t(__popcll(m));
-  }
-  return part;
+  return part + uint32_t(__popcll(chunkBitmapWord(bm, c, within, lane)));
 }
 
 // r2: one wave per member: N, the range check, rank(first) and rank(end) ->
@@ -853,8 +864,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(80))) void
   const uint64_t info = BatchDesc::tableAt(t.archInfo, slot);
   gp<const uint8_t> a = (gp<const uint8_t>)reinterpret_cast<const uint8_t*>(BatchDesc::tableAt(t.archPtr, slot));
   gp<const uint8_t> bm = a + kSparseHeaderBytes;
-  uint64_t mv = 0;
-  if (lane < kChunkRows && 64 * lane < end - i0) mv = maskToBitmap(*(gp<const uint64_t>)(bm + i0 / 8 + 8 * lane));
+  // (the bits at or past `end` are cut: no wanted word's list index counts them)
+  const uint64_t mv = chunkBitmapWord(bm, c, end - i0, lane);
   // the chunk's rank less the slice's start
   const uint32_t base = chunkListOffset(G(chunkPre) + uint64_t(uint32_t(info)) * kThreads,
                                         G(blockTot) + uint32_t(info), c, lane) -
@@ -897,62 +908,29 @@ void sparseRangeT(const FloatDecompressConfig& config, const SparseRangeCall& c)
   StackDeviceMemory& res = c.res;
   const hipStream_t s = c.s;
   const uint32_t nb = c.nb;
-  // the distinct archives and, of each, the largest range end among its
-  // members (64 bits: first + count may pass 2^32; such a member fails on the
-  // device, where N is known)
-  std::vector<uint32_t> order(nb);
-  for (uint32_t i = 0; i < nb; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return c.in[x] < c.in[y]; });
-  std::vector<uint64_t> archPtr, maxEnd, slotFirst(nb);
-  uint32_t maxCount = 0;
-  for (uint32_t k = 0; k < nb; ++k) {
-    const uint32_t i = order[k];
-    if (k == 0 || c.in[i] != archPtr.back()) {
-      archPtr.push_back(c.in[i]);
-      maxEnd.push_back(0);
-    }
-    slotFirst[i] = uint64_t(archPtr.size() - 1) | (uint64_t(c.first[i]) << 32);
-    // a range that ends past 2^32 - 1 words fails whatever N is (the plan
-    // kernel refuses it; nothing is counted, decoded or expanded for it), so
-    // it sizes neither the counts nor the scratch rows
-    const uint64_t end = uint64_t(c.first[i]) + c.count[i];
-    if (end > uint64_t(UINT32_MAX)) continue;
-    maxEnd.back() = std::max(maxEnd.back(), end);
-    maxCount = std::max(maxCount, c.count[i]);
-  }
-  const uint32_t nArch = uint32_t(archPtr.size());
-  std::vector<uint64_t> archInfo(nArch);
-  uint64_t totalBlocks = 0;
-  uint32_t maxCblocks = 1;
-  for (uint32_t a = 0; a < nArch; ++a) {
-    const uint64_t chunks = (maxEnd[a] + kChunkWords - 1) / kChunkWords;  // <= 2^22
-    const uint32_t cblocks = uint32_t((chunks + kThreads - 1) / kThreads);
-    archInfo[a] = totalBlocks | (chunks << 32);
-    totalBlocks += cblocks;
-    maxCblocks = std::max(maxCblocks, cblocks);
-  }
-  DG_CHECK(totalBlocks * kThreads <= uint64_t(UINT32_MAX), "range ends too large for one call");
+  // the distinct archives, each counted once up to the largest range end
+  // among its members, and the sizes of everything below (sparse_plan.h)
+  const SparseRangePlan plan = planSparseRange(c.in.data(), c.first, c.count, nb);
+  DG_CHECK(!plan.tooLarge, "range ends too large for one call");
   const std::vector<uint32_t> counts(c.count, c.count + nb);
-  const auto t = uploadTables(res, s, {&archPtr, &archInfo, &c.out, &slotFirst}, counts);
+  const auto t = uploadTables(res, s, {&plan.archPtr, &plan.archInfo, &c.out, &plan.slotFirst}, counts);
   const SparseRangeTabs tabs{t.u64[0], t.u64[1], t.u64[3], t.u32};
-  auto chunkPre = res.alloc<uint32_t>(s, std::max<size_t>(size_t(totalBlocks) * kThreads, 1));
-  auto blockTot = res.alloc<uint32_t>(s, std::max<size_t>(size_t(totalBlocks), 1));
+  auto chunkPre = res.alloc<uint32_t>(s, plan.chunkPre);
+  auto blockTot = res.alloc<uint32_t>(s, plan.blockTot);
   auto densePtrs = res.alloc<uint64_t>(s, nb);
   auto listFirst = res.alloc<uint32_t>(s, nb);
   auto listCount = res.alloc<uint32_t>(s, nb);
   auto flags = res.alloc<uint8_t>(s, nb);
   auto denseOk = res.alloc<uint8_t>(s, nb);
   auto dummy = res.alloc<uint32_t>(s, 64);
-  // the list slices: 16 B-aligned rows of count + 1 words at most.  Sized by
-  // the call's largest count before any N is known: a member whose count
-  // cannot be valid but still ends below 2^32 makes every row that long, and
-  // a call whose rows do not fit the arena throws (GpuFloatCodec.h)
-  const uint64_t rowWords = (uint64_t(maxCount) + 1 + 15) / 16 * 16 + 16;
-  auto slices = res.alloc<uint8_t>(s, size_t(nb) * rowWords * sizeof(W));
-  if (totalBlocks != 0) {
-    forGridYSlices(nArch, [&](uint32_t y0, uint32_t ny) {
+  // the list slices: 16 B-aligned rows of count + 1 words at most, sized by
+  // the call's largest count; a call whose rows do not fit the arena throws
+  // (GpuFloatCodec.h)
+  auto slices = res.alloc<uint8_t>(s, size_t(nb) * plan.rowWords * sizeof(W));
+  if (plan.totalBlocks != 0) {
+    forGridYSlices(plan.nArch, [&](uint32_t y0, uint32_t ny) {
       prof::Scope p("sparse", s);
-      k_sparseRangeChunks<<<dim3(maxCblocks, ny), kThreads, 0, s>>>(tabs, y0, chunkPre.data(), blockTot.data());
+      k_sparseRangeChunks<<<dim3(plan.maxCblocks, ny), kThreads, 0, s>>>(tabs, y0, chunkPre.data(), blockTot.data());
       HIP_LAUNCH_CHECK();
     });
   }
@@ -963,23 +941,20 @@ void sparseRangeT(const FloatDecompressConfig& config, const SparseRangeCall& c)
                                                              flags.data(), dummy.data());
     HIP_LAUNCH_CHECK();
   }
-  // dense range decode of the slices.  The slice's start inside a block is
-  // not known here, hence one block more (workgroups past a slice's last
-  // block return at once)
+  // dense range decode of the slices
   DecodeCall dense{res, s};
   dense.nb = nb;
   dense.in = BatchDesc::pointers(densePtrs.data(), listFirst.data());
-  dense.out = BatchDesc::strided(slices.data(), rowWords * sizeof(W), 0);
+  dense.out = BatchDesc::strided(slices.data(), plan.rowWords * sizeof(W), 0);
   dense.out.sizes = listCount.data();
   dense.outSuccess_dev = denseOk.data();
   dense.form = DecodeForm::kRange;
-  dense.maxRangeBlocks = uint32_t((uint64_t(maxCount) + 1 + kBlockSize - 1) / kBlockSize) + 1;
+  dense.maxRangeBlocks = plan.maxRangeBlocks;
   floatDecompressDescs(config, dense);
   const BatchDesc outs = BatchDesc::pointers(t.u64[2], nullptr);
-  const uint32_t chunkWaves = uint32_t((uint64_t(maxCount) + kChunkWords - 1) / kChunkWords) + 1;
   forGridYSlices(nb, [&](uint32_t y0, uint32_t ny) {
     prof::Scope p("sparse", s);
-    k_sparseExpandRange<FT><<<dim3(divUp(chunkWaves, kWaves), ny), kThreads, 0, s>>>(
+    k_sparseExpandRange<FT><<<dim3(plan.expandGridX, ny), kThreads, 0, s>>>(
         tabs, outs, y0, chunkPre.data(), blockTot.data(), listFirst.data(), flags.data(), dense.out, denseOk.data(),
         c.outSuccess_dev, c.outSize_dev);
     HIP_LAUNCH_CHECK();
@@ -994,39 +969,36 @@ uint32_t getMaxSparseFloatCompressedSize(FloatType ft, uint32_t size) {
   return uint32_t(v);
 }
 
-// The sparse kernels take no InlineTable: DeviceDescs turns the tables into
-// one device upload, or for one element (the reference's SparseFloatBenchmark
-// shape) into stride descriptors without any upload.
+// The sparse kernels take no InlineTable: DeviceDescs turns the tables of a
+// batch (pointerBatch, batch_tables.h) into one device upload, or for one
+// element (the reference's SparseFloatBenchmark shape) into stride descriptors
+// without any upload.
 void floatCompressSparse(StackDeviceMemory& res, const FloatCompressConfig& config,
                          uint32_t numInBatch, const void** in, const uint32_t* inSize, void** out,
                          uint32_t* outSize_dev, hipStream_t stream) {
   if (numInBatch == 0) return;
-  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
-  const int ft = int(config.floatType);
-  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
-  const uint32_t ws = floatWordBytes(ft);
-  const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
-  const SizeColumn sz(inSize, numInBatch);
-  std::vector<uint64_t> dp(numInBatch);  // the dense archives, after header and bitmap
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DG_CHECK(op[i] % 16 == 0, "out[i] must be 16-byte aligned");
-    DG_CHECK(ip[i] % ws == 0, "input not word aligned");
-    dp[i] = op[i] + sparsePrefixBytes(sz.sizes[i]);
-  }
-  const auto t = uploadTables(res, stream, {&ip, &op, &dp}, sz.sizes, true);
-  const DeviceDescs dd(res, stream, &t, numInBatch);
-  CompressCall c{res, stream};
-  c.nb = numInBatch;
-  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], t.u32)));
-  c.maxSize = sz.maxSize;
-  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], nullptr)));
-  c.outSize_dev = outSize_dev;
-  c.inAligned16 = allAligned16(ip);
+  checkFloatConfig(config);
+  // third column: the dense archives, after header and bitmap
+  const auto b = pointerBatch(res, stream, numInBatch, in, out, inSize, true, floatWordBytes(int(config.floatType)),
+                              [](uint32_t n) { return sparsePrefixBytes(n); });
+  const DeviceDescs dd(res, stream, &b.t, numInBatch);
+  CompressCall c = compressCall(res, stream, numInBatch, b, outSize_dev);
+  c.in = dd.map(b.in);
+  c.out = dd.map(b.out);
+  c.tabs = nullptr;
   // one element: the dense archive's size writer reads N from the sparse
   // header k_sparseCount writes first (word 0 of the archive)
   c.sparseN = numInBatch == 1 ? reinterpret_cast<const uint32_t*>(out[0]) : c.in.sizes;
-  const BatchDesc denseOut = dd.map(t.tag(BatchDesc::pointers(t.u64[2], nullptr)));
+  const BatchDesc denseOut = dd.map(b.out2);
   dispatchFloatType(config.floatType, [&](auto f) { sparseCompressT<decltype(f)::value>(config, c, denseOut); });
+}
+
+// c's descriptors mapped for the sparse kernels (DeviceDescs in the caller's scope)
+static DecodeCall mapped(DecodeCall c, const DeviceDescs& dd) {
+  c.in = dd.map(c.in);
+  c.out = dd.map(c.out);
+  c.tabs = nullptr;
+  return c;
 }
 
 FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
@@ -1035,60 +1007,28 @@ FloatDecompressStatus floatDecompressSparse(StackDeviceMemory& res,
                                             const uint32_t* outCapacity, uint8_t* outSuccess_dev,
                                             uint32_t* outSize_dev, hipStream_t stream) {
   if (numInBatch == 0) return FloatDecompressStatus();
-  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
-  const int ft = int(config.floatType);
-  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
-  const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
-  const SizeColumn cap(outCapacity, numInBatch);
-  const auto t = uploadTables(res, stream, {&ip, &op}, cap.sizes, true);
-  const DeviceDescs dd(res, stream, &t, numInBatch);
-  DecodeCall c{res, stream};
-  c.nb = numInBatch;
-  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], nullptr)));
-  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], t.u32)));
-  c.maxCapacity = cap.maxSize;
-  c.outSuccess_dev = outSuccess_dev;
-  c.outSize_dev = outSize_dev;
+  checkFloatConfig(config);
+  // unit 1: this entry point has never checked its outputs' alignment
+  const auto b = pointerBatch(res, stream, numInBatch, in, out, outCapacity, false, 1);
+  const DeviceDescs dd(res, stream, &b.t, numInBatch);
+  const DecodeCall c = mapped(decodeCall(res, stream, numInBatch, b, outSuccess_dev, outSize_dev), dd);
   return dispatchFloatType(config.floatType,
                            [&](auto f) { return sparseDecompressT<decltype(f)::value>(config, c); });
 }
 
-// Sparse decode-and-accumulate.  As below, every host check
-// precedes the first allocation, upload or launch.
+// Sparse decode-and-accumulate: the dense entry point's
+// checks, with 16-byte aligned archives.
 void floatDecompressSparseAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config,
                                      uint32_t numInBatch, const void** in, void** acc,
                                      const uint32_t* accCapacity, FloatType accType, uint8_t* outSuccess_dev,
                                      uint32_t* outSize_dev, hipStream_t stream) {
-  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
-  const int ft = int(config.floatType);
-  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
-  DG_CHECK(!config.useChecksum,
-           "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded words)");
-  const bool half = config.floatType == FloatType::kFloat16 || config.floatType == FloatType::kBFloat16;
-  const bool wide = half && accType == FloatType::kFloat32;
-  DG_CHECK(accType == config.floatType || wide,
-           "accumulator type " << int(accType) << " does not go with float type " << ft
-                               << " (the archive's own type, or fp32 for fp16 / bf16 archives)");
-  if (numInBatch == 0) return;
-  const uint32_t aws = floatWordBytes(int(accType));
-  const auto ip = addressColumn(in, numInBatch), op = addressColumn(acc, numInBatch);
-  for (uint32_t i = 0; i < numInBatch; ++i) {
-    DG_CHECK(op[i] % aws == 0, "accumulator " << i << " not aligned to its word size");
-    // (the compressor requires it of its output; the bitmap is read as u64)
-    DG_CHECK(ip[i] % 16 == 0, "sparse archive " << i << " must be 16-byte aligned");
-  }
-  const SizeColumn cap(accCapacity, numInBatch);
-  const auto t = uploadTables(res, stream, {&ip, &op}, cap.sizes, true);
-  const DeviceDescs dd(res, stream, &t, numInBatch);
-  DecodeCall c{res, stream};
-  c.form = wide ? DecodeForm::kAccumulateFp32 : DecodeForm::kAccumulate;
-  c.nb = numInBatch;
-  c.in = dd.map(t.tag(BatchDesc::pointers(t.u64[0], nullptr)));
-  c.out = dd.map(t.tag(BatchDesc::pointers(t.u64[1], t.u32)));
-  c.maxCapacity = cap.maxSize;
-  c.outSuccess_dev = outSuccess_dev;
-  c.outSize_dev = outSize_dev;
-  dispatchFloatType(config.floatType, [&](auto f) { sparseDecompressT<decltype(f)::value>(config, c); });
+  accumulateEntry(res, config, numInBatch, in, acc, accCapacity, accType, outSuccess_dev, outSize_dev, stream, 16,
+                  [&](const DecodeCall& call) {
+                    const DeviceDescs dd(res, stream, call.tabs, numInBatch);
+                    const DecodeCall c = mapped(call, dd);
+                    dispatchFloatType(config.floatType,
+                                      [&](auto f) { sparseDecompressT<decltype(f)::value>(config, c); });
+                  });
 }
 
 // Every host check precedes the first allocation, upload or launch.
@@ -1096,19 +1036,15 @@ void floatDecompressSparseRange(StackDeviceMemory& res, const FloatDecompressCon
                                 uint32_t numInBatch, const void** in, const uint32_t* first,
                                 const uint32_t* count, void** out, uint8_t* outSuccess_dev,
                                 uint32_t* outSize_dev, hipStream_t stream) {
-  DG_CHECK(!config.ansConfig.useChecksum, "ANS-level checksum not allowed in float mode");
-  const int ft = int(config.floatType);
-  DG_CHECK(ft >= 1 && ft <= 4, "bad float type");
-  const int pb = config.ansConfig.probBits;
-  DG_CHECK(pb >= 9 && pb <= 11, "unhandled pdf precision " << pb << " (must be 9, 10 or 11)");
-  DG_CHECK(!config.useChecksum, "a range decode cannot verify a checksum (it covers the whole element)");
+  checkFloatConfig(config);
+  checkProbBits(config.ansConfig.probBits);
+  checkNoChecksum(config.useChecksum, PartialDecode::kRange);
   if (numInBatch == 0) return;
-  const uint32_t ws = floatWordBytes(ft);
+  const uint32_t ws = floatWordBytes(int(config.floatType));
   const auto ip = addressColumn(in, numInBatch), op = addressColumn(out, numInBatch);
   for (uint32_t i = 0; i < numInBatch; ++i) {
     DG_CHECK(op[i] % ws == 0, "float output " << i << " not aligned to its word size");
-    // (the compressor requires it of its output; the bitmap is read as u64)
-    DG_CHECK(ip[i] % 16 == 0, "sparse archive " << i << " must be 16-byte aligned");
+    checkArchiveAligned(ip[i], i, 16);
   }
   const SparseRangeCall c{res, stream, numInBatch, ip, op, first, count, outSuccess_dev, outSize_dev};
   dispatchFloatType(config.floatType, [&](auto f) { sparseRangeT<decltype(f)::value>(config, c); });

@@ -127,9 +127,78 @@ static void checkBatch(StackDeviceMemory& res, uint32_t nb, int nCols, uint32_t 
   REQUIRE(res.getSizeAvailable() == avail);  // everything released, in stack order
 }
 
+// The sparse compressor's batch through the shared pointerBatch: inputs,
+// archives and, as the third column, the dense archives at out[i] +
+// prefix(size[i]); mapped for the sparse kernels by DeviceDescs (one element:
+// stride descriptors, nothing uploaded).
+static uint64_t prefixOf(uint32_t n) { return 16 + (uint64_t(n) + 7) / 8; }
+
+static void checkSparseCompressBatch(StackDeviceMemory& res, uint32_t nb, uint32_t unit) {
+  gNb = nb;
+  std::vector<const void*> in(nb);
+  std::vector<void*> out(nb);
+  std::vector<uint32_t> raw(nb);
+  uint32_t mx = 0;
+  for (uint32_t i = 0; i < nb; ++i) {
+    raw[i] = (i * 2654435761u) % 70000;  // element 0 is empty
+    mx = std::max(mx, raw[i]);
+    in[i] = reinterpret_cast<const void*>(0x100000ull + 80ull * unit * i + (i == 3 ? unit : 0));
+    out[i] = reinterpret_cast<void*>(0x40000000ull + 0x10000ull * i);
+  }
+  const size_t avail = res.getSizeAvailable();
+  {
+    const BatchTables b = pointerBatch(res, nullptr, nb, in.data(), out.data(), raw.data(), true, unit, prefixOf);
+    const size_t bytes = size_t(nb) * 28;
+    REQUIRE(b.t.host.size() == bytes && b.t.u64.size() == 3);
+    REQUIRE(b.t.inl == (kInlineBias + bytes <= sizeof(InlineTable)));
+    REQUIRE((res.getSizeAvailable() == avail) == b.t.inl);
+    REQUIRE(b.maxSize == mx && b.inAligned16 == (nb <= 3));
+    const uint32_t tagged = b.t.inl ? uint32_t(BatchDesc::kInlPtrs) : 0u;
+    REQUIRE(b.in.inl == (b.t.inl ? (BatchDesc::kInlPtrs | BatchDesc::kInlSizes) : 0u));
+    REQUIRE(b.out.inl == tagged && b.out2.inl == tagged);
+    for (uint32_t i = 0; i < nb; ++i) {
+      REQUIRE(entry(b.t, b.t.u64[0], i) == reinterpret_cast<uint64_t>(in[i]));
+      REQUIRE(entry(b.t, b.t.u64[1], i) == reinterpret_cast<uint64_t>(out[i]));
+      REQUIRE(entry(b.t, b.t.u64[2], i) == reinterpret_cast<uint64_t>(out[i]) + prefixOf(raw[i]));
+      REQUIRE(entry(b.t, b.t.u32, i) == raw[i]);
+    }
+    const size_t before = res.getSizeAvailable();
+    {
+      const DeviceDescs dd(res, nullptr, &b.t, nb);
+      REQUIRE((res.getSizeAvailable() == before) == (!b.t.inl || nb == 1));
+      const BatchDesc mi = dd.map(b.in), mo = dd.map(b.out), md = dd.map(b.out2);
+      REQUIRE(mi.inl == 0 && mo.inl == 0 && md.inl == 0);
+      if (nb == 1) REQUIRE(mi.mode == BatchDesc::kStride && mo.mode == BatchDesc::kStride && md.mode == BatchDesc::kStride);
+      for (uint32_t i = 0; i < nb; ++i) {
+        REQUIRE(startOf(mi, i) == reinterpret_cast<uint64_t>(in[i]) && sizeOf(mi, i) == raw[i]);
+        REQUIRE(startOf(mo, i) == reinterpret_cast<uint64_t>(out[i]) && sizeOf(mo, i) == 0);
+        REQUIRE(startOf(md, i) == reinterpret_cast<uint64_t>(out[i]) + prefixOf(raw[i]) && sizeOf(md, i) == 0);
+      }
+    }
+    REQUIRE(res.getSizeAvailable() == before);
+  }
+  REQUIRE(res.getSizeAvailable() == avail);
+  // the alignment checks: the input to its unit, the archive to 16 bytes
+  auto refused = [&](const void* i0, void* o0) {
+    const void* ii[1] = {i0};
+    void* oo[1] = {o0};
+    try {
+      pointerBatch(res, nullptr, 1, ii, oo, raw.data(), true, unit, prefixOf);
+    } catch (const DietGpuError&) {
+      return true;
+    }
+    return false;
+  };
+  REQUIRE(!refused(in[0], out[0]) && refused(in[0], static_cast<uint8_t*>(out[0]) + 8));
+  REQUIRE(refused(static_cast<const uint8_t*>(in[0]) + 1, out[0]) == (unit > 1));
+  REQUIRE(res.getSizeAvailable() == avail);
+}
+
 int main() {
   std::vector<uint8_t> arena((1 << 20) + kSDMAlignment);
   StackDeviceMemory res(0, arena.data(), arena.size());
+  for (uint32_t nb : {1u, 2u, 4u, 292u, 293u, 400u})
+    for (uint32_t unit : {2u, 4u, 8u}) checkSparseCompressBatch(res, nb, unit);
   // 1, 2; 400 / 401; the inline limits of 28-, 20- and 12-byte entries
   for (uint32_t nb : {1u, 2u, 4u, 292u, 293u, 400u, 401u, 409u, 410u, 682u, 683u})
     for (int nCols : {2, 3})

@@ -184,6 +184,49 @@ def test_three_kernel_rows_back_to_back(env):
     assert C.device_error_count(reset=True) == 0
 
 
+def test_empty_sparse_element_zeroes_its_rows(env):
+    """Whoever holds a rows lease zeroes its rows of the other buffer, an
+    empty element included (commitHistRow, encode.h): a one-element sparse
+    compress of 0 words takes a one-row lease, counts nothing, and the arena
+    records the other buffer as clean on its word.  On a fresh stream with
+    one workspace: a sparse call of one row dirties a buffer, the empty call
+    follows, then a sparse and a dense call of one row each, which take the
+    buffers as zeroed; fp32, then fp64 (two segments).  Every archive must
+    equal the oracle's, byte for byte and in size."""
+    N, C = env
+    from tests.util import sparsify
+
+    ws = C.Workspace(64 << 20)
+    s = torch.cuda.Stream()
+    tdt = {3: torch.int32, 4: torch.int64}
+    ndt = {3: np.int32, 4: np.int64}
+    fdt = {3: torch.float32, 4: torch.float64}
+    C.device_error_count(reset=True)
+    with C.compress_path("three-kernel"), torch.cuda.stream(s):
+        for ft in (3, 4):
+            seed = 4100 + 10 * ft
+            steps = [("sparse", sparsify(float_words(ft, 4096, seed=seed), frac_zero=0.5, seed=seed + 1)),
+                     ("sparse", float_words(ft, 4096, seed=seed)[:0]),
+                     ("sparse", sparsify(float_words(ft, 3000, seed=seed + 2), frac_zero=0.3, seed=seed + 3)),
+                     ("dense", float_words(ft, 3000, seed=seed + 4))]
+            for k, (kind, w) in enumerate(steps):
+                if kind == "sparse":
+                    ref = O.sparse_compress(w, ft)
+                    x = torch.from_numpy(w.view(ndt[ft])).to(DEV).view(fdt[ft])
+                    out, sizes = C.sparse_compress([x], ws=ws)
+                else:
+                    ref = O.float_compress(w, ft)
+                    x = torch.from_numpy(w.view(ndt[ft])[None, :]).to(DEV)
+                    out = torch.full([1, C.max_float_compressed_size(ft, w.size)], SENTINEL, dtype=torch.uint8,
+                                     device=DEV)
+                    sizes = torch.empty([1], dtype=torch.int32, device=DEV)
+                    C.float_compress_stride(x.view(tdt[ft]), ft=ft, ws=ws, out=out, sizes=sizes)
+                s.synchronize()
+                assert int(sizes[0]) == ref.size, (ft, k, int(sizes[0]), ref.size)
+                np.testing.assert_array_equal(out[0, : ref.size].cpu().numpy(), ref, err_msg=f"ft {ft} step {k}")
+    assert C.device_error_count(reset=True) == 0
+
+
 def test_sparse_rows_interleaved_with_three_kernel(env):
     """The single-element sparse compressor counts its list's histogram into
     the same arena row buffers (k_sparseCount, no zeroing launch) and zeroes
