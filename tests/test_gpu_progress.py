@@ -127,7 +127,7 @@ def test_out_of_order_dispatch(C, ws, shape):
     look-back, through the product's skew hook (dietgpu_set_dispatch_skew).
     c2: k_pcompress carries no hook, so with the
     product library this leg runs unskewed; tools/skew_check.sh runs it
-    against the test-only variant library tools/ablibs/pskew.so
+    against the test-only variant library set tools/ablibs/pskew/
     (tools/variants.py pskew), whose k_pcompress starts skewed the same way
     (team look-back, element-log read, team barrier)."""
     C.device_error_count(reset=True)

@@ -16,7 +16,6 @@ to --out.  Reads nothing outside the repository.
     usage: python tools/accumulate_bench.py [--out profiles/accumulate.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -24,19 +23,19 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402  (tools/timing.py, next to this script)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/accumulate.json")
-    ap.add_argument("--windows", type=int, default=9)
-    ap.add_argument("--calls", type=int, default=20)
+    timing.add_args(ap, "profiles/accumulate.json")
     a = ap.parse_args()
 
     import dietgpu_fork_amd  # noqa: F401
     from dietgpu_fork_amd import codec as C
 
     dev = "cuda"
+    gpu = timing.Gpu()
     ws = C.Workspace(256 << 20)
     lines = []
     for shape, (nb, n) in (("c2_256x524288", (256, 524288)), ("1x64MiB", (1, 32 << 20))):
@@ -74,18 +73,8 @@ def main():
             acc.copy_(start)
 
             variants = {"fused": fused, "unfused": unfused, "decode": decode}
-            times = {k: [] for k in variants}
-            for w in range(a.windows + 1):  # window 0 is warm-up
-                for name, f in variants.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record()
-                    for _ in range(a.calls):
-                        f()
-                    e1.record()
-                    e1.synchronize()
-                    if w:
-                        times[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
+            times = {k: v["stream"] for k, v in timing.run_windows(
+                variants, lambda name, f: timing.measure(f, a.calls, gpu, stream=True), a.windows).items()}
             u = nb * n * 2
             ub = nb * n * acc.element_size()
             med = {k: statistics.median(v) for k, v in times.items()}
@@ -93,8 +82,7 @@ def main():
             for name in variants:
                 lines.append({
                     "shape": shape, "dtype": "bf16", "acc": {1: "bf16", 2: "fp32"}[mode], "variant": name,
-                    "us": round(med[name], 2), "us_min": round(min(times[name]), 2),
-                    "us_max": round(max(times[name]), 2), "vs_unfused": round(med[name] / med["unfused"], 4),
+                    **timing.summary(times[name], "us"), "vs_unfused": round(med[name] / med["unfused"], 4),
                     "ratio": round(comp_bytes / u, 4),
                     # bytes the algorithm moves: archive C, decoded U, accumulator U' (unfused: the
                     # temporary is written and read, and tmp.float() writes and add_ reads a second one)
@@ -105,11 +93,7 @@ def main():
                     "windows": a.windows, "calls_per_window": a.calls, "device": torch.cuda.get_device_name(0)})
             del acc, accs
         del x, arch2d, tmp, tmps, archives
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for ln in lines:
-            print(json.dumps(ln))
-            fh.write(json.dumps(ln) + "\n")
+    timing.write_lines(lines, a.out)
 
 
 if __name__ == "__main__":

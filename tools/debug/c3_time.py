@@ -1,6 +1,6 @@
 """GPU debug: c3 compress / decompress times (1024 x 4 MiB bytes, uniform
-over 16 symbols) with whatever library is in-tree (tools/ab scripts swap
-variants in), a rocprof-free per-kernel breakdown, and oracle identity of
+over 16 symbols) with whatever library is in-tree (`tools/ab.py with SET --
+...` swaps a variant in), a rocprof-free per-kernel breakdown, and oracle identity of
 two elements.  usage: python tools/debug/c3_time.py [nb]"""
 import os
 import sys

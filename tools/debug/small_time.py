@@ -1,6 +1,6 @@
 """GPU debug: back-to-back compress / decompress times of small bf16 batches
 (the single-pass compressor's one-round shapes) with whatever library is
-in-tree (tools/debug/lib_run.sh swaps variants in), and a roundtrip check.
+in-tree (`tools/ab.py with SET -- ...` swaps a variant in), and a roundtrip check.
 usage: python tools/debug/small_time.py [NBxN ...]"""
 import os
 import sys

@@ -1,6 +1,6 @@
 """GPU debug: per-wave phase timeline of the three-item k_pcompress pipeline
-from a stamp3-instrumented build (python tools/variants.py stamp3, then the
-library copied over the in-tree one).  One c2 compress; per iteration the
+from a stamp3-instrumented build (python tools/variants.py stamp3, then
+`python tools/ab.py with tools/ablibs/stamp3 -- python tools/debug/stamps3.py`).  One c2 compress; per iteration the
 median time of each phase boundary per wave, relative to the iteration start.
 usage: python tools/debug/stamps3.py"""
 import ctypes

@@ -16,24 +16,21 @@ writes them to --out.
     usage: python tools/gather_bench.py [--out profiles/gather.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402  (tools/timing.py, next to this script)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/gather.json")
+    timing.add_args(ap, "profiles/gather.json")
     ap.add_argument("--mib", type=int, default=64)
-    ap.add_argument("--windows", type=int, default=9)
-    ap.add_argument("--calls", type=int, default=20)
     a = ap.parse_args()
 
     import dietgpu_fork_amd  # noqa: F401
@@ -80,41 +77,22 @@ def main():
         assert bool(ok.all())
         assert torch.equal(out.view(torch.int16), xi.view(-1, row_words)[idx])
 
+    # kernel and call time of the same calls, the profiler on
+    gpu = timing.Gpu()
     C.profile(True)
-    kern = {k: [] for k in cases}
-    call = {k: [] for k in cases}
-    for w in range(a.windows + 1):  # window 0 is warm-up
-        for name, (family, f) in cases.items():
-            C.profile_reset()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(a.calls):
-                f()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            ms, launches = C.profile_query(family)
-            assert launches == a.calls, (name, launches)
-            if w:
-                kern[name].append(1e3 * ms / a.calls)
-                call[name].append(1e6 * dt / a.calls)
+    times = timing.run_windows(cases, lambda name, case: timing.measure(
+        case[1], a.calls, gpu, call=True, prof=C, families=(case[0],), check_launches=True), a.windows)
     C.profile(False)
 
     lines = []
-    base = statistics.median(kern["full"])
+    base = statistics.median(times["full"]["kernel"])
     for name, (family, _) in cases.items():
-        k = statistics.median(kern[name])
+        t = times[name]
         lines.append({"case": name, "family": family, "element_mib": a.mib, "dtype": "bf16",
-                      "kernel_us": round(k, 2), "kernel_us_min": round(min(kern[name]), 2),
-                      "kernel_us_max": round(max(kern[name]), 2),
-                      "call_us": round(statistics.median(call[name]), 2),
-                      "call_us_min": round(min(call[name]), 2), "call_us_max": round(max(call[name]), 2),
-                      "kernel_vs_full": round(k / base, 4), "windows": a.windows, "calls_per_window": a.calls,
-                      "device": torch.cuda.get_device_name(0)})
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for ln in lines:
-            print(json.dumps(ln))
-            fh.write(json.dumps(ln) + "\n")
+                      **timing.summary(t["kernel"], "kernel_us"), **timing.summary(t["call"], "call_us"),
+                      "kernel_vs_full": round(statistics.median(t["kernel"]) / base, 4), "windows": a.windows,
+                      "calls_per_window": a.calls, "device": torch.cuda.get_device_name(0)})
+    timing.write_lines(lines, a.out)
 
 
 if __name__ == "__main__":

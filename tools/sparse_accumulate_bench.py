@@ -19,7 +19,6 @@ variant and writes them to --out.  Reads nothing outside the repository.
     usage: python tools/sparse_accumulate_bench.py [--out profiles/sparse_accumulate.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -27,6 +26,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402  (tools/timing.py, next to this script)
 
 N15M = 15 * 1000 * 1000
 # (shape name, elements, words each, dtype, fraction of zeros, accumulator dtypes, run): zeros fall
@@ -45,15 +45,14 @@ NAME = {torch.float32: "fp32", torch.bfloat16: "bf16"}
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/sparse_accumulate.json")
-    ap.add_argument("--windows", type=int, default=9)
-    ap.add_argument("--calls", type=int, default=20)
+    timing.add_args(ap, "profiles/sparse_accumulate.json")
     a = ap.parse_args()
 
     import dietgpu_fork_amd  # noqa: F401
     from dietgpu_fork_amd import codec as C
 
     dev = "cuda"
+    gpu = timing.Gpu()
     ws = C.Workspace(2 << 30)
     lines = []
     for shape, nb, n, dtype, zeros, acc_dtypes, run in SHAPES:
@@ -98,18 +97,8 @@ def main():
             del got
 
             variants = {"fused": fused, "unfused": unfused, "decode": decode}
-            times = {k: [] for k in variants}
-            for w in range(a.windows + 1):  # window 0 is warm-up
-                for name, f in variants.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record()
-                    for _ in range(a.calls):
-                        f()
-                    e1.record()
-                    e1.synchronize()
-                    if w:
-                        times[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
+            times = {k: v["stream"] for k, v in timing.run_windows(
+                variants, lambda name, f: timing.measure(f, a.calls, gpu, stream=True), a.windows).items()}
             wb, ab = x.element_size(), acc.element_size()
             u = nb * n * wb           # the decoded elements
             ub = nb * n * ab          # the accumulators
@@ -120,8 +109,7 @@ def main():
                 lines.append({
                     "shape": shape, "dtype": NAME[dtype], "zeros": zeros, "zero_run": run, "acc": NAME[acc_dtype],
                     "variant": name,
-                    "us": round(med[name], 2), "us_min": round(min(times[name]), 2),
-                    "us_max": round(max(times[name]), 2), "vs_unfused": round(med[name] / med["unfused"], 4),
+                    **timing.summary(times[name], "us"), "vs_unfused": round(med[name] / med["unfused"], 4),
                     "ratio": round(comp_bytes / u, 4), "nonzero": round(nnz / (nb * n), 4),
                     # bytes the algorithm moves: archive C (its bitmap is read twice: counted, then
                     # expanded), list L written and read; fused: the accumulator words under nonzero
@@ -135,11 +123,7 @@ def main():
             del acc, accs, start
         del x, arch2d, tmp, tmps, archives
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for ln in lines:
-            print(json.dumps(ln))
-            fh.write(json.dumps(ln) + "\n")
+    timing.write_lines(lines, a.out)
 
 
 if __name__ == "__main__":

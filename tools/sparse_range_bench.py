@@ -16,24 +16,21 @@ them to --out.
     usage: python tools/sparse_range_bench.py [--out profiles/sparse_range_decode.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402  (tools/timing.py, next to this script)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/sparse_range_decode.json")
+    timing.add_args(ap, "profiles/sparse_range_decode.json")
     ap.add_argument("--rows", type=int, default=15 * 1024)
-    ap.add_argument("--windows", type=int, default=9)
-    ap.add_argument("--calls", type=int, default=20)
     a = ap.parse_args()
 
     import dietgpu_fork_amd  # noqa: F401
@@ -78,47 +75,28 @@ def main():
     for got, want in checks:
         assert torch.equal(got.view(torch.int32).reshape(-1), want.reshape(-1))
 
-    stream = {k: [] for k in cases}
-    kern = {k: [] for k in cases}
-    call = {k: [] for k in cases}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for w in range(a.windows + 1):  # window 0 is warm-up
-        for name, (families, f) in cases.items():
-            C.profile(False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            e0.record()
-            for _ in range(a.calls):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            C.profile(True)
-            C.profile_reset()
-            for _ in range(a.calls):
-                f()
-            torch.cuda.synchronize()
-            ms = sum(C.profile_query(fam)[0] for fam in families)
-            if w:
-                stream[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
-                kern[name].append(1e3 * ms / a.calls)
-                call[name].append(1e6 * dt / a.calls)
+    gpu = timing.Gpu()
+
+    def measure_case(name, case):
+        families, f = case
+        C.profile(False)  # stream and call time of the same calls, the profiler off
+        t = timing.measure(f, a.calls, gpu, stream=True, call=True)
+        C.profile(True)  # kernel time of a second run of the calls
+        t.update(timing.measure(f, a.calls, gpu, prof=C, families=families))
+        return t
+
+    times = timing.run_windows(cases, measure_case, a.windows)
     C.profile(False)
 
     lines = []
-    for name in cases:
-        base = "full_z" + name.rsplit("_z", 1)[1]
-        med = {k: statistics.median(v[name]) for k, v in (("stream", stream), ("kernel", kern), ("call", call))}
-        lines.append({"case": name, "element_words": n, "dtype": "fp32", "stream_us": round(med["stream"], 2),
-                      "stream_us_min": round(min(stream[name]), 2), "stream_us_max": round(max(stream[name]), 2),
-                      "kernel_us": round(med["kernel"], 2), "call_us": round(med["call"], 2),
-                      "stream_vs_full": round(med["stream"] / statistics.median(stream[base]), 4),
+    for name, t in times.items():
+        base = times["full_z" + name.rsplit("_z", 1)[1]]
+        lines.append({"case": name, "element_words": n, "dtype": "fp32", **timing.summary(t["stream"], "stream_us"),
+                      "kernel_us": round(statistics.median(t["kernel"]), 2),
+                      "call_us": round(statistics.median(t["call"]), 2),
+                      "stream_vs_full": round(statistics.median(t["stream"]) / statistics.median(base["stream"]), 4),
                       "windows": a.windows, "calls_per_window": a.calls, "device": torch.cuda.get_device_name(0)})
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for ln in lines:
-            print(json.dumps(ln))
-            fh.write(json.dumps(ln) + "\n")
+    timing.write_lines(lines, a.out)
 
 
 if __name__ == "__main__":
