@@ -32,15 +32,37 @@ def gather_sizes(local_sizes, nb, group=None):
     return out[:nb].to(torch.int64)
 
 
-def archive_offsets(sizes, align=16):
+_ALIGN = 16  # archives are packed at 16 B aligned offsets
+
+
+def _pad(sizes, align=_ALIGN):
+    """roundUp(sizes, align): a number or a tensor of them."""
+    return (sizes + (align - 1)) // align * align
+
+
+def archive_offsets(sizes, align=_ALIGN):
     """Exclusive prefix of roundUp(size, align): where each element's archive
     lands when the batch is packed back to back (archives are 16 B aligned,
     SURVEY 8(b))."""
-    r = (sizes + (align - 1)) // align * align
+    r = _pad(sizes, align)
     return torch.cumsum(r, 0) - r
 
 
-class GpuFloatCodec:
+class _GpuCodec:
+    """What the two codecs of the compressed collectives share: the check of a
+    decode's per-archive status and the read of a dense float header."""
+
+    @staticmethod
+    def _raise_on_failure(ok):
+        if not bool((ok != 0).all()):
+            raise RuntimeError("compressed collective: an archive failed to decode")
+
+    def info(self, archive):
+        """(numel, dtype) of the element `archive` encodes."""
+        return _archive_info(archive)
+
+
+class GpuFloatCodec(_GpuCodec):
     """The float codec on the local GPU (ops.compress_data /
     ops.decompress_data: k_pcompress or k_hist -> k_encode, then k_decode) for the compressed collectives."""
 
@@ -58,8 +80,7 @@ class GpuFloatCodec:
 
         status = torch.empty(len(archives), dtype=torch.uint8, device=outs[0].device)
         ops.decompress_data(True, archives, outs, self.checksum, out_status=status)
-        if not bool((status != 0).all()):
-            raise RuntimeError("compressed collective: an archive failed to decode")
+        self._raise_on_failure(status)
 
     def accumulate(self, archives, accs):
         """accs[i] += the element archives[i] encodes, in place (k_decode's
@@ -69,15 +90,10 @@ class GpuFloatCodec:
 
         status = torch.empty(len(archives), dtype=torch.uint8, device=accs[0].device)
         ops.decompress_data_accumulate(archives, accs, out_status=status)
-        if not bool((status != 0).all()):
-            raise RuntimeError("compressed collective: an archive failed to decode")
-
-    def info(self, archive):
-        """(numel, dtype) of the element `archive` encodes."""
-        return _archive_info(archive)
+        self._raise_on_failure(status)
 
 
-class GpuSparseFloatCodec:
+class GpuSparseFloatCodec(_GpuCodec):
     """The sparse float codec on the local GPU (codec.sparse_compress /
     sparse_decompress / sparse_decompress_accumulate: bitmap + the dense codec
     on the nonzero words) for the compressed collectives, for tensors that are
@@ -97,27 +113,24 @@ class GpuSparseFloatCodec:
         self.workspace_bytes = workspace_bytes
         self._ws = {}
 
-    def _workspace(self, device):
+    def _run(self, f, device, *args, **kw):
+        """f, a function of codec.py, with this codec's prob_bits and its
+        workspace on `device` (made at the first call there)."""
         from . import codec
 
         if device not in self._ws:
             self._ws[device] = codec.Workspace(self.workspace_bytes, device)
-        return self._ws[device]
+        return f(*args, prob_bits=self.prob_bits, ws=self._ws[device], **kw)
 
     def compress(self, tensors):
         from . import codec
 
-        return codec.sparse_compress(tensors, prob_bits=self.prob_bits, ws=self._workspace(tensors[0].device))
-
-    @staticmethod
-    def _raise_on_failure(ok):
-        if not bool((ok != 0).all()):
-            raise RuntimeError("compressed collective: an archive failed to decode")
+        return self._run(codec.sparse_compress, tensors[0].device, tensors)
 
     def decompress(self, archives, outs):
         from . import codec
 
-        ok, _ = codec.sparse_decompress(archives, outs, prob_bits=self.prob_bits, ws=self._workspace(outs[0].device))
+        ok, _ = self._run(codec.sparse_decompress, outs[0].device, archives, outs)
         self._raise_on_failure(ok)
 
     def accumulate(self, archives, accs):
@@ -127,8 +140,7 @@ class GpuSparseFloatCodec:
 
         # (a float32 accumulator serves three archive types: the header tells)
         ft = self.info(archives[0])[1] if accs[0].dtype == torch.float32 else accs[0].dtype
-        ok, _ = codec.sparse_decompress_accumulate(archives, accs, ft=codec.FLOAT_TYPE[ft], prob_bits=self.prob_bits,
-                                                   ws=self._workspace(accs[0].device))
+        ok, _ = self._run(codec.sparse_decompress_accumulate, accs[0].device, archives, accs, ft=codec.FLOAT_TYPE[ft])
         self._raise_on_failure(ok)
 
     def info(self, archive):
@@ -136,8 +148,8 @@ class GpuSparseFloatCodec:
         from the sparse header, dtype from the dense header behind the bitmap
         (two small reads on the host)."""
         n = int(archive[:4].cpu().numpy().view("<u4")[0])
-        at = 16 + (((n + 7) // 8 + 15) // 16) * 16
-        return n, _archive_info(archive[at:at + 32])[1]
+        at = 16 + _pad((n + 7) // 8)  # the sparse header, then the bitmap
+        return n, super().info(archive[at:at + 32])[1]
 
 
 def _check_sizes(sizes, what):
@@ -152,26 +164,43 @@ def _check_sizes(sizes, what):
         raise RuntimeError(f"{what}: compression of element(s) {bad[:8]} was abandoned (archive size 0)")
 
 
-def _pack(comp, sizes, offs, length, dev):
+def _pack(comp, sizes, length, dev):
     """Pack the archive rows comp[i, :sizes[i]] back to back at the 16 B
-    aligned offsets `offs` (= archive_offsets(sizes)) into a buffer of
-    `length` bytes: one masked gather over the [nb, cols] archive matrix (the
-    16 B tails of each row ride along as don't-care padding), no per-element
-    launches."""
-    nb, cols = comp.shape
-    if cols % 16:
-        comp = torch.nn.functional.pad(comp, (0, 16 - cols % 16))
+    aligned offsets archive_offsets(sizes) into a buffer of `length` bytes:
+    one masked gather over the [nb, cols] archive matrix (the 16 B tails of
+    each row ride along as don't-care padding), no per-element launches."""
+    cols = comp.shape[1]
+    if cols % _ALIGN:
+        comp = torch.nn.functional.pad(comp, (0, _ALIGN - cols % _ALIGN))
         cols = comp.shape[1]
-    padded = ((sizes.to(torch.int64) + 15) // 16 * 16).to(comp.device)
-    if nb:
-        expect = torch.cumsum(padded.cpu(), 0) - padded.cpu()
-        assert torch.equal(expect, torch.as_tensor(offs, dtype=torch.int64).cpu()), \
-            "_pack: offsets must be the 16 B aligned exclusive prefix of the sizes"
-    buf = torch.zeros(max(int(length), 16), dtype=torch.uint8, device=dev)
+    padded = _pad(torch.as_tensor(sizes, dtype=torch.int64)).to(comp.device)
+    buf = torch.zeros(max(int(length), _ALIGN), dtype=torch.uint8, device=dev)
     mask = torch.arange(cols, device=comp.device)[None, :] < padded[:, None]
     flat = comp[mask]
     buf[: flat.numel()] = flat.to(dev)
     return buf
+
+
+def _unpack(buf, sizes, base=0):
+    """_pack's counterpart: the archive views buf[o:o + sizes[i]] of a buffer
+    packed from `sizes` (a list) that starts at byte `base` of buf, o = base +
+    the padded exclusive prefix of the sizes."""
+    views = []
+    for n in sizes:
+        views.append(buf[base:base + n])
+        base += _pad(n)
+    return views
+
+
+def _gather_table(numels, sizes, group, dev):
+    """The one metadata exchange: this rank's k rows of (numel, archive size)
+    are all-gathered (2 * k int64 per rank); returns every rank's rows as the
+    host table t[rank][row] = [numel, size] (plain lists: [world, k, 2])."""
+    meta = torch.tensor(list(zip(numels, sizes)), dtype=torch.int64, device=dev)
+    world = dist.get_world_size(group)
+    table = torch.empty([world * len(numels), 2], dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(table, meta, group=group)
+    return table.view(world, len(numels), 2).tolist()
 
 
 def all_gather_compressed(tensors, group=None, codec=None):
@@ -190,35 +219,70 @@ def all_gather_compressed(tensors, group=None, codec=None):
     """
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size(group)
-    k = len(tensors)
-    if k == 0:
+    if len(tensors) == 0:
         return []
     dtype, dev = tensors[0].dtype, tensors[0].device
     flat = [t.contiguous().view(-1) for t in tensors]
     comp, sizes = codec.compress(flat)
-    meta = torch.stack([torch.tensor([t.numel() for t in flat], dtype=torch.int64),
-                        sizes.to("cpu", torch.int64)]).to(dev)
-    allmeta = torch.empty(world * 2 * k, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allmeta, meta.view(-1), group=group)
-    allmeta = allmeta.view(world, 2, k).cpu()
-    asizes = allmeta[:, 1, :]
-    _check_sizes(asizes.reshape(-1), "all_gather_compressed")
-    offs = archive_offsets(asizes.reshape(-1)).view(world, k)
-    offs = offs - offs[:, :1]  # per-rank packing, from 0
-    packed = offs[:, -1] + (asizes[:, -1] + 15) // 16 * 16
-    span = max(int(packed.max()), 16)
-    rank = dist.get_rank(group)
-    send = _pack(comp, asizes[rank], offs[rank], span, dev)
+    table = _gather_table([t.numel() for t in flat], sizes.tolist(), group, dev)  # [rank][tensor]
+    asizes = [[size for _, size in rows] for rows in table]
+    _check_sizes([size for rows in asizes for size in rows], "all_gather_compressed")
+    span = max(max(sum(_pad(size) for size in rows) for rows in asizes), _ALIGN)  # per-rank packing, from 0
+    send = _pack(comp, asizes[dist.get_rank(group)], span, dev)
     recv = torch.empty(world * span, dtype=torch.uint8, device=dev)
     dist.all_gather_into_tensor(recv, send, group=group)
-    archives, outs = [], []
-    for r in range(world):
-        for i in range(k):
-            o = r * span + int(offs[r, i])
-            archives.append(recv[o:o + int(asizes[r, i])])
-            outs.append(torch.empty(int(allmeta[r, 0, i]), dtype=dtype, device=dev))
+    archives = [a for r in range(world) for a in _unpack(recv, asizes[r], r * span)]
+    outs = [torch.empty(numel, dtype=dtype, device=dev) for rows in table for numel, _ in rows]
     codec.decompress(archives, outs)
     return outs
+
+
+def _all_to_all_archives(flat, travels, what, group, codec, check_table=None):
+    """The transport of all_to_all_compressed and reduce_scatter_compressed
+    (`what` names the caller in messages): flat[j] is bound for rank j.
+
+    travels(source, destination, numel) -> bool is the rule of who sends to
+    whom; every rank evaluates it alike.  What travels from this rank is
+    compressed in one batch (no codec call when nothing does); one all-gather
+    exchanges the whole [source][destination] table of (numel, archive size),
+    so every rank can run check_table(table) and then the size check over
+    exactly the travelling entries, and a bad table raises on every rank
+    before the payload moves; one all_to_all_single with the padded sizes as
+    splits moves the packed archives (skipped on every rank alike when nothing
+    travels anywhere).  Returns (archives, numels) of what this rank received,
+    ascending source rank."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    dev = flat[0].device
+    numels = [t.numel() for t in flat]
+    going = [j for j in range(world) if travels(rank, j, numels[j])]
+    sizes = [0] * world
+    comp = torch.zeros([0, _ALIGN], dtype=torch.uint8, device=dev)
+    if going:
+        comp, csz = codec.compress([flat[j] for j in going])
+        for j, size in zip(going, csz.tolist()):
+            sizes[j] = size
+    table = _gather_table(numels, sizes, group, dev)  # row j of a rank goes to rank j
+    if check_table is not None:
+        check_table(table)
+    # what travels, as (source, destination, archive size), sources ascending
+    moving = [(src, dst, size) for src, row in enumerate(table) for dst, (numel, size) in enumerate(row)
+              if travels(src, dst, numel)]
+    _check_sizes([size for _, _, size in moving], what)
+    lens = [0] * world  # what this rank sends to each destination
+    rlens = [0] * world  # ... and receives from each source
+    for src, dst, size in moving:
+        if src == rank:
+            lens[dst] = _pad(size)
+        if dst == rank:
+            rlens[src] = _pad(size)
+    recv = torch.empty(max(sum(rlens), _ALIGN), dtype=torch.uint8, device=dev)
+    if moving:  # (the same on every rank)
+        send = _pack(comp, [sizes[j] for j in going], sum(lens), dev)
+        dist.all_to_all_single(recv[: sum(rlens)], send[: sum(lens)],
+                               output_split_sizes=rlens, input_split_sizes=lens, group=group)
+    arrivals = [(src, size) for src, dst, size in moving if dst == rank]
+    archives = _unpack(recv, [size for _, size in arrivals])
+    return archives, [table[src][rank][0] for src, _ in arrivals]
 
 
 def all_to_all_compressed(tensors, group=None, codec=None):
@@ -229,32 +293,13 @@ def all_to_all_compressed(tensors, group=None, codec=None):
     all_to_all_single, the packed archives with one all_to_all_single whose
     split sizes are the packed lengths."""
     codec = codec or GpuFloatCodec()
-    world = dist.get_world_size(group)
-    if len(tensors) != world:
+    if len(tensors) != dist.get_world_size(group):
         raise ValueError("all_to_all_compressed: one tensor per destination rank")
     dtype, dev = tensors[0].dtype, tensors[0].device
-    flat = [t.contiguous().view(-1) for t in tensors]
-    comp, sizes = codec.compress(flat)
-    sizes = sizes.to("cpu", torch.int64)
-    lens = (sizes + 15) // 16 * 16
-    send = _pack(comp, sizes, torch.cumsum(lens, 0) - lens, int(lens.sum()), dev)
-    meta = torch.stack([torch.tensor([t.numel() for t in flat], dtype=torch.int64), sizes],
-                       dim=1).to(dev)  # row j goes to rank j
-    # every rank gathers the whole (source, destination) table, so a poisoned
-    # archive anywhere raises on every rank before the payload exchange
-    allmeta = torch.empty([world * world, 2], dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allmeta, meta, group=group)
-    allmeta = allmeta.view(world, world, 2).cpu()
-    _check_sizes(allmeta[:, :, 1].reshape(-1), "all_to_all_compressed")
-    rmeta = allmeta[:, dist.get_rank(group), :]
-    rlens = (rmeta[:, 1] + 15) // 16 * 16
-    recv = torch.empty(max(int(rlens.sum()), 16), dtype=torch.uint8, device=dev)
-    dist.all_to_all_single(recv[: int(rlens.sum())], send[: int(lens.sum())],
-                           output_split_sizes=rlens.tolist(), input_split_sizes=lens.tolist(),
-                           group=group)
-    roffs = torch.cumsum(rlens, 0) - rlens
-    archives = [recv[int(roffs[r]):int(roffs[r]) + int(rmeta[r, 1])] for r in range(world)]
-    outs = [torch.empty(int(rmeta[r, 0]), dtype=dtype, device=dev) for r in range(world)]
+    # everything travels, this rank's tensor to itself and empty ones included
+    archives, numels = _all_to_all_archives([t.contiguous().view(-1) for t in tensors], lambda src, dst, numel: True,
+                                            "all_to_all_compressed", group, codec)
+    outs = [torch.empty(n, dtype=dtype, device=dev) for n in numels]
     codec.decompress(archives, outs)
     return outs
 
@@ -335,42 +380,21 @@ def reduce_scatter_compressed(tensors, group=None, codec=None, acc_dtype=None):
     the payload moves; one all_to_all_single moves the packed archives."""
     codec = codec or GpuFloatCodec()
     world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
     if len(tensors) != world:
         raise ValueError("reduce_scatter_compressed: one tensor per destination rank")
-    dtype, dev = tensors[0].dtype, tensors[0].device
-    _acc_dtype(dtype, acc_dtype)
+    _acc_dtype(tensors[0].dtype, acc_dtype)
     flat = [t.contiguous().view(-1) for t in tensors]
-    numels = torch.tensor([t.numel() for t in flat], dtype=torch.int64)
-    # the tensors that travel: every destination but this rank, empties aside
-    going = [j for j in range(world) if j != rank and flat[j].numel() > 0]
-    sizes = torch.zeros(world, dtype=torch.int64)
-    comp = torch.zeros([0, 16], dtype=torch.uint8, device=dev)
-    if going:
-        comp, csz = codec.compress([flat[j] for j in going])
-        sizes[going] = csz.to("cpu", torch.int64)
-    meta = torch.stack([numels, sizes], dim=1).to(dev)  # row j goes to rank j
-    allmeta = torch.empty([world * world, 2], dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allmeta, meta, group=group)
-    allmeta = allmeta.view(world, world, 2).cpu()  # [source, destination]
-    for j in range(world):
-        col = allmeta[:, j, 0]
-        if not bool((col == col[0]).all()):
-            raise RuntimeError(f"reduce_scatter_compressed: the ranks' tensors[{j}] differ in numel: {col.tolist()}")
-    travels = (~torch.eye(world, dtype=torch.bool)) & (allmeta[:, :, 0] > 0)
-    _check_sizes(allmeta[:, :, 1][travels], "reduce_scatter_compressed")
-    asizes = torch.where(travels, allmeta[:, :, 1], torch.zeros_like(allmeta[:, :, 1]))
-    lens = (asizes[rank] + 15) // 16 * 16  # what this rank sends to each destination
-    rlens = (asizes[:, rank] + 15) // 16 * 16  # ... and receives from each source
-    recv = torch.empty(max(int(rlens.sum()), 16), dtype=torch.uint8, device=dev)
-    if int(asizes.sum()) > 0:  # (the same on every rank)
-        glens = lens[going]
-        send = _pack(comp, asizes[rank][going], torch.cumsum(glens, 0) - glens, int(glens.sum()), dev)
-        dist.all_to_all_single(recv[: int(rlens.sum())], send[: int(lens.sum())],
-                               output_split_sizes=rlens.tolist(), input_split_sizes=lens.tolist(), group=group)
-    roffs = torch.cumsum(rlens, 0) - rlens
-    archives = [recv[int(roffs[r]):int(roffs[r]) + int(asizes[r, rank])] for r in range(world) if travels[r, rank]]
-    return reduce_archives(flat[rank], archives, codec, acc_dtype)
+
+    def same_numels(table):
+        for j in range(world):
+            col = [row[j][0] for row in table]
+            if col != col[:1] * world:
+                raise RuntimeError(f"reduce_scatter_compressed: the ranks' tensors[{j}] differ in numel: {col}")
+
+    # the tensors that travel: every destination but the rank itself, empties aside
+    archives, _ = _all_to_all_archives(flat, lambda src, dst, numel: src != dst and numel > 0,
+                                       "reduce_scatter_compressed", group, codec, same_numels)
+    return reduce_archives(flat[dist.get_rank(group)], archives, codec, acc_dtype)
 
 
 def all_reduce_compressed(tensor, group=None, codec=None, acc_dtype=None):

@@ -4,51 +4,36 @@ in for the per-rank GPU codec here), all-gather the sizes and derive the
 same packing offsets; the sharded archives equal the single-process ones
 (a per-element archive is a pure function of its bytes)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from tests.dist_cases import OracleCodec, run_ranks
 from tests.util import float_words
 
 NB = 11  # odd: the last shard is short
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _inputs():
     return [float_words(2, 300 + 517 * i, seed=i) for i in range(NB)]
 
 
-def _worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
-        from oracle import oracle as O
+def _worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
+    from oracle import oracle as O
 
-        xs = _inputs()
-        a, b = D.shard_range(NB, rank, world)
-        archives = [O.float_compress(xs[i], 2, 10) for i in range(a, b)]
-        local = torch.tensor([x.size for x in archives], dtype=torch.int32)
-        sizes = D.gather_sizes(local, NB)
-        offs = D.archive_offsets(sizes)
-        np.save(os.path.join(outdir, f"sizes{rank}.npy"), sizes.numpy())
-        np.save(os.path.join(outdir, f"offs{rank}.npy"), offs.numpy())
-        for i, arch in zip(range(a, b), archives):
-            np.save(os.path.join(outdir, f"arch{i}.npy"), arch)
-    finally:
-        dist.destroy_process_group()
+    xs = _inputs()
+    a, b = D.shard_range(NB, rank, world)
+    archives = [O.float_compress(xs[i], 2, 10) for i in range(a, b)]
+    local = torch.tensor([x.size for x in archives], dtype=torch.int32)
+    sizes = D.gather_sizes(local, NB)
+    offs = D.archive_offsets(sizes)
+    np.save(os.path.join(outdir, f"sizes{rank}.npy"), sizes.numpy())
+    np.save(os.path.join(outdir, f"offs{rank}.npy"), offs.numpy())
+    for i, arch in zip(range(a, b), archives):
+        np.save(os.path.join(outdir, f"arch{i}.npy"), arch)
 
 
 def test_shard_range_covers_batch():
@@ -65,7 +50,7 @@ def test_two_rank_gloo_size_gather(tmp_path):
     from dietgpu_fork_amd import dist as D
     from oracle import oracle as O
 
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    run_ranks(_worker, 2, tmp_path)
     xs = _inputs()
     ref = [O.float_compress(x, 2, 10) for x in xs]
     ref_sizes = np.array([r.size for r in ref], dtype=np.int64)
@@ -76,29 +61,6 @@ def test_two_rank_gloo_size_gather(tmp_path):
         assert (offs % 16 == 0).all()
     for i in range(NB):
         assert np.array_equal(np.load(tmp_path / f"arch{i}.npy"), ref[i])
-
-
-class _OracleCodec:
-    """CPU stand-in for dist.GpuFloatCodec in gloo tests (bf16): the oracle's
-    float codec, same archives as the GPU path."""
-
-    def compress(self, tensors):
-        from oracle import oracle as O
-
-        arch = [O.float_compress(t.view(torch.int16).numpy().view(np.uint16), 2, 10)
-                for t in tensors]
-        comp = torch.zeros(len(arch), max(a.size for a in arch), dtype=torch.uint8)
-        for i, a in enumerate(arch):
-            comp[i, : a.size] = torch.from_numpy(a)
-        return comp, torch.tensor([a.size for a in arch], dtype=torch.int32)
-
-    def decompress(self, archives, outs):
-        from oracle import oracle as O
-
-        for a, o in zip(archives, outs):
-            st, words = O.float_decompress(a.numpy(), 2, 10)
-            assert st == 0 and words.size == o.numel()
-            o.view(torch.int16).copy_(torch.from_numpy(words.view(np.int16)))
 
 
 def _bf16(n, seed):
@@ -114,29 +76,22 @@ def _a2a_input(src, dst):
     return _bf16(700 + 1111 * src + 37 * dst, 100 + 10 * src + dst)
 
 
-def _cc_worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
+def _cc_worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
 
-        got = D.all_gather_compressed(_gather_inputs(rank), codec=_OracleCodec())
-        for j, t in enumerate(got):
-            np.save(os.path.join(outdir, f"ag{rank}_{j}.npy"), t.view(torch.int16).numpy())
-        got = D.all_to_all_compressed([_a2a_input(rank, d) for d in range(world)],
-                                      codec=_OracleCodec())
-        for s, t in enumerate(got):
-            np.save(os.path.join(outdir, f"a2a{rank}_{s}.npy"), t.view(torch.int16).numpy())
-    finally:
-        dist.destroy_process_group()
+    got = D.all_gather_compressed(_gather_inputs(rank), codec=OracleCodec())
+    for j, t in enumerate(got):
+        np.save(os.path.join(outdir, f"ag{rank}_{j}.npy"), t.view(torch.int16).numpy())
+    got = D.all_to_all_compressed([_a2a_input(rank, d) for d in range(world)], codec=OracleCodec())
+    for s, t in enumerate(got):
+        np.save(os.path.join(outdir, f"a2a{rank}_{s}.npy"), t.view(torch.int16).numpy())
 
 
 def test_two_rank_gloo_compressed_collectives(tmp_path):
     """all_gather_compressed / all_to_all_compressed deliver every tensor bit
     for bit (world 2, gloo, the oracle codec standing in for the GPU one)."""
     world = 2
-    mp.spawn(_cc_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_cc_worker, world, tmp_path)
     want = [t for r in range(world) for t in _gather_inputs(r)]
     for rank in range(world):
         for j, t in enumerate(want):
@@ -147,39 +102,21 @@ def test_two_rank_gloo_compressed_collectives(tmp_path):
             assert np.array_equal(got, _a2a_input(s, rank).view(torch.int16).numpy()), (rank, s)
 
 
-class _PoisonCodec(_OracleCodec):
-    """The oracle codec with one abandoned element on rank 1 (archive size 0,
-    as a poisoned compression reports it)."""
+def _poison_worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
 
-    def __init__(self, rank):
-        self.rank = rank
-
-    def compress(self, tensors):
-        comp, sizes = super().compress(tensors)
-        if self.rank == 1:
-            sizes[1] = 0
-        return comp, sizes
-
-
-def _poison_worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
-
-        msgs = []
-        for fn, arg in ((D.all_gather_compressed, _gather_inputs(rank)),
-                        (D.all_to_all_compressed, [_a2a_input(rank, d) for d in range(world)])):
-            try:
-                fn(arg, codec=_PoisonCodec(rank))
-                msgs.append("no error")
-            except RuntimeError as e:
-                msgs.append(str(e))
-        with open(os.path.join(outdir, f"poison{rank}.txt"), "w") as f:
-            f.write("\n".join(msgs))
-    finally:
-        dist.destroy_process_group()
+    msgs = []
+    # one abandoned element on rank 1: archive size 0, as a poisoned compression reports it
+    codec = OracleCodec(poison=1 if rank == 1 else None)
+    for fn, arg in ((D.all_gather_compressed, _gather_inputs(rank)),
+                    (D.all_to_all_compressed, [_a2a_input(rank, d) for d in range(world)])):
+        try:
+            fn(arg, codec=codec)
+            msgs.append("no error")
+        except RuntimeError as e:
+            msgs.append(str(e))
+    with open(os.path.join(outdir, f"poison{rank}.txt"), "w") as f:
+        f.write("\n".join(msgs))
 
 
 def test_two_rank_gloo_abandoned_archive_raises_everywhere(tmp_path):
@@ -187,7 +124,7 @@ def test_two_rank_gloo_abandoned_archive_raises_everywhere(tmp_path):
     on EVERY rank before the payload exchange (no rank left waiting, no
     zero-length slot aliasing the next archive)."""
     world = 2
-    mp.spawn(_poison_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_poison_worker, world, tmp_path)
     for rank in range(world):
         msgs = (tmp_path / f"poison{rank}.txt").read_text().split("\n")
         assert len(msgs) == 2
@@ -198,31 +135,25 @@ def test_two_rank_gloo_abandoned_archive_raises_everywhere(tmp_path):
 C5_TOTAL, C5_WORDS = 64, 257  # the c5 plan at test size (bench.py: 8192 x 524288)
 
 
-def _c5_worker(rank, world, port, outdir):
+def _c5_worker(rank, world, outdir):
     """bench.py's N>1 leg minus the GPU: this rank's contiguous share of the
     fixed batch (bench._bf16_rows), compressed locally (oracle standing in for
     the GPU codec), per-element sizes all-gathered, max-over-ranks timing."""
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import bench
-        from dietgpu_fork_amd import dist as D
-        from oracle import oracle as O
+    import bench
+    from dietgpu_fork_amd import dist as D
+    from oracle import oracle as O
 
-        first, last = D.shard_range(C5_TOTAL, rank, world)
-        assert last - first == C5_TOTAL // world
-        x = bench._bf16_rows(first, last, C5_WORDS, "cpu", chunk=16)
-        sizes = torch.tensor([O.float_compress(r.view(torch.int16).numpy().view(np.uint16), 2).size
-                              for r in x], dtype=torch.int32)
-        allsizes = D.gather_sizes(sizes, C5_TOTAL)
-        t = torch.tensor([float(rank + 1)], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        np.save(os.path.join(outdir, f"c5sizes{rank}.npy"), allsizes.numpy())
-        np.save(os.path.join(outdir, f"c5rows{rank}.npy"), x.view(torch.int16).numpy())
-        np.save(os.path.join(outdir, f"c5t{rank}.npy"), t.numpy())
-    finally:
-        dist.destroy_process_group()
+    first, last = D.shard_range(C5_TOTAL, rank, world)
+    assert last - first == C5_TOTAL // world
+    x = bench._bf16_rows(first, last, C5_WORDS, "cpu", chunk=16)
+    sizes = torch.tensor([O.float_compress(r.view(torch.int16).numpy().view(np.uint16), 2).size
+                          for r in x], dtype=torch.int32)
+    allsizes = D.gather_sizes(sizes, C5_TOTAL)
+    t = torch.tensor([float(rank + 1)], dtype=torch.float64)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    np.save(os.path.join(outdir, f"c5sizes{rank}.npy"), allsizes.numpy())
+    np.save(os.path.join(outdir, f"c5rows{rank}.npy"), x.view(torch.int16).numpy())
+    np.save(os.path.join(outdir, f"c5t{rank}.npy"), t.numpy())
 
 
 @pytest.mark.parametrize("world", [2, 4])
@@ -233,7 +164,7 @@ def test_c5_sharded_bench_plan(tmp_path, world):
     import bench
     from oracle import oracle as O
 
-    mp.spawn(_c5_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_c5_worker, world, tmp_path)
     full = bench._bf16_rows(0, C5_TOTAL, C5_WORDS, "cpu", chunk=16)
     ref = np.array([O.float_compress(r.view(torch.int16).numpy().view(np.uint16), 2).size for r in full])
     rows = np.concatenate([np.load(tmp_path / f"c5rows{r}.npy") for r in range(world)])
@@ -251,7 +182,7 @@ def test_pack_matches_per_element_copies():
     sizes = torch.tensor([0, 1, 15, 16, 17, 99, 100])
     offs = D.archive_offsets(sizes)
     length = int(offs[-1] + (sizes[-1] + 15) // 16 * 16) + 5
-    buf = D._pack(comp, sizes, offs, length, "cpu")
+    buf = D._pack(comp, sizes, length, "cpu")
     assert buf.numel() == length
     for i in range(7):
         o, s = int(offs[i]), int(sizes[i])

@@ -6,67 +6,15 @@ The codec is a stand-in backed by the CPU oracle; its accumulate is the CPU
 model of tests/accumulate_cases.py, so these tests cover the collectives'
 bookkeeping and order, and tests/test_gpu_accumulate.py the kernel."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import accumulate_cases as A
+from tests.dist_cases import FT_OF, OracleCodec, numels, run_ranks, save_bits, sizes_for
 
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-class OracleCodec:
-    """CPU stand-in for dist.GpuFloatCodec: the oracle's archives, the model's
-    accumulate.  poison: report the archive of that outgoing index as
-    abandoned (size 0)."""
-
-    def __init__(self, poison=None):
-        self.poison = poison
-
-    def compress(self, tensors):
-        from oracle import oracle as O
-
-        arch = [O.float_compress(A.float_to_words(t, FT_OF[t.dtype]), FT_OF[t.dtype], 10) for t in tensors]
-        comp = torch.zeros(len(arch), max(a.size for a in arch), dtype=torch.uint8)
-        for i, a in enumerate(arch):
-            comp[i, : a.size] = torch.from_numpy(a)
-        sizes = torch.tensor([a.size for a in arch], dtype=torch.int32)
-        if self.poison is not None:
-            sizes[self.poison] = 0
-        return comp, sizes
-
-    @staticmethod
-    def _decode(archive, ft):
-        from oracle import oracle as O
-
-        st, words = O.float_decompress(archive.numpy(), ft, 10)
-        assert st == 0
-        return A.words_to_float(words, ft)
-
-    def decompress(self, archives, outs):
-        for a, o in zip(archives, outs):
-            x = self._decode(a, FT_OF[o.dtype])
-            assert x.numel() == o.numel()
-            o.copy_(x)
-
-    def accumulate(self, archives, accs):
-        for a, acc in zip(archives, accs):
-            ft = int(a[8]) & 0xf  # the header's type word
-            mode = 1 if FT_OF[acc.dtype] == ft else 2
-            acc.copy_(A.model(acc, self._decode(a, ft), mode))
 
 
 def contribution(dtype, src, dst, n, tag=0):
@@ -77,15 +25,6 @@ def contribution(dtype, src, dst, n, tag=0):
     if src > 0 and n > 3:
         x[3] = -contribution(dtype, 0, dst, n, tag)[3]  # an exact cancellation against rank 0
     return x
-
-
-def numels(world, n):
-    """tensors[j]'s numel: n for every j, except that the large case varies it."""
-    return [n + 100 * j if n > 1000 else n for j in range(world)]
-
-
-def sizes_for(world):
-    return (0, 1, world - 1, 12345)
 
 
 def documented_sum(dtype, parts, own, acc_dtype=None):
@@ -101,40 +40,30 @@ def documented_sum(dtype, parts, own, acc_dtype=None):
     return acc.to(dtype)
 
 
-def _save(outdir, name, t):
-    np.save(os.path.join(outdir, name + ".npy"), A.bits(t).numpy())
+def _reduce_worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
 
-
-def _reduce_worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
-
-        codec = OracleCodec()
-        for di, dtype in enumerate(DTYPES):
-            for n in sizes_for(world):
-                ts = [contribution(dtype, rank, j, m, tag=di) for j, m in enumerate(numels(world, n))]
-                keep = [t.clone() for t in ts]
-                got = D.reduce_scatter_compressed(ts, codec=codec)
-                assert got.dtype == dtype and got.dim() == 1
-                assert all(torch.equal(A.bits(a), A.bits(b)) for a, b in zip(ts, keep))
-                _save(outdir, f"rs_{di}_{n}_{rank}", got)
-                x = contribution(dtype, rank, 99, n, tag=di).view(-1, 1) if n else contribution(dtype, rank, 99, n)
-                got = D.all_reduce_compressed(x, codec=codec)
-                assert got.shape == x.shape and got.dtype == dtype
-                _save(outdir, f"ar_{di}_{n}_{rank}", got.reshape(-1))
-        # the sum kept in bf16 itself
-        ts = [contribution(torch.bfloat16, rank, j, 4097, tag=7) for j in range(world)]
-        _save(outdir, f"rsbf_{rank}", D.reduce_scatter_compressed(ts, codec=codec, acc_dtype=torch.bfloat16))
-    finally:
-        dist.destroy_process_group()
+    codec = OracleCodec()
+    for di, dtype in enumerate(DTYPES):
+        for n in sizes_for(world):
+            ts = [contribution(dtype, rank, j, m, tag=di) for j, m in enumerate(numels(world, n))]
+            keep = [t.clone() for t in ts]
+            got = D.reduce_scatter_compressed(ts, codec=codec)
+            assert got.dtype == dtype and got.dim() == 1
+            assert all(torch.equal(A.bits(a), A.bits(b)) for a, b in zip(ts, keep))
+            save_bits(outdir, f"rs_{di}_{n}_{rank}", got)
+            x = contribution(dtype, rank, 99, n, tag=di).view(-1, 1) if n else contribution(dtype, rank, 99, n)
+            got = D.all_reduce_compressed(x, codec=codec)
+            assert got.shape == x.shape and got.dtype == dtype
+            save_bits(outdir, f"ar_{di}_{n}_{rank}", got.reshape(-1))
+    # the sum kept in bf16 itself
+    ts = [contribution(torch.bfloat16, rank, j, 4097, tag=7) for j in range(world)]
+    save_bits(outdir, f"rsbf_{rank}", D.reduce_scatter_compressed(ts, codec=codec, acc_dtype=torch.bfloat16))
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_reduce_scatter_and_all_reduce_follow_the_documented_order(tmp_path, world):
-    mp.spawn(_reduce_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_reduce_worker, world, tmp_path)
     for di, dtype in enumerate(DTYPES):
         it = A.TORCH_INT[dtype]
         for n in sizes_for(world):
@@ -173,40 +102,34 @@ def test_the_order_matters_in_the_inputs_used():
     assert not A.same_bits(own_first, ascending)
 
 
-def _error_worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
+def _error_worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
 
-        msgs = []
-        # rank 1's tensors[0] is one word longer than everybody else's
-        ts = [contribution(torch.bfloat16, rank, j, 500 + (rank == 1 and j == 0)) for j in range(world)]
-        # then: rank 1 reports its first outgoing archive as abandoned
-        for tensors, codec in ((ts, OracleCodec()),
-                               ([contribution(torch.bfloat16, rank, j, 500) for j in range(world)],
-                                OracleCodec(poison=0 if rank == 1 else None))):
-            try:
-                D.reduce_scatter_compressed(tensors, codec=codec)
-                msgs.append("no error")
-            except RuntimeError as e:
-                msgs.append(str(e))
+    msgs = []
+    # rank 1's tensors[0] is one word longer than everybody else's
+    ts = [contribution(torch.bfloat16, rank, j, 500 + (rank == 1 and j == 0)) for j in range(world)]
+    # then: rank 1 reports its first outgoing archive as abandoned
+    for tensors, codec in ((ts, OracleCodec()),
+                           ([contribution(torch.bfloat16, rank, j, 500) for j in range(world)],
+                            OracleCodec(poison=0 if rank == 1 else None))):
         try:
-            D.all_reduce_compressed(contribution(torch.float16, rank, 0, 3000),
-                                    codec=OracleCodec(poison=0 if rank == 1 else None))
+            D.reduce_scatter_compressed(tensors, codec=codec)
             msgs.append("no error")
         except RuntimeError as e:
             msgs.append(str(e))
-        with open(os.path.join(outdir, f"err{rank}.txt"), "w") as f:
-            f.write("\n".join(msgs))
-    finally:
-        dist.destroy_process_group()
+    try:
+        D.all_reduce_compressed(contribution(torch.float16, rank, 0, 3000),
+                                codec=OracleCodec(poison=0 if rank == 1 else None))
+        msgs.append("no error")
+    except RuntimeError as e:
+        msgs.append(str(e))
+    with open(os.path.join(outdir, f"err{rank}.txt"), "w") as f:
+        f.write("\n".join(msgs))
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_numel_mismatch_and_abandoned_archive_raise_on_every_rank(tmp_path, world):
-    mp.spawn(_error_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_error_worker, world, tmp_path)
     for rank in range(world):
         msgs = (tmp_path / f"err{rank}.txt").read_text().split("\n")
         assert len(msgs) == 3, msgs

@@ -8,67 +8,16 @@ accumulate is the sparse model of tests/sparse_accumulate_cases.py, so these
 tests cover the collectives' bookkeeping, the order and the codec's `info`,
 and tests/test_gpu_sparse_accumulate.py the kernel."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import sparse_accumulate_cases as S
+from tests.dist_cases import FT_OF, OracleCodec, numels, run_ranks, save_bits, sizes_for
 
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 ZERO_RANK = 1  # the rank whose contributions are all zero
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-class SparseOracleCodec:
-    """CPU stand-in for dist.GpuSparseFloatCodec: the oracle's sparse
-    archives, the sparse model's accumulate, the sparse header's info."""
-
-    def compress(self, tensors):
-        from oracle import oracle as O
-
-        arch = [O.sparse_compress(S.float_to_words(t, FT_OF[t.dtype]), FT_OF[t.dtype], 10) for t in tensors]
-        comp = torch.zeros(len(arch), max(a.size for a in arch), dtype=torch.uint8)
-        for i, a in enumerate(arch):
-            comp[i, : a.size] = torch.from_numpy(a)
-        return comp, torch.tensor([a.size for a in arch], dtype=torch.int32)
-
-    def info(self, archive):
-        a = archive.numpy()
-        n = int(a[0:4].view(np.uint32)[0])
-        at = 16 + (((n + 7) // 8 + 15) // 16) * 16
-        assert int(a[at:at + 4].view(np.uint32)[0]) == 0xf00f0001
-        return n, S.TORCH_FLOAT[int(a[at + 8]) & 0xf]
-
-    def _words(self, archive):
-        from oracle import oracle as O
-
-        ft = FT_OF[self.info(archive)[1]]
-        st, words = O.sparse_decompress(archive.numpy(), ft, 10)
-        assert st == 0
-        return words, ft
-
-    def decompress(self, archives, outs):
-        for a, o in zip(archives, outs):
-            words, ft = self._words(a)
-            assert words.size == o.numel() and FT_OF[o.dtype] == ft
-            o.copy_(S.words_to_float(words, ft))
-
-    def accumulate(self, archives, accs):
-        for a, acc in zip(archives, accs):
-            words, ft = self._words(a)
-            acc.copy_(S.expected(acc, words, ft, 1 if FT_OF[acc.dtype] == ft else 2))
 
 
 def contribution(dtype, src, dst, n, tag=0):
@@ -93,14 +42,6 @@ def contribution(dtype, src, dst, n, tag=0):
     return x
 
 
-def numels(world, n):
-    return [n + 100 * j if n > 1000 else n for j in range(world)]
-
-
-def sizes_for(world):
-    return (0, 1, world - 1, 12345)
-
-
 def documented_sum(dtype, parts, own, acc_dtype=None):
     """round_dtype((...((x_own + x_r1) + x_r2) + ...)) over the peers whose
     word is nonzero, r1 < r2 < ... the other ranks ascending, every add in
@@ -115,45 +56,35 @@ def documented_sum(dtype, parts, own, acc_dtype=None):
     return acc.to(dtype)
 
 
-def _save(outdir, name, t):
-    np.save(os.path.join(outdir, name + ".npy"), S.bits(t).numpy())
+def _reduce_worker(rank, world, outdir):
+    from dietgpu_fork_amd import dist as D
 
-
-def _reduce_worker(rank, world, port, outdir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from dietgpu_fork_amd import dist as D
-
-        codec = SparseOracleCodec()
-        for di, dtype in enumerate(DTYPES):
-            for n in sizes_for(world):
-                ts = [contribution(dtype, rank, j, m, tag=di) for j, m in enumerate(numels(world, n))]
-                keep = [t.clone() for t in ts]
-                got = D.reduce_scatter_compressed(ts, codec=codec)
-                assert got.dtype == dtype and got.dim() == 1
-                assert all(torch.equal(S.bits(a), S.bits(b)) for a, b in zip(ts, keep))
-                _save(outdir, f"rs_{di}_{n}_{rank}", got)
-                x = contribution(dtype, rank, 99, n, tag=di).view(-1, 1) if n else contribution(dtype, rank, 99, n)
-                got = D.all_reduce_compressed(x, codec=codec)
-                assert got.shape == x.shape and got.dtype == dtype
-                _save(outdir, f"ar_{di}_{n}_{rank}", got.reshape(-1))
-        msg = "no error"
-        try:  # rank 1's tensors[0] is one word longer than everybody else's
-            D.reduce_scatter_compressed([contribution(torch.bfloat16, rank, j, 500 + (rank == 1 and j == 0))
-                                         for j in range(world)], codec=codec)
-        except RuntimeError as e:
-            msg = str(e)
-        with open(os.path.join(outdir, f"err{rank}.txt"), "w") as f:
-            f.write(msg)
-    finally:
-        dist.destroy_process_group()
+    codec = OracleCodec(sparse=True)
+    for di, dtype in enumerate(DTYPES):
+        for n in sizes_for(world):
+            ts = [contribution(dtype, rank, j, m, tag=di) for j, m in enumerate(numels(world, n))]
+            keep = [t.clone() for t in ts]
+            got = D.reduce_scatter_compressed(ts, codec=codec)
+            assert got.dtype == dtype and got.dim() == 1
+            assert all(torch.equal(S.bits(a), S.bits(b)) for a, b in zip(ts, keep))
+            save_bits(outdir, f"rs_{di}_{n}_{rank}", got)
+            x = contribution(dtype, rank, 99, n, tag=di).view(-1, 1) if n else contribution(dtype, rank, 99, n)
+            got = D.all_reduce_compressed(x, codec=codec)
+            assert got.shape == x.shape and got.dtype == dtype
+            save_bits(outdir, f"ar_{di}_{n}_{rank}", got.reshape(-1))
+    msg = "no error"
+    try:  # rank 1's tensors[0] is one word longer than everybody else's
+        D.reduce_scatter_compressed([contribution(torch.bfloat16, rank, j, 500 + (rank == 1 and j == 0))
+                                     for j in range(world)], codec=codec)
+    except RuntimeError as e:
+        msg = str(e)
+    with open(os.path.join(outdir, f"err{rank}.txt"), "w") as f:
+        f.write(msg)
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sparse_reduce_scatter_and_all_reduce_follow_the_documented_order(tmp_path, world):
-    mp.spawn(_reduce_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    run_ranks(_reduce_worker, world, tmp_path)
     for di, dtype in enumerate(DTYPES):
         it = S.bits(torch.zeros(1, dtype=dtype)).dtype
         for n in sizes_for(world):
@@ -200,7 +131,7 @@ def test_the_inputs_tell_the_sparse_sum_from_the_dense_one():
 def test_reduce_archives_reads_the_codecs_info():
     from dietgpu_fork_amd import dist as D
 
-    codec = SparseOracleCodec()
+    codec = OracleCodec(sparse=True)
     for dtype in DTYPES:
         parts = [contribution(dtype, src, 0, 4097, tag=3) for src in (0, 2, 3, 4)]
         comp, sizes = codec.compress(parts[1:])

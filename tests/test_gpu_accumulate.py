@@ -11,14 +11,13 @@ case additionally feeds a GPU-compressed archive).  All accumulators of a call
 live in one buffer of random finite values with at least 16 words between
 them; the buffer is compared whole, so a stray read-modify-write, or any write
 to a failing member's accumulator, fails the test."""
-import socket
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle as O
 from tests import accumulate_cases as A
+from tests.dist_cases import pg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -395,26 +394,6 @@ def test_several_passes_per_workgroup(C, mode):
 
 
 # ----------------------------------------------------------- collectives ----
-
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-@pytest.fixture(scope="module")
-def pg():
-    import torch.distributed as dist
-
-    import dietgpu_fork_amd  # noqa: F401
-
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_port()}", rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    yield
-    dist.destroy_process_group()
-
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32], ids=["bf16", "fp16", "fp32"])
 def test_world_of_one_returns_its_input(pg, dtype):

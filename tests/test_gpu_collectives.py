@@ -2,31 +2,12 @@
 world_size 1 with the "nccl" backend runs the real GPU codec (k_pcompress or
 k_hist -> k_encode, k_decode) and the real RCCL calls; the gloo world-2 test in test_dist.py
 covers the multi-rank bookkeeping on the CPU."""
-import socket
-
 import pytest
 import torch
-import torch.distributed as dist
+
+from tests.dist_cases import pg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-@pytest.fixture(scope="module")
-def pg():
-    import dietgpu_fork_amd  # noqa: F401
-
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_port()}", rank=0,
-                            world_size=1, device_id=torch.device("cuda", 0))
-    yield
-    dist.destroy_process_group()
 
 
 def _bf16(n, seed):

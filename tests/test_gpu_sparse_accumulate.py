@@ -12,8 +12,6 @@ says otherwise.  All accumulators of a call are slices of one buffer of random
 finite values (every fifth one -0.0) with 16 guard words on each side, and the
 buffer is compared whole: zero positions, tails past n, neighbours and failing
 members' accumulators are all checked."""
-import socket
-
 import numpy as np
 import pytest
 import torch
@@ -21,6 +19,7 @@ import torch
 from oracle import oracle as O
 from tests import pyref
 from tests import sparse_accumulate_cases as S
+from tests.dist_cases import pg  # noqa: F401
 from tests.util import SPARSE_LARGE_B, sparse_far_element, sparsify
 
 pytestmark = pytest.mark.gpu
@@ -397,26 +396,6 @@ def test_cpp_entry_point_rejects_checksum_and_bad_acc_type(C, ws):
 
 
 # ----------------------------------------------------------- collectives ----
-
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-@pytest.fixture(scope="module")
-def pg():
-    import torch.distributed as dist
-
-    import dietgpu_fork_amd  # noqa: F401
-
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_port()}", rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    yield
-    dist.destroy_process_group()
-
 
 def sparse_tensor(ft, n, seed):
     """90 % zeros, -0.0 among the nonzero words."""
