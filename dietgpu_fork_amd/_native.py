@@ -42,6 +42,7 @@ def _declare(L):
         "dietgpu_set_barrier_budget": (None, [c_u32]),
         "dietgpu_set_dispatch_skew": (None, [c_u32]),
         "dietgpu_set_compress_path": (None, [c_int]),
+        "dietgpu_set_reduce_max_sources": (None, [c_u32]),
         "dietgpu_version": (ctypes.c_char_p, []),
         "dietgpu_stack_create": (vp, [c_int, P, c_size]),
         "dietgpu_stack_destroy": (None, [vp]),
@@ -83,6 +84,7 @@ def _declare(L):
         "dietgpu_float_decompress_sparse_range": (c_int, [vp, c_int, c_int, c_u32, P, P, P, P, P, P, P]),
         "dietgpu_float_decompress_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
         "dietgpu_float_decompress_sparse_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
+        "dietgpu_float_reduce": (c_int, [vp, c_int, c_int, c_u32, c_u32, P, P, c_int, P, P, c_int, P, P, P]),
         "dietgpu_ans_gather_rows": (c_int, [vp, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_float_gather_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
@@ -128,6 +130,7 @@ def testlib():
                "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
+               "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
                "dietgpu_test_compress_plan": (c_int, [c_int, c_u32, c_u32, c_int, c_int, c_int, P])}
         for name, (res, args) in sig.items():
             f = getattr(T, name)

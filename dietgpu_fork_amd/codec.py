@@ -305,6 +305,76 @@ def _accumulate_types(who, archives, accs, ft):
     return ft, acc_ft
 
 
+REDUCE_MAX_SOURCES = 64
+
+
+def set_reduce_max_sources(ns):
+    """Test / tuning hook: the most sources one k_reduce launch takes (0: the
+    largest instance, the default); more sources chain passes through an fp32
+    partial.  The results are the same bits."""
+    N.lib().dietgpu_set_reduce_max_sources(int(ns))
+
+
+def float_reduce(sources, outs, inits=None, ft=None, prob_bits=10, ws=None):
+    """outs[b] = round((..(inits[b] + x_1) + ..) + x_K), every add in fp32, in
+    one fused kernel (k_reduce) -> (ok, sz).  sources: K lists (1 <= K <= 64)
+    of one dense float archive per member, x_k = sources[k][b]; all K of a
+    member hold the same number of words.  inits: None (the sum starts as
+    x_1), or one tensor per member of the archives' dtype or float32; outs: of
+    the archives' dtype (rounded once) or float32.  `ft` names the archives'
+    type (fp16, bf16 or fp32) and defaults to the outs' (so it must be given
+    for fp32 outs of 16-bit archives).  outs[b] may be inits[b] itself.  A
+    member with a bad archive, differing sizes or a short out fails as a whole:
+    its out and init are untouched.  No checksum is verified."""
+    ft, init_ft, out_ft = _reduce_types(sources, outs, inits, ft)
+    K, nb = len(sources), len(outs)
+    dev = outs[0].device
+    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
+    sz = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    N.check(N.lib().dietgpu_float_reduce(
+        ws.h, ft, prob_bits, nb, K, N.ptr_array([a.data_ptr() for row in sources for a in row]),
+        N.ptr_array([t.data_ptr() for t in inits]) if inits is not None else None, init_ft,
+        N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]), out_ft,
+        ok.data_ptr(), sz.data_ptr(), _s()))
+    return ok, sz
+
+
+def _reduce_types(sources, outs, inits, ft):
+    """float_reduce's argument checks, before the library is touched -> (the
+    archives' float type, the inits' (0: none), the outs')."""
+    who = "float_reduce"
+    K, nb = len(sources), len(outs)
+    if not 1 <= K <= REDUCE_MAX_SOURCES:
+        raise ValueError(f"{who}: the number of sources ({K}) must be in 1 .. {REDUCE_MAX_SOURCES}")
+    if nb == 0:
+        raise ValueError(f"{who}: empty batch")
+    if any(len(row) != nb for row in sources) or (inits is not None and len(inits) != nb):
+        raise ValueError(f"{who}: every source list, inits and outs must have one entry per member")
+    for what, ts in (("outs", outs), ("inits", inits)):
+        if ts is None:
+            continue
+        if any(t.dtype != ts[0].dtype for t in ts):
+            raise ValueError(f"{who}: the {what} must share a dtype")
+        if ts[0].dtype not in FLOAT_TYPE:
+            raise ValueError(f"{who}: unsupported {what} dtype {ts[0].dtype}")
+        if any(not t.is_contiguous() for t in ts):
+            raise ValueError(f"{who}: the {what} must be contiguous")
+    out_ft = FLOAT_TYPE[outs[0].dtype]
+    init_ft = FLOAT_TYPE[inits[0].dtype] if inits is not None else 0
+    ft = ft or out_ft
+    if ft not in (1, 2, 3):
+        raise ValueError(f"{who}: fp16, bf16 or fp32 archives only, not float type {ft}")
+    if out_ft not in (ft, 3):
+        raise ValueError(f"{who}: out type {out_ft} does not go with float type {ft}")
+    if inits is not None and init_ft not in (ft, 3):
+        raise ValueError(f"{who}: init type {init_ft} does not go with float type {ft}")
+    tensors = [a for row in sources for a in row] + list(outs) + list(inits or [])
+    if any(not t.is_cuda for t in tensors):
+        raise ValueError(f"{who}: archives, inits and outs must be CUDA tensors")
+    return ft, init_ft, out_ft
+
+
 # ---------------------------------------------------------------- range ----
 
 def _range_launch(fn, head, dev, nb, in_ptrs, firsts, counts, out_ptrs, ws):

@@ -346,6 +346,20 @@ int dietgpu_float_decompress_sparse_accumulate(dietgpu_stack* res, int ft, int p
   });
 }
 
+int dietgpu_float_reduce(dietgpu_stack* res, int ft, int pb, uint32_t nb, uint32_t num_sources, const void** in,
+                         const void** init, int init_type, void** out, const uint32_t* cap, int out_type,
+                         uint8_t* succ, uint32_t* sizes, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkReduceShape(ft, num_sources, init != nullptr, init_type, out_type);
+    checkProbBits(pb);
+    floatReduceArchives(R(res), cfg, nb, num_sources, in, init, FloatType(init_type), out, cap,
+                        FloatType(out_type), succ, sizes, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 // (the gather entry points check the flattened config and the row shape
 // before they look at the stack or any pointer)
 int dietgpu_ans_gather_rows(dietgpu_stack* res, int pb, const void* archive_dev, uint32_t row_words,
@@ -395,6 +409,7 @@ void dietgpu_set_spin_cap(uint32_t polls) { setSpinCap(polls); }
 void dietgpu_set_barrier_budget(uint32_t ticks) { setBarrierBudget(ticks); }
 void dietgpu_set_dispatch_skew(uint32_t ticks) { setDispatchSkew(ticks); }
 void dietgpu_set_compress_path(int mode) { setCompressPath(mode < 0 || mode > 2 ? 0 : mode); }
+void dietgpu_set_reduce_max_sources(uint32_t sources) { setReduceMaxSources(sources); }
 
 void dietgpu_profile_enable(int on) { prof::setEnabled(on != 0); }
 void dietgpu_profile_filter(const char* kernel) { prof::setFilter(kernel); }

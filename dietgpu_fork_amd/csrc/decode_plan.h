@@ -3,7 +3,8 @@
 // their waves run with remaining-work priorities.  Host only and free of HIP
 // headers, so that the rule -- performance policy, DESIGN.md 5.2 -- is stated
 // once and tested without a GPU (tests/test_decode_plan.py).  Below it the
-// grid rule of k_gather (gather.h; tests/test_gather_plan.py).
+// grid rule of k_gather (gather.h; tests/test_gather_plan.py) and the pass and
+// grid rules of k_reduce (reduce.h; tests/test_reduce_plan.py).
 #pragma once
 
 #include <algorithm>
@@ -91,6 +92,50 @@ inline GatherPlan planGather(uint32_t numIdx, uint32_t rowWords, uint32_t slots)
   if (tasks >= (1ull << 32)) return {false, K, 0, 0};
   const uint32_t groups = uint32_t((tasks + kGatherTasksPerWG - 1) / kGatherTasksPerWG);
   return {true, K, groups, std::min(std::max(1u, slots), groups)};
+}
+
+// The pass rule of the fused reduce (k_reduce, reduce.h; DESIGN.md 5.2g;
+// tests/test_reduce_plan.py): K sources, at most nsMax per launch.  The
+// sources go to the passes in order, evenly (the larger passes first: fewer
+// sources per launch leave more workgroups resident); every pass but the last
+// writes an fp32 partial that the next one reads as its init, so the order of
+// the adds, and with it every bit, is that of one pass over all K.
+constexpr uint32_t kReduceMaxSources = 64;
+
+struct ReducePass {
+  uint32_t first, count;  // sources [first, first + count)
+  bool initIsPartial;     // reads the partial (else the caller's init, if any)
+  bool outIsPartial;      // writes the partial (else the caller's out)
+};
+
+struct ReducePlan {
+  bool valid;  // 1 <= K <= kReduceMaxSources, nsMax >= 1
+  uint32_t numPasses;
+  ReducePass passes[kReduceMaxSources];
+  uint64_t partialBytes;  // fp32 words of every member's capacity, each padded to 4; 0 for one pass
+};
+
+// partialWords: the sum over the members of their capacity rounded up to 4
+// words (a member's partial starts 16 B-aligned).
+inline ReducePlan planReduce(uint32_t K, uint32_t nsMax, uint64_t partialWords) {
+  ReducePlan p{};
+  p.valid = K >= 1 && K <= kReduceMaxSources && nsMax >= 1;
+  if (!p.valid) return p;
+  p.numPasses = (K + nsMax - 1) / nsMax;
+  uint32_t first = 0;
+  for (uint32_t i = 0; i < p.numPasses; ++i) {
+    const uint32_t count = K / p.numPasses + (i < K % p.numPasses ? 1 : 0);
+    p.passes[i] = {first, count, i > 0, i + 1 < p.numPasses};
+    first += count;
+  }
+  p.partialBytes = p.numPasses > 1 ? 4 * partialWords : 0;
+  return p;
+}
+
+// The grid of one pass over a slice of ny members: k_decode's accumulate rule
+// on the resident workgroups of the k_reduce instance launched.
+inline DecodePlan planReduceGrid(uint32_t maxBlocks, uint32_t blocksPerWG, uint32_t ny, uint32_t slots) {
+  return planDecode(DecodeForm::kAccumulate, false, maxBlocks, blocksPerWG, ny, std::max(1u, slots));
 }
 
 }  // namespace dietgpu

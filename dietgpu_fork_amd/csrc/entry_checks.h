@@ -24,7 +24,7 @@ inline void checkFloatConfig(const FloatCodecConfig& c) {
 
 // The forms that decode part of an element, or add it to something: none can
 // verify the archive's checksum, and a config that asks for it is refused.
-enum class PartialDecode { kRange, kGather, kAccumulate };
+enum class PartialDecode { kRange, kGather, kAccumulate, kReduce };
 
 inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
   switch (what) {
@@ -39,7 +39,26 @@ inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
                "a decode-and-accumulate cannot verify a checksum (the accumulator no longer holds the decoded "
                "words)");
       break;
+    case PartialDecode::kReduce:
+      DG_CHECK(!useChecksum, "a fused reduce cannot verify a checksum (the decoded words are never stored)");
+      break;
   }
+}
+
+// The fused reduce (floatReduceArchives; float types as FloatType's values):
+// fp16, bf16 and fp32 archives, 1 .. 64 sources, an init (if any) and an out
+// of the archives' type or fp32.  The C ABI makes the same checks before it
+// looks at the stack or any pointer.
+inline void checkReduceShape(int floatType, uint32_t numSources, bool hasInit, int initType, int outType) {
+  DG_CHECK(floatType >= 1 && floatType <= 3, "a fused reduce takes fp16, bf16 or fp32 archives (float type 1..3), not "
+                                                 << floatType);
+  DG_CHECK(numSources >= 1 && numSources <= kReduceMaxSources,
+           "numSources (" << numSources << ") must be in 1 .. " << kReduceMaxSources);
+  DG_CHECK(outType == floatType || outType == 3,
+           "out type " << outType << " does not go with float type " << floatType << " (the archives' type, or fp32)");
+  DG_CHECK(!hasInit || initType == floatType || initType == 3,
+           "init type " << initType << " does not go with float type " << floatType
+                        << " (the archives' type, or fp32)");
 }
 
 // An accumulator has the archive's own float type, or is fp32 for an fp16 /

@@ -54,6 +54,9 @@ uint32_t dispatchSkew() { return gDispatchSkew.load(); }
 std::atomic<int> gCompressPath{0};
 void setCompressPath(int mode) { gCompressPath.store(mode); }
 int compressPath() { return gCompressPath.load(); }
+std::atomic<uint32_t> gReduceMaxSources{0};
+void setReduceMaxSources(uint32_t ns) { gReduceMaxSources.store(ns); }
+uint32_t reduceMaxSources() { return gReduceMaxSources.load(); }
 
 SyncLease::SyncLease(StackDeviceMemory& res, hipStream_t stream, const size_t (&bytesIn)[kSyncRegions],
                      bool dequeue, size_t rowsBytes) {

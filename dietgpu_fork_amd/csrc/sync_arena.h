@@ -114,4 +114,10 @@ uint32_t dispatchSkew();
 void setCompressPath(int mode);
 int compressPath();
 
+// Test / tuning hook: the most sources one k_reduce launch takes (reduce.h);
+// 0 (default) and anything above the largest instance mean that instance.
+// Results are the same bits whatever the value (planReduce, decode_plan.h).
+void setReduceMaxSources(uint32_t ns);
+uint32_t reduceMaxSources();
+
 }  // namespace dietgpu

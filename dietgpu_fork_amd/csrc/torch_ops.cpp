@@ -17,7 +17,9 @@
 // the twelfth, decompress_data_accumulate: it adds each archive's element to
 // an accumulator tensor in place (floatDecompressAccumulate).  A thirteenth,
 // gather_rows, gathers rows of a table held by one archive, named by an index
-// tensor on the device (floatGatherRows / ansGatherRows).
+// tensor on the device (floatGatherRows / ansGatherRows).  A fourteenth,
+// reduce_data, decodes several archives per member and sums them in one
+// kernel (floatReduceArchives).
 //
 // Argument checks the reference lacks (its DietGpu.cpp says "FIXME: total
 // range checking" where they belong); each raises before any temp-memory
@@ -569,6 +571,86 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
   return int64_t(res.getMaxMemoryUsage());
 }
 
+// Extension (no reference counterpart): the fused multi-archive reduce
+// (floatReduceArchives).  ts_in holds num_sources archives per member,
+// source-major: archive k of member b is ts_in[k * len(ts_out) + b].
+//   ts_out[b] = round((..(ts_init[b] + x_1) + ..) + x_K), every add in fp32
+// in one kernel pass over the K archives (without ts_init the sum starts as
+// x_1).  The outputs share one dtype, as do the inits: float16 / bfloat16
+// name the archives' type themselves; when both are float32 (or there is no
+// init and the outputs are float32) the archives' type is read from ts_in[0]'s
+// header, as decompress_data_accumulate does, and the call synchronises the
+// stream once.  ts_out[b] may be ts_init[b].  A member with an invalid
+// archive, archives of different sizes or a short output fails as a whole
+// with status 0 and is left untouched.
+int64_t reduce_data(const std::vector<at::Tensor>& tsIn, int64_t numSources, const std::vector<at::Tensor>& tsOut,
+                    const std::optional<std::vector<at::Tensor>>& tsInit, const std::optional<at::Tensor>& tempMem,
+                    const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
+  TORCH_CHECK(numSources >= 1 && numSources <= 64, "num_sources (", numSources, ") must be in 1 .. 64");
+  TORCH_CHECK(!tsOut.empty() && int64_t(tsIn.size()) == numSources * int64_t(tsOut.size()),
+              "ts_in must hold num_sources archives for each of the (one or more) ts_out");
+  TORCH_CHECK(!tsInit || tsInit->size() == tsOut.size(), "ts_init and ts_out must have the same length");
+  auto sharedDtype = [](const std::vector<at::Tensor>& ts, const char* name) {
+    for (const auto& t : ts) {
+      const auto d = t.scalar_type();
+      TORCH_CHECK(d == at::kHalf || d == at::kBFloat16 || d == at::kFloat, name,
+                  " must be float16, bfloat16 or float32");
+      TORCH_CHECK(d == ts.front().scalar_type(), name, " must share a dtype");
+    }
+    return ts.front().scalar_type();
+  };
+  const at::ScalarType outD = sharedDtype(tsOut, "ts_out");
+  const at::ScalarType initD = tsInit ? sharedDtype(*tsInit, "ts_init") : outD;
+  TORCH_CHECK(outD == at::kFloat || initD == at::kFloat || outD == initD,
+              "ts_init and ts_out name different 16-bit archive types");
+  const int dev = inputDevice(tsIn);
+  c10::hip::HIPGuard guard(dev);
+  const size_t nb = tsOut.size();
+  std::vector<const void*> in(tsIn.size()), init(tsInit ? nb : 0);
+  std::vector<void*> out(nb);
+  std::vector<uint32_t> cap(nb);
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    checkArchiveTensor(tsIn[i], dev);
+    in[i] = tsIn[i].data_ptr();
+  }
+  for (size_t b = 0; b < nb; ++b) {
+    const auto& to = tsOut[b];
+    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
+                "ts_out must be contiguous GPU tensors on the input device");
+    TORCH_CHECK(uint64_t(to.numel()) <= kU32Max);
+    out[b] = to.data_ptr();
+    cap[b] = uint32_t(to.numel());
+    if (tsInit) {
+      const auto& ti = (*tsInit)[b];
+      TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous(),
+                  "ts_init must be contiguous GPU tensors on the input device");
+      // (a member whose element is longer than its init fails like one whose
+      // output is short: the capacity covers both)
+      cap[b] = uint32_t(std::min<int64_t>(to.numel(), ti.numel()));
+      init[b] = ti.data_ptr();
+    }
+  }
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(nb), dev);
+  auto res = makeStack(dev, tempMem);
+  const hipStream_t s = currentStream(dev);
+  const FloatType outType = floatTypeOf(outD), initType = floatTypeOf(initD);
+  FloatType ft = outType != FloatType::kFloat32 ? outType : initType;
+  if (ft == FloatType::kFloat32) {
+    at::Tensor type = at::zeros({1}, tsIn.front().options().dtype(at::kInt));
+    floatGetCompressedInfo(res, in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
+                           s);
+    const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
+    TORCH_CHECK(t0 != 4, "reduce_data takes float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
+    // (anything that is no float archive is reduced as fp32 and fails on the
+    // device with status 0, like any other invalid member)
+    if (t0 == 1 || t0 == 2) ft = FloatType(t0);
+  }
+  const FloatDecompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, false);
+  floatReduceArchives(res, cfg, uint32_t(nb), uint32_t(numSources), in.data(), tsInit ? init.data() : nullptr,
+                      initType, out.data(), cap.data(), outType, st, sz, s);
+  return int64_t(res.getMaxMemoryUsage());
+}
+
 // Extension (no reference counterpart): rows t_idx[...] of the [R, row_words]
 // table that archive t_in holds, into t_out [*t_idx.shape, row_words]
 // (floatGatherRows / ansGatherRows).  t_idx is an int32 or int64 tensor on the
@@ -743,6 +825,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "gather_rows(bool compress_as_float, Tensor t_in, int row_words, Tensor t_idx, Tensor t_out, Tensor? "
       "temp_mem=None, Tensor? out_status=None) -> int");
+  m.def(
+      "reduce_data(Tensor[] ts_in, int num_sources, Tensor[] ts_out, Tensor[]? ts_init=None, Tensor? temp_mem=None, "
+      "Tensor? out_status=None, Tensor? out_sizes=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -759,4 +844,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("decompress_data_range", &dietgpu::decompress_data_range);
   m.impl("decompress_data_accumulate", &dietgpu::decompress_data_accumulate);
   m.impl("gather_rows", &dietgpu::gather_rows);
+  m.impl("reduce_data", &dietgpu::reduce_data);
 }

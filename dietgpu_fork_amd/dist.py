@@ -92,6 +92,21 @@ class GpuFloatCodec(_GpuCodec):
         ops.decompress_data_accumulate(archives, accs, out_status=status)
         self._raise_on_failure(status)
 
+    def reduce(self, own, archives, out_dtype):
+        """round_out_dtype((...((own + x_1) + x_2) + ...)) over the elements
+        x_k of `archives`, every add in float32, in one fused kernel pass
+        (k_reduce; ops.reduce_data): no accumulator between the peers.
+        own=None: the sum starts as x_1.  float16, bfloat16 and float32."""
+        from . import ops
+
+        device = archives[0].device
+        n = own.numel() if own is not None else self.info(archives[0])[0]
+        out = torch.empty(n, dtype=out_dtype, device=device)
+        status = torch.empty(1, dtype=torch.uint8, device=device)
+        ops.reduce_data(list(archives), len(archives), [out], None if own is None else [own], out_status=status)
+        self._raise_on_failure(status)
+        return out
+
 
 class GpuSparseFloatCodec(_GpuCodec):
     """The sparse float codec on the local GPU (codec.sparse_compress /
@@ -325,6 +340,20 @@ def _acc_dtype(dtype, acc_dtype):
     return acc_dtype
 
 
+_FUSED_REDUCE_MAX = 64  # sources of one fused call (codec.REDUCE_MAX_SOURCES)
+
+
+def _fused_reduce(codec, dtype, acc_dtype, num_archives):
+    """The routing rule of reduce_archives: the fused kernel
+    takes the reduction when the codec has one (`reduce`), the adds are
+    float32 adds of float16, bfloat16 or float32 tensors, and there are 1 ..
+    64 archives; everything else (a codec without `reduce`, a 16-bit
+    accumulator that rounds at every add, float64) keeps the per-peer loop.
+    Both give the same bits."""
+    return (hasattr(codec, "reduce") and acc_dtype == torch.float32
+            and dtype in (torch.float16, torch.bfloat16, torch.float32) and 1 <= num_archives <= _FUSED_REDUCE_MAX)
+
+
 def reduce_archives(own, archives, codec, acc_dtype=None):
     """The local part of a compressed reduction: `own` (this rank's flat,
     uncompressed contribution) plus the elements of `archives` (the peers'
@@ -334,8 +363,11 @@ def reduce_archives(own, archives, codec, acc_dtype=None):
 
     every add correctly rounded in acc_dtype (default: float32 for float16 /
     bfloat16 tensors, else the tensors' dtype) and the result rounded once to
-    the tensors' dtype.  One codec.accumulate call per peer; no decoded
-    temporary.  The accumulator starts as `own` converted to acc_dtype, not as
+    the tensors' dtype.  With float32 adds and a codec that has a fused
+    `reduce` (GpuFloatCodec) the whole sum is one codec.reduce call, the
+    running sum in registers (_fused_reduce states the rule); otherwise one
+    codec.accumulate call per peer.  No decoded temporary either way, and the
+    same bits.  The accumulator starts as `own` converted to acc_dtype, not as
     +0.0: with no archives the result is `own` bit for bit (-0.0 included).
     own=None: the first archive's element takes the place of `own` (its numel
     and dtype come from codec.info(archive), or from a dense float header when
@@ -343,9 +375,13 @@ def reduce_archives(own, archives, codec, acc_dtype=None):
     With GpuSparseFloatCodec a peer's zero words are skipped: the sum runs
     over the peers whose word is nonzero, which is the same value except that
     a running sum of -0.0 stays -0.0 where a peer holds +0.0."""
+    if own is None and not archives:
+        raise ValueError("reduce_archives: nothing to reduce")
+    dtype = own.dtype if own is not None else getattr(codec, "info", _archive_info)(archives[0])[1]
+    if _fused_reduce(codec, dtype, _acc_dtype(dtype, acc_dtype), len(archives)):
+        flat = None if own is None else own.contiguous().view(-1)
+        return codec.reduce(flat, archives, dtype)
     if own is None:
-        if not archives:
-            raise ValueError("reduce_archives: nothing to reduce")
         n, dtype = getattr(codec, "info", _archive_info)(archives[0])
         own = torch.empty(n, dtype=dtype, device=archives[0].device)
         codec.decompress([archives[0]], [own])

@@ -9,7 +9,8 @@ with the same schemas, validation and return values).  An eleventh,
 decodes a word range of each archive.  A twelfth,
 ``decompress_data_accumulate``, adds each archive's element to an accumulator
 tensor in place.  ``gather_rows`` (``MORE_OPS``) gathers rows of a table held
-by one archive, named by an index tensor on the device.  This module only
+by one archive, named by an index tensor on the device; ``reduce_data``
+(``REDUCE_OPS``) sums several archives per member in one kernel.  This module only
 loads that library
 and forwards ``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.
 """
@@ -41,6 +42,10 @@ OPS = (
 # of a table held by one archive, named by an index tensor on the device
 MORE_OPS = ("gather_rows",)
 
+# reduce_data decodes num_sources archives per member and sums them in one
+# kernel (the fused reduce of the reducing collectives)
+REDUCE_OPS = ("reduce_data",)
+
 _LOADED = False
 
 
@@ -59,7 +64,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS or name in MORE_OPS:
+    if name in OPS or name in MORE_OPS or name in REDUCE_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

@@ -188,6 +188,36 @@ void floatDecompressAccumulate(StackDeviceMemory& res,
                                uint8_t* outSuccess_dev, uint32_t* outSize_dev,
                                hipStream_t stream);
 
+// Fused multi-archive reduce: for member b, the numSources dense float
+// archives x_1 .. x_K = in[k * numInBatch + b] (source-major), each of n words:
+//   out[b][i] = round((...((init[b][i] + x_1[i]) + x_2[i]) + ...) + x_K[i])
+// for 0 <= i < n, in one kernel pass over all K archives with the running sum
+// in registers (K above the kernel's source limit: chained passes through an
+// fp32 partial taken from `res`; the split never changes the order or the
+// bits).  config.floatType is kFloat16, kBFloat16 or kFloat32; every add is
+// one correctly rounded fp32 add (archive words widened exactly).  init may be
+// null (the sum then starts as float(x_1), not +0.0: K = 1 returns the decoded
+// element, -0.0 included), else initType is config.floatType or kFloat32.
+// outType is config.floatType (the sum rounded once, to nearest even) or
+// kFloat32 (not rounded).  numSources in 1 .. 64; anything else throws.
+// out[b] may be init[b] itself when the types agree; any other overlap is
+// undefined and not checked.  in[.] 4-byte aligned, init[b] / out[b] aligned
+// to their words, outCapacity[b] in out words.  outSuccess_dev[b] = 1 iff all
+// K archives are valid for this config, hold the same n, and
+// outCapacity[b] >= n; outSize_dev[b] = n when all K are valid and agree, else
+// 0.  A member fails as a whole: its out and init are neither read nor
+// written, and nothing outside out[b][0 .. n) ever is.  config.useChecksum
+// must be false, for floatDecompressAccumulate's reason (archives written with
+// a checksum reduce normally).  No host synchronisation, no allocation outside
+// `res`: the call can be captured in a graph and replayed on new archive bytes.
+void floatReduceArchives(StackDeviceMemory& res,
+                         const FloatDecompressConfig& config,
+                         uint32_t numInBatch, uint32_t numSources,
+                         const void** in, const void** init, FloatType initType,
+                         void** out, const uint32_t* outCapacity,
+                         FloatType outType, uint8_t* outSuccess_dev,
+                         uint32_t* outSize_dev, hipStream_t stream);
+
 // Sparse decode-and-accumulate: acc[b][i] = acc[b][i] + x[i] for every i < n
 // whose bit is set in the bitmap of sparse float archive in[b] (x: the n-word
 // element it encodes; a word is "set" iff it is not +0.0 bitwise, so -0.0 is

@@ -207,6 +207,20 @@ int dietgpu_float_decompress_accumulate(dietgpu_stack* res, int float_type, int 
                                         uint8_t* out_success_dev, uint32_t* out_size_dev,
                                         void* stream);
 
+/* Fused multi-archive reduce (floatReduceArchives, GpuFloatCodec.h):
+ * out[b][i] = round((..(init[b][i] + x_1[i]) + ..) + x_K[i]), every add in
+ * fp32, where x_k is the element dense float archive in[k * num_in_batch + b]
+ * encodes (source-major; float_type 1..3, num_sources 1..64).  init may be
+ * null (the sum starts as x_1), else init_type is float_type or 3 (fp32);
+ * out_type is float_type (rounded once) or 3.  out_capacity counts out words.
+ * A member succeeds iff all its archives are valid, hold the same number of
+ * words n and out_capacity[b] >= n; a failing member's out and init are left
+ * alone.  Archives written with a checksum are accepted; none is verified. */
+int dietgpu_float_reduce(dietgpu_stack* res, int float_type, int prob_bits, uint32_t num_in_batch,
+                         uint32_t num_sources, const void** in, const void** init, int init_type,
+                         void** out, const uint32_t* out_capacity, int out_type,
+                         uint8_t* out_success_dev, uint32_t* out_size_dev, void* stream);
+
 /* ... of sparse float archives (floatDecompressSparseAccumulate,
  * GpuFloatCodec.h; in[b] 16-byte aligned): acc[b][i] += word i of the element
  * for every i whose bitmap bit is set, i.e. whose word is not +0.0 bitwise.
@@ -294,6 +308,11 @@ void dietgpu_set_dispatch_skew(uint32_t ticks);
  * symbols, no caller histogram); 2: always the three-kernel path.  Archives
  * are byte-identical whatever the mode; other values mean 0. */
 void dietgpu_set_compress_path(int mode);
+/* Test / tuning hook: the most sources one launch of the fused reduce's kernel
+ * takes; a call with more chains passes through an fp32 partial.  0 (default)
+ * and anything above the largest kernel instance (4) mean that instance.
+ * Results are the same bits whatever the value. */
+void dietgpu_set_reduce_max_sources(uint32_t sources);
 
 #ifdef __cplusplus
 }

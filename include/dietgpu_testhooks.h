@@ -65,6 +65,14 @@ int dietgpu_test_sparse_accumulate_config(dietgpu_stack* res, int float_type, in
                                           const void* in, void* acc, uint32_t acc_capacity,
                                           uint8_t* out_success_dev, uint32_t* out_size_dev, void* stream);
 
+/* Calls floatReduceArchives for one member of num_sources archives `in` with
+ * `use_checksum` set in its config (the C ABI carries no checksum flag): no
+ * init, an output of float_type.  DIETGPU_ERR_INVALID when the entry point
+ * throws, DIETGPU_OK after a reduce. */
+int dietgpu_test_reduce_config(dietgpu_stack* res, int float_type, int use_checksum, uint32_t num_sources,
+                               const void** in, void* out, uint32_t out_capacity, uint8_t* out_success_dev,
+                               uint32_t* out_size_dev, void* stream);
+
 /* The same for the row gather's C++ entry points (floatGatherRows,
  * ansGatherRows; float_type 0 = the byte codec): num_idx int64 indices at
  * idx_dev, rows of row_words words at a stride of row_words. */
