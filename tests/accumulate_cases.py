@@ -10,13 +10,10 @@ tensors of the float dtype.  Seeded, numpy and torch only."""
 import numpy as np
 import torch
 
-from tests.util import NP_WORD
+from tests.util import FT_IDS, NP_SIGNED, NP_WORD, TORCH_FLOAT
 
-TORCH_FLOAT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
 TORCH_INT = {torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32,
              torch.float64: torch.int64}
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-FT_IDS = {1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
 # (float type, mode): the six kernel instances
 MODES = ((1, 1), (2, 1), (3, 1), (4, 1), (1, 2), (2, 2))
 MODE_IDS = [f"{FT_IDS[ft]}-acc{m}" for ft, m in MODES]

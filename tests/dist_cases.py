@@ -14,8 +14,7 @@ import torch.multiprocessing as mp
 
 from tests import accumulate_cases as A
 from tests import sparse_accumulate_cases as S
-
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
+from tests.util import FT_OF
 
 
 def free_port():

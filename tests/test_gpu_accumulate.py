@@ -18,48 +18,39 @@ import torch
 from oracle import oracle as O
 from tests import accumulate_cases as A
 from tests.dist_cases import pg  # noqa: F401
+from tests.gpu_harness import (C, DEV, GUARD as CANARY, Cache, Member, accumulate_call, check_placed,  # noqa: F401
+                               compress_one, expected_placed, place_members, workspace_fixture)
+from tests.util import FT_OF
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-CANARY = 16
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
-
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(64 << 20)
-
-
-_ARCH = {}
+ws = workspace_fixture(64 << 20)
+_ARCH = Cache()
+NAMES = {"codec": "float_decompress_accumulate", "op": "decompress_data_accumulate",
+         "capi": "dietgpu_float_decompress_accumulate"}
 
 
 def oracle_archive(ft, n, seed=0, pb=10, checksum=False):
     """(words, archive bytes) from the CPU oracle, computed once per key."""
-    key = (ft, n, seed, pb, checksum)
-    if key not in _ARCH:
+    def make():
         w = A.member_words(ft, n, seed=seed)
-        _ARCH[key] = (w, O.float_compress(w, ft, pb, checksum))
-    return _ARCH[key]
+        return w, O.float_compress(w, ft, pb, checksum)
+    return _ARCH.get((ft, n, seed, pb, checksum), make)
 
 
-class M:
+def M(arch, x, cap=None, acc_off=0, arch_off=0, ok=True, size=None):
     """One member of a call: archive bytes, the words it encodes (None: it
-    must fail), the accumulator's capacity and the two alignments."""
+    must fail, and reports size 0 unless `size` says otherwise), the
+    accumulator's capacity and the two alignments."""
+    return Member(arch, x, cap, acc_off, arch_off, ok, size)
 
-    def __init__(self, arch, x, cap=None, acc_off=0, arch_off=0, ok=True, size=None):
-        self.arch, self.x, self.ok = arch, x, ok
-        self.cap = (x.size if x is not None else 0) if cap is None else cap
-        self.acc_off, self.arch_off = acc_off, arch_off
-        self.size = (x.size if (ok and x is not None) else 0) if size is None else size
+
+def model_of(ft, mode):
+    """(apply, touched, compare) of expected_placed() / check_placed(): the
+    model adds every word, and the buffer is compared with same_bits."""
+    return (lambda acc, w: A.model(acc, A.words_to_float(w, ft), mode),
+            lambda w: torch.ones(w.size, dtype=torch.bool),
+            lambda got, want, init, touch: None if A.same_bits(got, want) else A.mismatch_report(got, want))
 
 
 def place(ft, mode, members, seed=0, acc_init=None):
@@ -67,76 +58,24 @@ def place(ft, mode, members, seed=0, acc_init=None):
     arch_off bytes inside one uint8 buffer, every accumulator acc_off words
     past a 16 B boundary inside one buffer `buf` of random finite values
     (`init` is its CPU copy), CANARY words apart at least."""
-    dt = A.acc_dtype(ft, mode)
-    per16 = 16 // dt.itemsize
-    starts, cur = [], 0
-    for m in members:
-        st = -(-(cur + CANARY) // per16) * per16 + m.acc_off
-        starts.append(st)
-        cur = st + m.cap + CANARY
-    total = cur + per16
-    init = A.random_acc(ft, mode, total, seed=seed) if acc_init is None else acc_init(total)
-    buf = init.to(DEV)
-    assert buf.data_ptr() % 16 == 0
-    offs, cur = [], 0
-    for m in members:
-        offs.append(cur + m.arch_off)
-        cur = -(-(cur + m.arch_off + m.arch.size) // 16) * 16
-    ab = torch.zeros(cur + 16, dtype=torch.uint8, device=DEV)
-    assert ab.data_ptr() % 16 == 0
-    host = np.zeros(cur + 16, dtype=np.uint8)
-    for m, o in zip(members, offs):
-        host[o:o + m.arch.size] = m.arch
-    ab.copy_(torch.from_numpy(host))
-    archives = [ab[o:o + m.arch.size] for m, o in zip(members, offs)]
-    accs = [buf[st:st + m.cap] for m, st in zip(members, starts)]
-    return archives, accs, buf, init, starts
+    init = (lambda total: A.random_acc(ft, mode, total, seed=seed)) if acc_init is None else acc_init
+    return place_members(members, A.acc_dtype(ft, mode), init)
 
 
 def expected(ft, mode, members, init, starts):
-    want = init.clone()
-    for m, st in zip(members, starts):
-        if m.ok:
-            x = A.words_to_float(m.x, ft)
-            want[st:st + x.numel()] = A.model(want[st:st + x.numel()], x, mode)
-    return want
+    return expected_placed(members, init, starts, *model_of(ft, mode)[:2])[0]
 
 
 def call(api, C, ws, ft, mode, archives, accs, pb=10, with_status=True, temp_mem=True):
     """-> (ok, sz) CPU lists, or None without status tensors."""
-    nb = len(archives)
-    ok = torch.full([nb], 7, dtype=torch.uint8, device=DEV) if with_status else None
-    sz = torch.full([nb], -7, dtype=torch.int32, device=DEV) if with_status else None
-    if api == "codec":
-        assert with_status
-        ok, sz = C.float_decompress_accumulate(archives, accs, ft=ft, prob_bits=pb, ws=ws)
-    elif api == "op":
-        assert pb == 10
-        tmp = ws.buf if temp_mem else None
-        used = torch.ops.dietgpu.decompress_data_accumulate(archives, accs, tmp, ok, sz)
-        assert isinstance(used, int) and used >= 0
-    else:
-        from dietgpu_fork_amd import _native as N
-
-        rc = N.lib().dietgpu_float_decompress_accumulate(
-            ws.h, ft, pb, nb, N.ptr_array([a.data_ptr() for a in archives]),
-            N.ptr_array([a.data_ptr() for a in accs]), N.u32_array([a.numel() for a in accs]),
-            3 if mode == 2 else ft, ok.data_ptr() if with_status else None,
-            sz.data_ptr() if with_status else None, torch.cuda.current_stream().cuda_stream)
-        assert rc == 0, N.lib().dietgpu_last_error()
-    torch.cuda.synchronize()
-    return (ok.cpu().tolist(), sz.cpu().tolist()) if with_status else None
+    return accumulate_call(api, NAMES, C, ws, ft, mode, archives, accs, [a.data_ptr() for a in accs], pb,
+                           with_status, temp_mem)
 
 
 def run(api, C, ws, ft, mode, members, pb=10, with_status=True, temp_mem=True, seed=0):
     archives, accs, buf, init, starts = place(ft, mode, members, seed=seed)
     st = call(api, C, ws, ft, mode, archives, accs, pb, with_status, temp_mem)
-    if st is not None:
-        assert st[0] == [int(m.ok) for m in members]
-        assert st[1] == [m.size for m in members]
-    want = expected(ft, mode, members, init, starts)
-    got = buf.cpu()
-    assert A.same_bits(got, want), A.mismatch_report(got, want)
+    check_placed(members, st, buf.cpu(), init, starts, *model_of(ft, mode))
 
 
 # ------------------------------------------------------------ size edges ----
@@ -156,18 +95,13 @@ def test_size_edges(C, ws, ft, mode):
 
 # ------------------------------------------------------------ arithmetic ----
 
-_PATTERN_ARCH = {}
-
-
 @pytest.mark.parametrize("ft,mode", [(1, 1), (2, 1), (1, 2), (2, 2)],
                          ids=["fp16-acc1", "bf16-acc1", "fp16-acc2", "bf16-acc2"])
 def test_every_16_bit_pattern(C, ws, ft, mode):
     """Every 16-bit pattern as x against each of the 16 fixed accumulator
     values and one random vector: 17 x 65,536 words."""
     xw, acc = A.arithmetic16(ft, mode)
-    if ft not in _PATTERN_ARCH:
-        _PATTERN_ARCH[ft] = O.float_compress(xw, ft, 10)
-    m = M(_PATTERN_ARCH[ft], xw)
+    m = M(_ARCH.get(("patterns", ft), lambda: O.float_compress(xw, ft, 10)), xw)
     archives, accs, buf, init, starts = place(ft, mode, [m], acc_init=lambda total: torch.cat(
         [A.random_acc(ft, mode, CANARY, seed=5), acc, A.random_acc(ft, mode, total - CANARY - acc.numel(), seed=6)]))
     assert starts == [CANARY]
@@ -267,9 +201,7 @@ def test_401_member_batch(C, ws):
 @pytest.mark.parametrize("ft,mode", [(2, 1), (2, 2), (3, 1)], ids=["bf16-acc1", "bf16-acc2", "fp32"])
 def test_gpu_compressed_archive(C, ws, ft, mode):
     w = A.member_words(ft, 70001, seed=21)
-    x = torch.from_numpy(w.view(A.NP_SIGNED[ft]).copy()).to(DEV)
-    out, sizes = C.float_compress_pointer([x], ft=ft, ws=ws)
-    arch = out[0, : int(sizes[0])].cpu().numpy()
+    arch = compress_one(C, ws, w, ft).cpu().numpy()
     run("codec", C, ws, ft, mode, [M(arch, w)])
 
 

@@ -19,57 +19,25 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import (BLOCK, LARGE_FAMILIES, NP_WORD, STD_BLOCKS, STD_RARE_C1, bytes_from_histogram,
-                        exp_bytes, hard_histograms, rate_extreme_bytes, small_extreme_bytes, std_extreme_bytes,
-                        std_mirror_bytes, words_from_symbols)
+from tests.gpu_harness import C, DEV, N, Cache, to_dev, workspace_fixture  # noqa: F401
+from tests.util import (BLOCK, FT_IDS, LARGE_FAMILIES, NP_W, NP_WORD, STD_BLOCKS, STD_RARE_C1, TORCH_FLOAT, TORCH_WORD,
+                        WORD_BYTES, bytes_from_histogram, exp_bytes, hard_histograms, rate_extreme_bytes,
+                        small_extreme_bytes, std_extreme_bytes, std_mirror_bytes, words_from_symbols)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 PBS = [9, 10, 11]
-NP_SIGNED = {0: np.uint8, 1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-NP_W = {0: np.uint8, **NP_WORD}
-TORCH_WORD = {0: torch.uint8, 1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-TORCH_FLOAT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
-WORD_BYTES = {0: 1, 1: 2, 2: 2, 3: 4, 4: 8}
-FT_IDS = {0: "bytes", 1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
 CANARY = 16
 FILL = 0xA5
 N_STD = STD_BLOCKS * BLOCK + 1000
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def N(C):
-    from dietgpu_fork_amd import _native
-
-    return _native
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(512 << 20)
-
-
+ws = workspace_fixture(512 << 20)
 # inputs and oracle archives: computed once, shared, left unchanged
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
+_CACHE = Cache()
 
 
 def byte_members():
-    return cached("bytes", lambda: [std_extreme_bytes(), small_extreme_bytes(), std_mirror_bytes(),
+    return _CACHE.get("bytes", lambda: [std_extreme_bytes(), small_extreme_bytes(), std_mirror_bytes(),
                                     exp_bytes(33, lam=10.0, seed=3)])
 
 
@@ -79,7 +47,7 @@ def float_members(ft):
         c1s = rate_extreme_bytes(5, [3], 0) if ft == 4 else None
         return [words_from_symbols(ft, std_extreme_bytes(), c1, seed=ft),
                 words_from_symbols(ft, small_extreme_bytes(), c1s, seed=10 + ft)]
-    return cached(("words", ft), make)
+    return _CACHE.get(("words", ft), make)
 
 
 def ref_archives(ft, key, words, pb, checksum=False):
@@ -88,15 +56,7 @@ def ref_archives(ft, key, words, pb, checksum=False):
         if ft == 0:
             return [O.ans_encode(w, pb, checksum) for w in words]
         return [O.float_compress(w, ft, pb, checksum) for w in words]
-    return cached(("ref", ft, key, pb, checksum), make)
-
-
-def to_dev(w, ft, offset=0):
-    """A device copy of the words; offset: words past a 16 B boundary."""
-    t = torch.empty(w.size + offset, dtype=TORCH_WORD[ft], device=DEV)
-    assert t.data_ptr() % 16 == 0
-    t[offset:].copy_(torch.from_numpy(w.view(NP_SIGNED[ft])))
-    return t[offset:]
+    return _CACHE.get(("ref", ft, key, pb, checksum), make)
 
 
 def encode_bytes(C, N, ws, ts, pb, checksum, hist=None):
@@ -282,7 +242,7 @@ def sparse_words(ft):
         # (the last two words stay zero: no n - 2 quirk of the reference)
         w[np.sort(rng.choice(n - 2, nz.size, replace=False))] = nz
         return w
-    return cached(("sparse", ft), make)
+    return _CACHE.get(("sparse", ft), make)
 
 
 @pytest.mark.parametrize("pb", PBS)
@@ -290,7 +250,7 @@ def sparse_words(ft):
 def test_rate_extreme_sparse(C, ws, ft, pb):
     w = sparse_words(ft)
     assert int((w != 0).sum()) == N_STD
-    ref = cached(("sparse-ref", ft, pb), lambda: O.sparse_compress(w, ft, pb))
+    ref = _CACHE.get(("sparse-ref", ft, pb), lambda: O.sparse_compress(w, ft, pb))
     t = to_dev(w, ft)
     out, sizes = C.sparse_compress([t], ft=ft, prob_bits=pb, ws=ws)
     sizes_h = check_archives(C, out, sizes, [ref])
@@ -309,7 +269,7 @@ def family_bytes():
         fams = hard_histograms(0)
         names = [n for n in fams if n not in LARGE_FAMILIES]
         return names, [bytes_from_histogram(fams[n], seed=40 + i) for i, n in enumerate(names)]
-    return cached("families", make)
+    return _CACHE.get("families", make)
 
 
 def pdf_section(names):
@@ -356,8 +316,8 @@ def test_hard_histograms_sparse(C, ws, pb):
     a batch of several elements would go through the dense codec's k_hist
     and prologue instead."""
     names, datas = family_bytes()
-    words = cached("family-words", lambda: [(d.astype(np.uint16) << 8) | np.uint16(1) for d in datas])
-    refs = cached(("family-sparse-ref", pb), lambda: [O.sparse_compress(w, 1, pb) for w in words])
+    words = _CACHE.get("family-words", lambda: [(d.astype(np.uint16) << 8) | np.uint16(1) for d in datas])
+    refs = _CACHE.get(("family-sparse-ref", pb), lambda: [O.sparse_compress(w, 1, pb) for w in words])
     for name, w, ref in zip(names, words, refs):
         # sparse header, bitmap, float header, raw low bytes, ANS header
         at = 16 + -(-((w.size + 7) // 8) // 16) * 16 + 32 + -(-w.size // 16) * 16 + 32
@@ -387,7 +347,7 @@ def test_hard_histograms_large_totals(C, N, ws, pb, route):
     def make():
         fams = hard_histograms(0)
         return [bytes_from_histogram(fams[n], seed=60 + i) for i, n in enumerate(LARGE_FAMILIES)]
-    datas = cached("large", make)
+    datas = _CACHE.get("large", make)
     checksum = route == "checksum"
     refs = ref_archives(0, "large", datas, pb, checksum)
     ts = [to_dev(d, 0) for d in datas]

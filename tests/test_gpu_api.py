@@ -15,35 +15,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD, exp_bytes, float_words, sparsify
+from tests.gpu_harness import C, DEV, N, workspace_fixture  # noqa: F401
+from tests.util import NP_SIGNED, NP_WORD, TORCH_FLOAT, TORCH_WORD, WORD_BYTES, exp_bytes, float_words, sparsify
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-TORCH_WORD = {1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-TORCH_FLOAT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
-WORD_BYTES = {1: 2, 2: 2, 3: 4, 4: 8}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def N(C):
-    from dietgpu_fork_amd import _native
-
-    return _native
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(512 << 20)
+ws = workspace_fixture(512 << 20)
 
 
 def _s():

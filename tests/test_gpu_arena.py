@@ -12,11 +12,11 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import DEV
 from tests.util import float_words
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 SENTINEL = 0xAB
 
 

@@ -13,26 +13,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import exp_bytes, float_words, sparsify
+from tests.gpu_harness import C, DEV, workspace_fixture  # noqa: F401
+from tests.util import NP_SIGNED, TORCH_WORD, exp_bytes, float_words, sparsify
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-WORD_DTYPE = {0: torch.uint8, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-NP_SIGNED = {0: np.uint8, 2: np.int16, 3: np.int32, 4: np.int64}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(256 << 20)
+ws = workspace_fixture(256 << 20)
 
 
 @pytest.fixture
@@ -88,7 +75,7 @@ def test_drivers_launch_what_the_plan_names(C, ws, profiled, name, ft, nb, n, ch
         refs = [O.float_compress(w, ft, 10, checksum) for w in contents]
     host = np.stack([contents[i % len(contents)] for i in range(nb)])
     # rows a multiple of 16 bytes apart: the single-pass compressor takes nothing else
-    rows = torch.zeros([nb, (n + 15) // 16 * 16], dtype=WORD_DTYPE[ft], device=DEV)
+    rows = torch.zeros([nb, (n + 15) // 16 * 16], dtype=TORCH_WORD[ft], device=DEV)
     x = rows[:, :n]
     x.copy_(torch.from_numpy(host.view(NP_SIGNED[ft])))
     hist = None

@@ -10,18 +10,9 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import C, DEV  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
 
 
 def test_c3_full(C):

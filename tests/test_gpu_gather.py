@@ -11,81 +11,32 @@ import torch
 
 from oracle import oracle as O
 from tests import gather_cases as G
-from tests.util import NP_WORD, exp_bytes, float_words
+from tests.gpu_harness import (C, DEV, N, Cache, compress_one, make_words, to_dev,  # noqa: F401
+                               workspace_fixture)
+from tests.util import FT_IDS, NP_W, TORCH_OUT, TORCH_WORD, WORD_BYTES, float_words
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NP_W = {0: np.uint8, **NP_WORD}  # ft 0 = the byte codec
-NP_SIGNED = {0: np.uint8, 1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-INT_T = {0: torch.uint8, 1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-OUT_T = {0: torch.uint8, 1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
-WORD_BYTES = {0: 1, 1: 2, 2: 2, 3: 4, 4: 8}
-FT_IDS = {0: "bytes", 1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
-FTS = [0, 1, 2, 3, 4]
+FTS = [0, 1, 2, 3, 4]  # ft 0 = the byte codec
 CANARY = 16  # words on each side of the destination
 FILL = 0xA5  # byte pattern of canaries, gaps and untouched rows
 IDX_T = {32: torch.int32, 64: torch.int64}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def N(C):
-    from dietgpu_fork_amd import _native
-
-    return _native
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(64 << 20)
-
-
-def make_words(ft, n, kind="normal", seed=0):
-    if kind == "normal":
-        return exp_bytes(n, lam=20.0, seed=seed + 1) if ft == 0 else float_words(ft, n, seed=seed)
-    # uniformly random bit patterns: incompressible, blocks of > 512 compressed words
-    rng = np.random.default_rng(seed + 77)
-    return rng.integers(0, 256, n * WORD_BYTES[ft], dtype=np.uint8).view(NP_W[ft])
-
-
-def to_dev(words, ft):
-    return torch.from_numpy(words.view(NP_SIGNED[ft]).copy()).to(DEV)
-
-
-def compress(C, ws, t, ft, pb=10, checksum=False):
-    """One archive (a 16 B-aligned uint8 CUDA tensor) from the GPU compressor."""
-    if ft == 0:
-        out, sizes = C.ans_encode_pointer([t], prob_bits=pb, checksum=checksum, ws=ws)
-    else:
-        out, sizes = C.float_compress_pointer([t], ft=ft, prob_bits=pb, checksum=checksum, ws=ws)
-    a = out[0, : int(sizes[0])]
-    assert a.data_ptr() % 16 == 0
-    return a
-
-
-_TABLES = {}
+ws = workspace_fixture(64 << 20)
+_TABLES = Cache()
 
 
 def table(C, ws, ft, kind="normal", pb=10, checksum=False, n=G.N_TABLE):
     """(words on the device as integers, archive, the archive 4 bytes off 16 B
     alignment), computed once per key and left unchanged."""
-    key = (ft, kind, pb, checksum, n)
-    if key not in _TABLES:
+    def make():
         t = to_dev(make_words(ft, n, kind, seed=ft + 3), ft)
-        a = compress(C, ws, t, ft, pb, checksum)
+        a = compress_one(C, ws, t, ft, pb, checksum)
         shifted = torch.empty([a.numel() + 16], dtype=torch.uint8, device=DEV)
         assert shifted.data_ptr() % 16 == 0
         shifted[4: 4 + a.numel()] = a
-        _TABLES[key] = (t, a, shifted[4: 4 + a.numel()])
-    return _TABLES[key]
+        return t, a, shifted[4: 4 + a.numel()]
+    return _TABLES.get((ft, kind, pb, checksum, n), make)
 
 
 def idx_tensor(idx, bits):
@@ -108,9 +59,9 @@ class Dest:
         self.stride = rw + pad
         self.start = -(-CANARY // per16) * per16 + off
         total = self.start + m * self.stride + CANARY + per16
-        self.buf = torch.full([total * wb], FILL, dtype=torch.uint8, device=DEV).view(INT_T[ft])
+        self.buf = torch.full([total * wb], FILL, dtype=torch.uint8, device=DEV).view(TORCH_WORD[ft])
         assert self.buf.data_ptr() % 16 == 0
-        self.out = self.view(self.buf, m, rw).view(OUT_T[ft])
+        self.out = self.view(self.buf, m, rw).view(TORCH_OUT[ft])
         assert m == 0 or (self.out.data_ptr() % 16 == 0) == (off % per16 == 0)
         self.want = self.buf.clone()
         self.ok = expect_ok(idx, rw, n) if ok is None else ok
@@ -135,7 +86,7 @@ class Dest:
 
 def gather(C, ws, ft, arch, rw, idx_t, dest, pb=10, **kw):
     status = torch.full([idx_t.numel()], 7, dtype=torch.uint8, device=DEV)
-    out, ok = C.gather_rows_device(arch, rw, idx_t, OUT_T[ft], out=dest.out, out_status=status, prob_bits=pb, ws=ws,
+    out, ok = C.gather_rows_device(arch, rw, idx_t, TORCH_OUT[ft], out=dest.out, out_status=status, prob_bits=pb, ws=ws,
                                    **kw)
     assert out is dest.out and ok is status
     return status
@@ -312,7 +263,7 @@ def test_no_indices(C, N, ws, ft):
     for bits in (32, 64):
         dest = Dest(ft, words, 64, [])
         it = torch.empty([0], dtype=IDX_T[bits], device=DEV)
-        out, ok = C.gather_rows_device(a16, 64, it, OUT_T[ft], ws=ws)
+        out, ok = C.gather_rows_device(a16, 64, it, TORCH_OUT[ft], ws=ws)
         assert tuple(out.shape) == (0, 64) and tuple(ok.shape) == (0,)
         c_abi(N, ws, ft, a16, 64, it, dest, None)
         dest.check(None, "no indices")
@@ -358,7 +309,7 @@ def test_graph_capture_replay(C):
     def load(seed):
         """New table, new archive bytes in abuf, new indices (two of them bad)."""
         w = to_dev(float_words(2, n, seed=seed, scale=1 + seed % 3), 2)
-        a = compress(C, ws, w, 2)
+        a = compress_one(C, ws, w, 2)
         abuf.zero_()
         abuf[: a.numel()] = a
         rows = torch.from_numpy(np.random.default_rng(seed).integers(0, R, m))
@@ -406,7 +357,7 @@ def test_torch_operator(C, ws, as_float):
         dest.check(status, "operator")
     # the guards that need device tensors, each with its own message
     i64 = idx_tensor([0, 1], 64)
-    o = torch.empty([2, rw], dtype=OUT_T[ft], device=DEV)
+    o = torch.empty([2, rw], dtype=TORCH_OUT[ft], device=DEV)
     with pytest.raises(RuntimeError, match="compressed inputs must be 4-byte aligned"):
         shifted = torch.empty([a16.numel() + 16], dtype=torch.uint8, device=DEV)
         op(as_float, shifted[1: 1 + a16.numel()], rw, i64, o)
@@ -493,8 +444,8 @@ def test_equals_the_host_index_gather(C, ws, ft):
     words, a16, _ = table(C, ws, ft)
     for rw in (8, 1024, 4097):
         idx = G.index_lists(rw)["random"][0][:128] + G.index_lists(rw)["edges"][0]
-        host = C.gather_rows(a16, rw, idx, OUT_T[ft], ws=ws)
-        dev, ok = C.gather_rows_device(a16, rw, idx_tensor(idx, 64), OUT_T[ft], ws=ws)
+        host = C.gather_rows(a16, rw, idx, TORCH_OUT[ft], ws=ws)
+        dev, ok = C.gather_rows_device(a16, rw, idx_tensor(idx, 64), TORCH_OUT[ft], ws=ws)
         torch.cuda.synchronize()
         assert bool(ok.all())
-        assert torch.equal(host.view(INT_T[ft]), dev.view(INT_T[ft]))
+        assert torch.equal(host.view(TORCH_WORD[ft]), dev.view(TORCH_WORD[ft]))

@@ -12,14 +12,12 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD
+from tests.gpu_harness import C, DEV, to_dev, workspace_fixture  # noqa: F401
+from tests.util import NP_WORD, TORCH_FLOAT
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden.npz")
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-FLOAT_DT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
 
 
 @pytest.fixture(scope="module")
@@ -28,21 +26,7 @@ def G():
         return {k: z[k] for k in z.files}
 
 
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(1 << 30)
-
-
-def dev_words(w, ft):
-    return torch.from_numpy(w.view(NP_SIGNED[ft]).copy()).to(DEV).view(FLOAT_DT[ft])
+ws = workspace_fixture(1 << 30)
 
 
 # --- golden fixtures ----------------------------------------------------------
@@ -65,7 +49,7 @@ def test_golden_c1_gpu(C, ws, G, pb, ck):
 @pytest.mark.parametrize("ft", [1, 2, 3, 4])
 def test_golden_float_gpu(C, ws, G, ft):
     ns = (1, 13, 4095, 4096, 4097, 12345)
-    xs = [dev_words(G[f"f{ft}_n{n}_in"], ft) for n in ns]
+    xs = [to_dev(G[f"f{ft}_n{n}_in"], ft, as_float=True) for n in ns]
     out, sizes = C.float_compress_pointer(xs, ft=ft, prob_bits=10, ws=ws)
     for i, n in enumerate(ns):
         ref = G[f"f{ft}_n{n}_pb10"]
@@ -81,7 +65,7 @@ def test_golden_float_gpu(C, ws, G, ft):
 
 @pytest.mark.parametrize("pb", [9, 11])
 def test_golden_float_pb_checksum_gpu(C, ws, G, pb):
-    x = dev_words(G["f2_pbx_in"], 2)
+    x = to_dev(G["f2_pbx_in"], 2, as_float=True)
     out, sizes = C.float_compress_pointer([x], ft=2, prob_bits=pb, checksum=True, ws=ws)
     ref = G[f"f2_pb{pb}_ck1"]
     np.testing.assert_array_equal(out[0, : int(sizes[0])].cpu().numpy(), ref)
@@ -90,7 +74,7 @@ def test_golden_float_pb_checksum_gpu(C, ws, G, pb):
 @pytest.mark.parametrize("ft", [2, 3])
 @pytest.mark.parametrize("tag", ["z", "nz"])
 def test_golden_sparse_gpu(C, ws, G, ft, tag):
-    x = dev_words(G[f"s{ft}_{tag}_in"], ft)
+    x = to_dev(G[f"s{ft}_{tag}_in"], ft, as_float=True)
     out, sizes = C.sparse_compress([x], ft=ft, prob_bits=10, ws=ws)
     ref = G[f"s{ft}_{tag}_pb10"]
     np.testing.assert_array_equal(out[0, : int(sizes[0])].cpu().numpy(), ref)
@@ -166,10 +150,10 @@ def test_throughput_shape_other_floats(C, ws, ft, nb, n):
     decode workgroups with several chunks each): bit-exact round trip and
     byte identity with the oracle on a sampled element."""
     g = torch.Generator(device=DEV).manual_seed(20 + ft)
-    x = torch.randn(nb, n, generator=g, device=DEV, dtype=torch.float64).to(FLOAT_DT[ft])
+    x = torch.randn(nb, n, generator=g, device=DEV, dtype=torch.float64).to(TORCH_FLOAT[ft])
     out, sizes = C.float_compress_stride(x, prob_bits=10, ws=ws)
     s = sizes.cpu().numpy().astype(np.int64)
-    y, ok, sz = C.float_decompress_stride(out, n, FLOAT_DT[ft], ws=ws)
+    y, ok, sz = C.float_decompress_stride(out, n, TORCH_FLOAT[ft], ws=ws)
     assert bool((ok == 1).all()) and bool((sz == n).all())
     assert torch.equal(y.view(torch.uint8), x.view(torch.uint8))
     i = nb // 3

@@ -29,25 +29,15 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import C, DEV, workspace_fixture  # noqa: F401
 from tests.util import exp_bytes
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "golden.npz")
 
 
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(256 << 20)
+ws = workspace_fixture(256 << 20)
 
 
 @pytest.fixture(scope="module")

@@ -5,34 +5,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD, exp_bytes, float_words, sparsify
+from tests.gpu_harness import C, DEV, to_dev, to_host_words, workspace_fixture  # noqa: F401
+from tests.util import NP_SIGNED, NP_WORD, TORCH_FLOAT, TORCH_WORD, exp_bytes, float_words, sparsify
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-TORCH_WORD = {1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(512 << 20)
-
-
-def to_dev_words(w, ft):
-    return torch.from_numpy(w.view(NP_SIGNED[ft]).copy()).to(DEV)
-
-
-def to_np_words(t, ft):
-    return t.cpu().numpy().view(NP_WORD[ft])
+ws = workspace_fixture(512 << 20)
 
 
 ANS_SIZES = [0, 1, 31, 32, 33, 4095, 4096, 4097, 12345, 65536, 100003]
@@ -125,7 +104,7 @@ FLOAT_SIZES = [0, 1, 2, 13, 4095, 4096, 4097, 12345, 65536, 100001]
 @pytest.mark.parametrize("pb", [9, 10, 11])
 def test_float_pointer_parity(C, ws, ft, pb):
     words = [float_words(ft, n, seed=10 + i) for i, n in enumerate(FLOAT_SIZES)]
-    ts = [to_dev_words(w, ft) for w in words]
+    ts = [to_dev(w, ft) for w in words]
     out, sizes = C.float_compress_pointer(ts, ft=ft, prob_bits=pb, ws=ws)
     sizes_h = sizes.cpu().tolist()
     host = out.cpu().numpy()
@@ -139,7 +118,7 @@ def test_float_pointer_parity(C, ws, ft, pb):
     assert ok.cpu().tolist() == [1] * len(ts)
     assert sz.cpu().tolist() == [w.size for w in words]
     for w, o in zip(words, outs):
-        np.testing.assert_array_equal(to_np_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)
 
 
 # Sizes at the edges of the kernels' index arithmetic: the decoder's 256-word
@@ -163,7 +142,7 @@ def test_segment_and_workgroup_edges(C, ws, ft, path):
         refs = [O.ans_encode(w, pb, False) for w in words]
     else:
         words = [float_words(ft, n, seed=50 + i) for i, n in enumerate(EDGE_SIZES)]
-        ts = [to_dev_words(w, ft) for w in words]
+        ts = [to_dev(w, ft) for w in words]
         refs = [O.float_compress(w, ft, pb) for w in words]
     with C.compress_path(path):
         if ft == 0:
@@ -192,13 +171,12 @@ def test_segment_and_workgroup_edges(C, ws, ft, path):
         assert ok.cpu().tolist() == [1] * len(ts)
         assert sz.cpu().tolist() == [300] * len(ts)
         for w, t in zip(words, tails):
-            np.testing.assert_array_equal(to_np_words(t.view(torch.int16), ft), w[-300:])
+            np.testing.assert_array_equal(to_host_words(t.view(torch.int16), ft), w[-300:])
 
 
 # 1, 2 and 3 blocks (both parities of the block-words pad entry); n mod 16 =
 # 1, 9, 7, so every plane of every float type's raw section has a rounding tail.
 HEADER_SIZES = [1, 4096 + 9, 2 * 4096 + 7]
-FLOAT_DTYPE = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
 
 
 @pytest.mark.parametrize("checksum", [False, True])
@@ -230,7 +208,7 @@ def test_headers_and_tails_into_dirty_buffers(C, ws, ft, path, checksum):
                 cols = C.max_compressed_size(n)
             else:
                 w = float_words(ft, n, seed=70 + i)
-                t = one_row(to_dev_words(w, ft))
+                t = one_row(to_dev(w, ft))
                 ref = O.float_compress(w, ft, pb, checksum)
                 cols = C.max_float_compressed_size(ft, n)
             out = torch.full([1, cols], 0xA5, dtype=torch.uint8, device=DEV)
@@ -251,7 +229,7 @@ def test_headers_and_tails_into_dirty_buffers(C, ws, ft, path, checksum):
             if ft == 0:
                 dec, ok, sz = C.ans_decode_stride(out, n, prob_bits=pb, checksum=checksum, ws=ws)
             else:
-                dec, ok, sz = C.float_decompress_stride(out, n, FLOAT_DTYPE[ft], prob_bits=pb, checksum=checksum,
+                dec, ok, sz = C.float_decompress_stride(out, n, TORCH_FLOAT[ft], prob_bits=pb, checksum=checksum,
                                                         ws=ws)
             assert ok.cpu().tolist() == [1] and sz.cpu().tolist() == [n]
             np.testing.assert_array_equal(dec[0].view(t.dtype).cpu().numpy().view(w.dtype), w)
@@ -262,7 +240,7 @@ def test_headers_and_tails_into_dirty_buffers(C, ws, ft, path, checksum):
 @pytest.mark.parametrize("ft", [1, 2, 3, 4])
 def test_float_checksum(C, ws, ft):
     words = [float_words(ft, n, seed=20 + i) for i, n in enumerate([1, 5000, 70000])]
-    ts = [to_dev_words(w, ft) for w in words]
+    ts = [to_dev(w, ft) for w in words]
     out, sizes = C.float_compress_pointer(ts, ft=ft, checksum=True, ws=ws)
     host = out.cpu().numpy()
     for i, w in enumerate(words):
@@ -285,7 +263,7 @@ def test_float_unaligned_pointers(C, ws, ft):
     # inputs / outputs that are only word aligned (split-size style offsets)
     n = 9999
     w = float_words(ft, n + 3, seed=33)
-    big = to_dev_words(w, ft)
+    big = to_dev(w, ft)
     ts = [big[1:n + 1], big[3:]]
     out, sizes = C.float_compress_pointer(ts, ft=ft, ws=ws)
     host = out.cpu().numpy()
@@ -295,8 +273,8 @@ def test_float_unaligned_pointers(C, ws, ft):
     outs = [dst[1:n + 1], dst[n + 3: 2 * n + 3]]
     arch = [out[0, : int(sizes[0])], out[1, : int(sizes[1])]]
     C.float_decompress_pointer(arch, outs, ft=ft, ws=ws)
-    np.testing.assert_array_equal(to_np_words(outs[0], ft), w[1:n + 1])
-    np.testing.assert_array_equal(to_np_words(outs[1], ft), w[3:])
+    np.testing.assert_array_equal(to_host_words(outs[0], ft), w[1:n + 1])
+    np.testing.assert_array_equal(to_host_words(outs[1], ft), w[3:])
 
 
 @pytest.mark.parametrize("ft", [2, 3])
@@ -326,7 +304,7 @@ def test_sparse_parity(C, ws, ft):
     words[5][-2] = 7
     words[6][-2] = 0
     words[6][-1] = 0
-    ts = [to_dev_words(w, ft) for w in words]
+    ts = [to_dev(w, ft) for w in words]
     out, sizes = C.sparse_compress(ts, ft=ft, ws=ws)
     host = out.cpu().numpy()
     sizes_h = sizes.cpu().tolist()
@@ -340,13 +318,13 @@ def test_sparse_parity(C, ws, ft):
     assert ok.cpu().tolist() == [1] * len(ts)
     assert sz.cpu().tolist() == [w.size for w in words]
     for w, o in zip(words, outs):
-        np.testing.assert_array_equal(to_np_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)
 
 
 def test_sparse_all_zero_and_dense(C, ws):
     ft = 3
     ws_ = [np.zeros(1000, np.uint32), float_words(3, 3000, seed=9), np.zeros(2, np.uint32)]
-    ts = [to_dev_words(w, ft) for w in ws_]
+    ts = [to_dev(w, ft) for w in ws_]
     out, sizes = C.sparse_compress(ts, ft=ft, ws=ws)
     host = out.cpu().numpy()
     for i, w in enumerate(ws_):
@@ -355,7 +333,7 @@ def test_sparse_all_zero_and_dense(C, ws):
     outs = [torch.empty(w.size, dtype=torch.int32, device=DEV) for w in ws_]
     C.sparse_decompress(arch, outs, ft=ft, ws=ws)
     for w, o in zip(ws_, outs):
-        np.testing.assert_array_equal(to_np_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)
 
 
 @pytest.mark.parametrize("ft", [2, 3])
@@ -366,7 +344,7 @@ def test_sparse_large_lists(C, ws, ft):
     n = 3 << 20
     fracs = [0.9, 0.0, 0.5, 1.0, 0.999]
     words = [sparsify(float_words(ft, n, seed=70 + i), f, seed=80 + i) for i, f in enumerate(fracs)]
-    ts = [to_dev_words(w, ft) for w in words]
+    ts = [to_dev(w, ft) for w in words]
     out, sizes = C.sparse_compress(ts, ft=ft, ws=ws)
     host = out.cpu().numpy()
     sizes_h = sizes.cpu().tolist()
@@ -381,7 +359,7 @@ def test_sparse_large_lists(C, ws, ft):
     ok, sz = C.sparse_decompress(arch, outs, ft=ft, ws=ws)
     assert ok.cpu().tolist() == [1] * len(ts)
     for w, o in zip(words, outs):
-        np.testing.assert_array_equal(to_np_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)
 
 
 def test_sparse_many_tiles(C, ws):
@@ -392,7 +370,7 @@ def test_sparse_many_tiles(C, ws):
     ft = 2
     sizes = [4100 * 4096 + 123, 777]
     words = [sparsify(float_words(ft, n, seed=90 + i), 0.9, seed=95 + i) for i, n in enumerate(sizes)]
-    ts = [to_dev_words(w, ft) for w in words]
+    ts = [to_dev(w, ft) for w in words]
     out, osz = C.sparse_compress(ts, ft=ft, ws=ws)
     host = out.cpu().numpy()
     osz_h = osz.cpu().tolist()
@@ -407,4 +385,4 @@ def test_sparse_many_tiles(C, ws):
     assert ok.cpu().tolist() == [1, 1]
     assert sz.cpu().tolist() == sizes
     for w, o in zip(words, outs):
-        np.testing.assert_array_equal(to_np_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)

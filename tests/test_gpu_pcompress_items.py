@@ -24,14 +24,12 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import exp_bytes, float_words
+from tests.gpu_harness import C, DEV, Cache, single_pass_fixture, workspace_fixture  # noqa: F401
+from tests.util import NP_W, exp_bytes, float_words
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 PB = 10
-NP_W = {0: np.uint8, 1: np.uint16, 2: np.uint16, 3: np.uint32}
-TORCH_W = {0: torch.uint8, 1: torch.int16, 2: torch.int16, 3: torch.int32}
 BUDGET_TICKS = 500_000  # 5 ms: a co-tenant cannot trip the no-fallback assertion
 
 # teams of 5 items (32768 words each): 5 items whose last holds 2 blocks,
@@ -44,27 +42,20 @@ EDGE_SIZES = (0, 1, 7, 4095, 4096, 4097, 32768)
 POOL = 1 << 18
 
 
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
+_single_pass = single_pass_fixture()
 
 
 @pytest.fixture(autouse=True)
-def _single_pass(C):
+def _barrier_budget(C, _single_pass):
+    """On the single-pass path, with a team-barrier budget of BUDGET_TICKS."""
     C.set_barrier_budget(BUDGET_TICKS)
     try:
-        with C.compress_path("single-pass"):
-            yield
+        yield
     finally:
         C.set_barrier_budget(20000)
 
 
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(768 << 20)
+ws = workspace_fixture(768 << 20)
 
 
 @pytest.fixture(scope="module")
@@ -73,14 +64,12 @@ def slots():
     return 4 * torch.cuda.get_device_properties(0).multi_processor_count
 
 
-_pools = {}
-_refs = {}
+_pools, _refs = Cache(), Cache()
 
 
 def _pool(ft):
-    if ft not in _pools:
-        _pools[ft] = exp_bytes(POOL, lam=20.0, seed=41) if ft == 0 else float_words(ft, POOL, seed=40 + ft)
-    return _pools[ft]
+    return _pools.get(ft, lambda: (exp_bytes(POOL, lam=20.0, seed=41) if ft == 0
+                                   else float_words(ft, POOL, seed=40 + ft)))
 
 
 def _elem(ft, k, n):
@@ -91,11 +80,10 @@ def _elem(ft, k, n):
 
 
 def _ref(ft, ck, off, n):
-    key = (ft, ck, off, n)
-    if key not in _refs:
+    def make():
         w = _pool(ft)[off: off + n]
-        _refs[key] = O.ans_encode(w, PB, ck) if ft == 0 else O.float_compress(w, ft, PB, ck)
-    return _refs[key]
+        return O.ans_encode(w, PB, ck) if ft == 0 else O.float_compress(w, ft, PB, ck)
+    return _refs.get((ft, ck, off, n), make)
 
 
 class Batch:

@@ -12,34 +12,16 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import C, DEV, single_pass_fixture, workspace_fixture  # noqa: F401
 from tests.util import exp_bytes, float_words
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 MIB = 1 << 20
 
 
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(autouse=True)
-def _single_pass(C):
-    """Small batches take the three-kernel path by default (the size rule,
-    codec.hip persistentPreferred): this module's batches are meant for the
-    single-pass compressor whenever it can take them."""
-    with C.compress_path("single-pass"):
-        yield
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(512 << 20)
+ws = workspace_fixture(512 << 20)
+_single_pass = single_pass_fixture()
 
 
 def _float_inputs(ft, sizes, seed0=0):

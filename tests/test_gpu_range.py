@@ -10,17 +10,11 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD, exp_bytes, float_words
+from tests.gpu_harness import C, DEV, N, Cache, compress_one, make_words, retyped, workspace_fixture  # noqa: F401
+from tests.util import FT_IDS, NP_W, TORCH_FLOAT, WORD_BYTES, float_words
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-# ft 0 = the byte codec
-NP_W = {0: np.uint8, **NP_WORD}
-NP_SIGNED = {0: np.uint8, 1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-TORCH_FLOAT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
-WORD_BYTES = {0: 1, 1: 2, 2: 2, 3: 4, 4: 8}
-FT_IDS = {0: "bytes", 1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
 CANARY = 16  # words on each side of every destination
 FILL = 0xA5  # byte pattern of canaries and untouched destinations
 
@@ -42,58 +36,16 @@ def big_ranges(n):
     ]
 
 
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def N(C):
-    from dietgpu_fork_amd import _native
-
-    return _native
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(64 << 20)
-
-
-def make_words(ft, n, kind="normal", seed=0):
-    if kind == "normal":
-        return exp_bytes(n, lam=20.0, seed=seed + 1) if ft == 0 else float_words(ft, n, seed=seed)
-    # uniformly random bit patterns: incompressible, blocks of > 512 compressed words
-    rng = np.random.default_rng(seed + 77)
-    return rng.integers(0, 256, n * WORD_BYTES[ft], dtype=np.uint8).view(NP_W[ft])
-
-
-def to_dev(words, ft):
-    return torch.from_numpy(words.view(NP_SIGNED[ft]).copy()).to(DEV)
-
-
-def compress(C, ws, words, ft, pb=10, checksum=False):
-    """One archive (a 16 B-aligned uint8 CUDA tensor) from the GPU compressor."""
-    t = to_dev(words, ft)
-    if ft == 0:
-        out, sizes = C.ans_encode_pointer([t], prob_bits=pb, checksum=checksum, ws=ws)
-    else:
-        out, sizes = C.float_compress_pointer([t], ft=ft, prob_bits=pb, checksum=checksum, ws=ws)
-    return out[0, : int(sizes[0])]
-
-
-_ARCHIVES = {}
+ws = workspace_fixture(64 << 20)
+_ARCHIVES = Cache()
 
 
 def archive(C, ws, ft, n=N_BIG, kind="normal", pb=10):
     """(words, archive), computed once per key and left unchanged."""
-    key = (ft, n, kind, pb)
-    if key not in _ARCHIVES:
+    def make():
         w = make_words(ft, n, kind, seed=ft + 10 * n % 1000)
-        _ARCHIVES[key] = (w, compress(C, ws, w, ft, pb))
-    return _ARCHIVES[key]
+        return w, compress_one(C, ws, w, ft, pb)
+    return _ARCHIVES.get((ft, n, kind, pb), make)
 
 
 def decode_range(C, ws, ft, archives, firsts, counts, outs, pb=10):
@@ -169,15 +121,6 @@ def test_prob_bits(C, ws, ft, pb):
                 pb=pb)
 
 
-def retyped(a, ft):
-    """A copy of float archive `a` whose header names another float type (the
-    type is the low nibble of header word 2); the layout stays that of `a`,
-    so the decoder's header reads stay inside it."""
-    p = a.clone()
-    p[8] = (int(a[8]) & 0xF0) | {1: 2, 2: 1, 3: 4, 4: 3}[ft]
-    return p
-
-
 @pytest.mark.parametrize("ft", [0, 1, 2, 3, 4], ids=FT_IDS.get)
 def test_failing_members(C, ws, ft):
     """Ranges past the element's end, an archive of another type and one of
@@ -221,7 +164,7 @@ def test_archive_from_the_cpu_oracle(C, ws, ft):
 
 def test_archive_with_a_checksum_decodes(C, ws):
     w = make_words(2, N_BIG, seed=5)
-    a = compress(C, ws, w, 2, checksum=True)
+    a = compress_one(C, ws, w, 2, checksum=True)
     run_members(C, ws, 2, [(a, w, f, c, 0, True) for f, c in big_ranges(N_BIG)])
 
 

@@ -18,46 +18,27 @@ from oracle import oracle as O
 from tests import accumulate_cases as A
 from tests import reduce_cases as R
 from tests.dist_cases import pg  # noqa: F401
+from tests.gpu_harness import C, DEV, Cache, pack_bytes, place_words, workspace_fixture  # noqa: F401
+from tests.util import FT_OF
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-GUARD = 16
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
-
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(64 << 20)
-
-
-_ARCH = {}
+ws = workspace_fixture(64 << 20)
+_ARCH = Cache()
 
 
 def archive_of(x, ft, pb=10, checksum=False, key=None):
     """The oracle's archive of float CPU tensor x (cached under `key`)."""
-    if key is not None and (key, pb, checksum) in _ARCH:
-        return _ARCH[(key, pb, checksum)]
-    a = O.float_compress(A.float_to_words(x, ft), ft, pb, checksum)
-    if key is not None:
-        _ARCH[(key, pb, checksum)] = a
-    return a
+    def make():
+        return O.float_compress(A.float_to_words(x, ft), ft, pb, checksum)
+    return make() if key is None else _ARCH.get((key, pb, checksum), make)
 
 
 def source(ft, n, seed, pb=10, checksum=False):
     """(values, archive) of one random source (cached)."""
     key = ("src", ft, n, seed)
-    if key not in _ARCH:
-        _ARCH[key] = A.random_acc(ft, 1, n, seed=seed)
-    return _ARCH[key], archive_of(_ARCH[key], ft, pb, checksum, key=key)
+    x = _ARCH.get(key, lambda: A.random_acc(ft, 1, n, seed=seed))
+    return x, archive_of(x, ft, pb, checksum, key=key)
 
 
 class M:
@@ -74,37 +55,14 @@ class M:
         self.size = (n if ok else 0) if size is None else size
 
 
-def pack_bytes(blobs, offs):
-    """Byte blobs in one uint8 device buffer, each 16 B-aligned plus its offset."""
-    at, cur = [], 0
-    for b, o in zip(blobs, offs):
-        at.append(cur + o)
-        cur = -(-(cur + o + b.size) // 16) * 16
-    host = np.zeros(cur + 16, dtype=np.uint8)
-    for b, a in zip(blobs, at):
-        host[a:a + b.size] = b
-    dev = torch.from_numpy(host).to(DEV)
-    assert dev.data_ptr() % 16 == 0
-    return [dev[a:a + b.size] for b, a in zip(blobs, at)]
-
-
-def place_words(dtype, caps, offs, seed):
-    """-> (views, buffer, CPU copy, starts): one buffer of random finite
-    values, member i's cap[i] words offs[i] words past a 16 B boundary, GUARD
-    words apart at least."""
-    per16 = 16 // dtype.itemsize
-    starts, cur = [], 0
-    for cap, off in zip(caps, offs):
-        st = -(-(cur + GUARD) // per16) * per16 + off
-        starts.append(st)
-        cur = st + cap + GUARD
-    total = cur + per16
-    g = torch.Generator().manual_seed(2000 + seed)
-    init = (torch.randn(total, generator=g, dtype=torch.float64)
-            * torch.exp2(torch.randint(-12, 12, (total,), generator=g).double())).to(dtype)
-    buf = init.to(DEV)
-    assert buf.data_ptr() % 16 == 0
-    return [buf[st:st + cap] for st, cap in zip(starts, caps)], buf, init, starts
+def random_init(dtype, seed):
+    """The `init` of place_words: random finite values over a wide exponent
+    range."""
+    def init(total):
+        g = torch.Generator().manual_seed(2000 + seed)
+        return (torch.randn(total, generator=g, dtype=torch.float64)
+                * torch.exp2(torch.randint(-12, 12, (total,), generator=g).double())).to(dtype)
+    return init
 
 
 def run(api, C, ws, ft, members, init_form, out_form, pb=10, with_status=True, temp_mem=True, seed=0, in_place=False):
@@ -115,14 +73,15 @@ def run(api, C, ws, ft, members, init_form, out_form, pb=10, with_status=True, t
     views = pack_bytes([a for k in range(K) for m in members for a in [m.archs[k]]],
                        [m.arch_offs[k] for k in range(K) for m in members])
     sources = [views[k * nb:(k + 1) * nb] for k in range(K)]
-    outs, obuf, ohost, ostarts = place_words(out_dt, [m.cap for m in members], [m.out_off for m in members], seed)
+    outs, obuf, ohost, ostarts = place_words(out_dt, [m.cap for m in members], [m.out_off for m in members],
+                                             random_init(out_dt, seed))
     inits = ibuf = ihost = istarts = None
     if in_place:
         assert init_dt == out_dt
         inits, ibuf, ihost, istarts = outs, obuf, ohost, ostarts
     elif init_dt is not None:
         inits, ibuf, ihost, istarts = place_words(init_dt, [m.cap for m in members], [m.init_off for m in members],
-                                                  seed + 1)
+                                                  random_init(init_dt, seed + 1))
     ok = torch.full([nb], 7, dtype=torch.uint8, device=DEV) if with_status else None
     sz = torch.full([nb], -7, dtype=torch.int32, device=DEV) if with_status else None
     if api == "codec":

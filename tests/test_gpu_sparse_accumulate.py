@@ -20,135 +20,68 @@ from oracle import oracle as O
 from tests import pyref
 from tests import sparse_accumulate_cases as S
 from tests.dist_cases import pg  # noqa: F401
-from tests.util import SPARSE_LARGE_B, sparse_far_element, sparsify
+from tests.gpu_harness import (C, DEV, Cache, Member, accumulate_call, check_placed, dense_at,  # noqa: F401
+                               expected_placed, place_members, retyped, workspace_fixture)
+from tests.util import FT_OF, SPARSE_LARGE_B, float_words, sparse_far_element, sparsify
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-GUARD = 16
-FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 GARBAGE = {1: 0xDEAD, 2: 0xBEEF, 3: 0xDEADBEEF, 4: 0xFFFFFFFFFFFFFFFF}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(512 << 20)
-
-
-_ARCH = {}
+ws = workspace_fixture(512 << 20)
+_ARCH = Cache()
+NAMES = {"codec": "sparse_decompress_accumulate", "capi": "dietgpu_float_decompress_sparse_accumulate"}
 
 
 def oracle_archive(ft, name, w, pb=10, checksum=False):
     """The CPU oracle's sparse archive, computed once per key and left unchanged."""
-    key = (ft, name, pb, checksum)
-    if key not in _ARCH:
-        _ARCH[key] = O.sparse_compress(w, ft, pb, checksum)
-    return _ARCH[key]
+    return _ARCH.get((ft, name, pb, checksum), lambda: O.sparse_compress(w, ft, pb, checksum))
 
 
 def random_words(ft, n, frac_zero, seed):
-    from tests.util import float_words
-
     return sparsify(float_words(ft, n, seed=seed), frac_zero, seed=seed + 1)
 
 
-class M:
-    """One member of a call: archive bytes, the words it encodes, the
-    accumulator's capacity and offset from a 16 B boundary, whether it must
-    succeed, and (acc) values to put into its accumulator instead of the
-    buffer's random ones."""
+def M(arch, x, cap=None, acc_off=0, ok=True, acc=None):
+    """One member of a call: archive bytes (always 16 B-aligned), the words it
+    encodes, the accumulator's capacity and offset from a 16 B boundary,
+    whether it must succeed, and (acc) values to put into its accumulator
+    instead of the buffer's random ones.  The sparse size comes from the
+    sparse header: n for every member, failing or not."""
+    return Member(arch, x, cap, acc_off, ok=ok, size=x.size, acc=acc)
 
-    def __init__(self, arch, x, cap=None, acc_off=0, ok=True, acc=None):
-        self.arch, self.x, self.ok, self.acc = arch, x, ok, acc
-        self.cap = x.size if cap is None else cap
-        self.acc_off = acc_off
-        self.size = x.size  # the sparse size comes from the sparse header: n for every member
+
+def model_of(ft, mode):
+    """(apply, touched, compare) of expected_placed() / check_placed(): the
+    model adds the nonzero words only, and S.check also holds every other
+    word to the initial buffer's very bits."""
+    return lambda acc, w: S.expected(acc, w, ft, mode), S.touched, S.check
 
 
 def place(ft, mode, members, seed=0):
     """-> (archives, accs, buf, init, starts): every archive 16 B-aligned in
     one uint8 buffer, every accumulator acc_off words past a 16 B boundary
-    inside one buffer `buf` (`init` is its CPU copy), GUARD words apart."""
-    dt = S.acc_dtype(ft, mode)
-    per16 = 16 // dt.itemsize
-    starts, cur = [], 0
-    for m in members:
-        st = -(-(cur + GUARD) // per16) * per16 + m.acc_off
-        starts.append(st)
-        cur = st + m.cap + GUARD
-    total = cur + per16
-    init = S.case_acc(ft, mode, total, seed=seed)
-    for m, st in zip(members, starts):
-        if m.acc is not None:
-            init[st:st + m.acc.numel()] = m.acc
-    buf = init.to(DEV)
-    assert buf.data_ptr() % 16 == 0
-    offs, cur = [], 0
-    for m in members:
-        offs.append(cur)
-        cur = -(-(cur + m.arch.size) // 16) * 16
-    host = np.zeros(cur + 16, dtype=np.uint8)
-    for m, o in zip(members, offs):
-        host[o:o + m.arch.size] = m.arch
-    ab = torch.from_numpy(host).to(DEV)
-    assert ab.data_ptr() % 16 == 0
-    archives = [ab[o:o + m.arch.size] for m, o in zip(members, offs)]
-    accs = [buf[st:st + m.cap] for m, st in zip(members, starts)]
-    return archives, accs, buf, init, starts
+    inside one buffer `buf` (`init` is its CPU copy), 16 guard words apart."""
+    return place_members(members, S.acc_dtype(ft, mode), lambda total: S.case_acc(ft, mode, total, seed=seed))
 
 
 def expected(ft, mode, members, init, starts):
     """-> (want, touch): the buffer after the call and the words it may write."""
-    want = init.clone()
-    touch = torch.zeros(init.numel(), dtype=torch.bool)
-    for m, st in zip(members, starts):
-        if m.ok:
-            n = m.x.size
-            want[st:st + n] = S.expected(want[st:st + n], m.x, ft, mode)
-            touch[st:st + n] = S.touched(m.x)
-    return want, touch
+    return expected_placed(members, init, starts, *model_of(ft, mode)[:2])
 
 
 def call(api, C, ws, ft, mode, archives, accs, buf, starts, pb=10, with_status=True):
-    """-> (ok, sz) CPU lists, or None without status arrays."""
-    nb = len(archives)
-    if api == "codec":
-        ok, sz = C.sparse_decompress_accumulate(archives, accs, ft=ft, prob_bits=pb, ws=ws)
-    else:
-        from dietgpu_fork_amd import _native as N
-
-        # every accumulator's address inside `buf`, also for a capacity of 0
-        # (an empty view has a null data pointer)
-        ok = torch.full([nb], 7, dtype=torch.uint8, device=DEV) if with_status else None
-        sz = torch.full([nb], -7, dtype=torch.int32, device=DEV) if with_status else None
-        rc = N.lib().dietgpu_float_decompress_sparse_accumulate(
-            ws.h, ft, pb, nb, N.ptr_array([a.data_ptr() for a in archives]),
-            N.ptr_array([buf.data_ptr() + st * buf.element_size() for st in starts]),
-            N.u32_array([a.numel() for a in accs]), 3 if mode == 2 else ft,
-            ok.data_ptr() if with_status else None, sz.data_ptr() if with_status else None,
-            torch.cuda.current_stream().cuda_stream)
-        assert rc == 0, N.lib().dietgpu_last_error()
-    torch.cuda.synchronize()
-    return (ok.cpu().tolist(), sz.cpu().tolist()) if with_status else None
+    """-> (ok, sz) CPU lists, or None without status arrays.  The C ABI gets
+    every accumulator's address inside `buf`, also for a capacity of 0 (an
+    empty view has a null data pointer)."""
+    return accumulate_call(api, NAMES, C, ws, ft, mode, archives, accs,
+                           [buf.data_ptr() + st * buf.element_size() for st in starts], pb, with_status)
 
 
 def run(api, C, ws, ft, mode, members, pb=10, with_status=True, seed=0):
     archives, accs, buf, init, starts = place(ft, mode, members, seed=seed)
     st = call(api, C, ws, ft, mode, archives, accs, buf, starts, pb, with_status)
-    if st is not None:
-        assert st[0] == [int(m.ok) for m in members]
-        assert st[1] == [m.size for m in members]
-    want, touch = expected(ft, mode, members, init, starts)
-    problem = S.check(buf.cpu(), want, init, touch)
-    assert problem is None, problem
+    check_placed(members, st, buf.cpu(), init, starts, *model_of(ft, mode))
 
 
 # ------------------------------------------------------------ size edges ----
@@ -229,19 +162,12 @@ def test_reference_legal_archives(C, ws, ft, mode):
 
 # ------------------------------------------------------ failure contract ----
 
-def dense_at(n):
-    """Where the dense archive starts inside a sparse archive of n words."""
-    return 16 + pyref.round_up((n + 7) // 8, 16)
-
-
 def failure_members(ft):
     els = {name: w for _, name, w in S.edge_elements(ft)}
     a, b, c, d, e = (els[k] for k in ("n4097_dense_t01", "n1025_dense_t01", "n200_dense_t10", "n8193_zero_t01",
                                       "n2049_zero_t01"))
     arch = {id(w): oracle_archive(ft, f"fail{k}", w) for k, w in enumerate((a, b, c, d, e))}
-    retyped = arch[id(d)].copy()  # the dense header names another float type
-    at = dense_at(d.size) + 8
-    retyped[at] = (int(retyped[at]) & 0xF0) | {1: 2, 2: 1, 3: 4, 4: 3}[ft]
+    other = retyped(arch[id(d)], ft, at=dense_at(d.size) + 8)  # the dense header names another float type
     pb9 = oracle_archive(ft, "fail_pb9", b, pb=9)
     magic = arch[id(a)].copy()
     magic[dense_at(a.size)] ^= 0x40  # the dense magic word
@@ -249,7 +175,7 @@ def failure_members(ft):
         M(arch[id(a)], a),
         M(arch[id(b)], b, cap=b.size - 1, ok=False),    # accumulator one word short
         M(arch[id(c)], c, acc_off=1),
-        M(retyped, d, ok=False),                        # dense part of another float type
+        M(other, d, ok=False),                          # dense part of another float type
         M(arch[id(e)], e, cap=e.size + 3),              # room to spare: only [0, n) may change
         M(pb9, b, acc_off=1, ok=False),                 # dense part with other prob bits
         M(magic, a, ok=False),                          # dense part with a corrupt magic

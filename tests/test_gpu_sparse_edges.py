@@ -18,50 +18,29 @@ import torch
 
 from oracle import oracle as O
 from tests import pyref
-from tests.util import (FT_NAME, NP_WORD, SPARSE_BLOCK_EDGE, SPARSE_LARGE_B, sparse_edge_elements,
-                        sparse_far_element, sparse_special_words)
+from tests.gpu_harness import C, DEV, Cache, dense_at, retyped, workspace_fixture  # noqa: F401
+from tests.util import (FT_NAME, NP_SIGNED, NP_WORD, SPARSE_BLOCK_EDGE, SPARSE_LARGE_B, TORCH_WORD, WORD_BYTES,
+                        sparse_edge_elements, sparse_far_element, sparse_special_words)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-TORCH_WORD = {1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-WORD_BYTES = {1: 2, 2: 2, 3: 4, 4: 8}
 FTS = [1, 2, 3, 4]
 CANARY = 16  # words on each side of every destination
 FILL = 0xA5  # byte pattern of canaries and untouched destinations
 GARBAGE = {1: 0xDEAD, 2: 0xBEEF, 3: 0xDEADBEEF, 4: 0xFFFFFFFFFFFFFFFF}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(1 << 30)
-
-
-_ELEMENTS, _ORACLE = {}, {}
+ws = workspace_fixture(1 << 30)
+_ELEMENTS, _ORACLE = Cache(), Cache()
 
 
 def elements(ft):
     """{name: (group, words)} of sparse_edge_elements(ft), generated once."""
-    if ft not in _ELEMENTS:
-        _ELEMENTS[ft] = {name: (group, w) for group, name, w in sparse_edge_elements(ft)}
-    return _ELEMENTS[ft]
+    return _ELEMENTS.get(ft, lambda: {name: (group, w) for group, name, w in sparse_edge_elements(ft)})
 
 
 def oracle_archive(ft, name, w, pb=10, checksum=False):
     """The CPU oracle's archive, computed once per key and left unchanged."""
-    key = (ft, name, pb, checksum)
-    if key not in _ORACLE:
-        _ORACLE[key] = O.sparse_compress(w, ft, pb, checksum)
-    return _ORACLE[key]
+    return _ORACLE.get((ft, name, pb, checksum), lambda: O.sparse_compress(w, ft, pb, checksum))
 
 
 def place(words, ft, off):
@@ -248,7 +227,7 @@ def test_reference_legal_archives(C, ws, ft):
         if n % 8:
             variants.append(pyref.sparse_compress(ft, w, 10, gap_fill=GARBAGE[ft] - 1, pad_fill=0xFF,
                                                   pad_bits=True))
-        prefix = 16 + pyref.round_up((n + 7) // 8, 16)
+        prefix = dense_at(n)
         for v in variants[1:]:
             assert not np.array_equal(v[prefix:], plain[prefix:])
         if len(variants) == 3:  # the last bitmap byte itself differs
@@ -260,16 +239,6 @@ def test_reference_legal_archives(C, ws, ft):
             members.append((torch.from_numpy(v.copy()).to(DEV), w, n, k % 2, True))
     assert len(members) >= 30
     decode_members(C, ws, ft, members)
-
-
-def retyped_sparse(a, n, ft):
-    """A copy of sparse archive `a` whose dense header names another float
-    type (the low nibble of its word 2); the layout stays that of `a`, so every
-    header read stays inside the archive."""
-    p = a.clone()
-    at = 16 + pyref.round_up((n + 7) // 8, 16) + 8
-    p[at] = (int(a[at]) & 0xF0) | {1: 2, 2: 1, 3: 4, 4: 3}[ft]
-    return p
 
 
 @pytest.mark.parametrize("ft", FTS, ids=FT_NAME.get)
@@ -289,10 +258,10 @@ def test_failure_contract(C, ws, ft):
         (arch[b], ws_[b], ws_[b].size - 1, 0, False),        # capacity n-1
         (arch[c], ws_[c], ws_[c].size, 1, True),
         (arch[a], ws_[a], 0, 0, False),                      # capacity 0
-        (retyped_sparse(arch[d], ws_[d].size, ft), ws_[d], ws_[d].size, 0, False),
+        (retyped(arch[d], ft, at=dense_at(ws_[d].size) + 8), ws_[d], ws_[d].size, 0, False),
         (arch[e], ws_[e], ws_[e].size + 3, 0, True),         # room to spare
         (with_pb9, ws_[b], ws_[b].size, 1, False),           # compressed at pb 9
-        (retyped_sparse(arch[b], ws_[b].size, ft), ws_[b], ws_[b].size, 0, False),
+        (retyped(arch[b], ft, at=dense_at(ws_[b].size) + 8), ws_[b], ws_[b].size, 0, False),
         (arch[b], ws_[b], ws_[b].size, 0, True),
     ]
     decode_members(C, ws, ft, members)
@@ -314,7 +283,7 @@ def test_checksum_mismatch_is_reported(C, ws, ft):
     arch = roundtrip(C, ws, ft, named, 0, 0, checksum=True)
     n = named[1][1].size
     bad = arch[1].clone()
-    bad[16 + pyref.round_up((n + 7) // 8, 16) + 40] ^= 0xFF
+    bad[dense_at(n) + 40] ^= 0xFF
     outs = [torch.empty(w.size, dtype=TORCH_WORD[ft], device=DEV) for _, w in named]
     with pytest.raises(ChecksumMismatch):
         C.sparse_decompress([arch[0], bad], outs, ft=ft, prob_bits=10, checksum=True, ws=ws)

@@ -13,26 +13,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.util import NP_WORD
+from tests.gpu_harness import C, DEV, workspace_fixture  # noqa: F401
+from tests.util import NP_WORD, TORCH_FLOAT, TORCH_WORD
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-TORCH_WORD = {1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-DTYPE = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(2 << 30)
+ws = workspace_fixture(2 << 30)
 
 
 def _sparse_batch(ft, nb, n, frac_zero, seed):
@@ -47,7 +34,7 @@ def _sparse_batch(ft, nb, n, frac_zero, seed):
             x = (torch.randn(n, generator=g, device=DEV).view(torch.int32) >> 16).to(torch.int16)
             x = x.view(torch.bfloat16)
         else:
-            x = torch.randn(n, generator=g, device=DEV).to(DTYPE[ft])
+            x = torch.randn(n, generator=g, device=DEV).to(TORCH_FLOAT[ft])
         x = x.view(TORCH_WORD[ft])
         x[torch.rand(n, generator=g, device=DEV) < frac_zero] = 0
         out.append(x)

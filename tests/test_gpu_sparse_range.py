@@ -16,47 +16,28 @@ import torch
 from oracle import oracle as O
 from tests import pyref
 from tests import sparse_range_cases as K
-from tests.util import FT_NAME, NP_WORD, sparse_edge_elements, sparse_far_element
+from tests.gpu_harness import C, DEV, Cache, dense_at, retyped, workspace_fixture  # noqa: F401
+from tests.util import (FT_NAME, NP_SIGNED, NP_WORD, TORCH_WORD, WORD_BYTES, sparse_edge_elements,
+                        sparse_far_element)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NP_SIGNED = {1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-TORCH_WORD = {1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-WORD_BYTES = {1: 2, 2: 2, 3: 4, 4: 8}
 FTS = [1, 2, 3, 4]
 CANARY = 16  # words on each side of every destination
 FILL = 0xA5  # byte pattern of canaries and untouched destinations
 
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(1 << 30)
-
-
-_ELEMENTS, _ARCHIVES = {}, {}
+ws = workspace_fixture(1 << 30)
+_ELEMENTS, _ARCHIVES = Cache(), Cache()
 
 
 def elements(ft):
-    if ft not in _ELEMENTS:
-        _ELEMENTS[ft] = {name: w for _, name, w in sparse_edge_elements(ft)}
-    return _ELEMENTS[ft]
+    return _ELEMENTS.get(ft, lambda: {name: w for _, name, w in sparse_edge_elements(ft)})
 
 
 def oracle_archive(ft, key, w, pb=10, checksum=False):
     """The CPU oracle's archive on the device, made once per key."""
-    k = (ft, key, pb, checksum)
-    if k not in _ARCHIVES:
-        _ARCHIVES[k] = torch.from_numpy(O.sparse_compress(w, ft, pb, checksum)).to(DEV)
-    return _ARCHIVES[k]
+    return _ARCHIVES.get((ft, key, pb, checksum),
+                         lambda: torch.from_numpy(O.sparse_compress(w, ft, pb, checksum)).to(DEV))
 
 
 def run_members(C, ws, ft, members, pb=10):
@@ -238,15 +219,6 @@ def test_parameters(C, ws):
     torch.cuda.synchronize()
 
 
-def retyped_sparse(a, n, ft):
-    """A copy of sparse archive `a` whose dense header names another float
-    type; the layout stays that of `a`."""
-    p = a.clone()
-    at = 16 + pyref.round_up((n + 7) // 8, 16) + 8
-    p[at] = (int(a[at]) & 0xF0) | {1: 2, 2: 1, 3: 4, 4: 3}[ft]
-    return p
-
-
 @pytest.mark.parametrize("ft", FTS, ids=FT_NAME.get)
 def test_failures_in_a_mixed_batch(C, ws, ft):
     """Each failing member: status 0, size 0, destination untouched; the good
@@ -276,7 +248,7 @@ def test_failures_in_a_mixed_batch(C, ws, ft):
         (a, w, 0xFFFFFFFF, 2, False),       # first + count wraps
         (a, w, 5, 0xFFFFFFFE, False),       # a count no archive can hold: sizes no scratch row
         (za, z, 0, n, True),
-        (retyped_sparse(a, n, ft), w, 0, n, False),   # the wrong float type
+        (retyped(a, ft, at=dense_at(n) + 8), w, 0, n, False),   # the wrong float type
         (pb9, w, 5, 50, False),             # the wrong prob bits
         (a, w, 4095, 2, True),
         (dense, w, 0, 100, False),          # a dense float archive

@@ -9,27 +9,11 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import C, DEV, single_pass_fixture  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(autouse=True)
-def _single_pass(C):
-    """Small batches take the three-kernel path by default (the size rule,
-    codec.hip persistentPreferred): this module's batches are meant for the
-    single-pass compressor whenever it can take them."""
-    with C.compress_path("single-pass"):
-        yield
+_single_pass = single_pass_fixture()
 
 
 def _bf16(n, seed):

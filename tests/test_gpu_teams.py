@@ -16,19 +16,10 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.gpu_harness import C, DEV, single_pass_fixture, workspace_fixture  # noqa: F401
 from tests.util import exp_bytes, float_words
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def C():
-    import dietgpu_fork_amd  # noqa: F401
-    from dietgpu_fork_amd import codec
-
-    return codec
 
 
 # Team-barrier budget while the no-fallback tests run: 5 ms instead of the
@@ -38,22 +29,20 @@ def C():
 BUDGET_TICKS = 500_000
 
 
+_single_pass = single_pass_fixture()
+
+
 @pytest.fixture(autouse=True)
-def _single_pass(C):
-    """Small batches take the three-kernel path by default (the size rule,
-    codec.hip persistentPreferred): this module's batches are meant for the
-    single-pass compressor whenever it can take them."""
+def _barrier_budget(C, _single_pass):
+    """On the single-pass path, with a team-barrier budget of BUDGET_TICKS."""
     C.set_barrier_budget(BUDGET_TICKS)
     try:
-        with C.compress_path("single-pass"):
-            yield
+        yield
     finally:
         C.set_barrier_budget(20000)
 
 
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(768 << 20)
+ws = workspace_fixture(768 << 20)
 
 
 def _bf16_batch(nb, n, seed0):

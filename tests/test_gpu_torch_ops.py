@@ -16,6 +16,7 @@ views, empty members, a side stream); (g) the size operators; (h) the
 rejections, the argument guards among them.  tests/test_torch_ops_args.py
 holds the rejections that fire without a device."""
 import types
+from functools import partial
 
 import numpy as np
 import pytest
@@ -23,37 +24,21 @@ import torch
 
 import dietgpu_fork_amd  # noqa: F401  (registers torch.ops.dietgpu)
 from oracle import oracle as O
+from tests.gpu_harness import (C, DEV, Cache, compress_one, retyped, to_dev, to_host_words,  # noqa: F401
+                               workspace_fixture)
 from tests.test_gpu_adversarial import byte_members, float_members, ref_archives
-from tests.test_gpu_range import retyped
-from tests.util import NP_WORD, exp_bytes, float_words
+from tests.util import FT_IDS, NP_SIGNED, TORCH_OUT, WORD_BYTES, exp_bytes, float_words
 
 pytestmark = pytest.mark.gpu
 
 D = torch.ops.dietgpu
-DEV = "cuda"
-# ft 0 = the byte codec
-NP_W = {0: np.uint8, **NP_WORD}
-NP_SIGNED = {0: np.uint8, 1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
-TORCH_WORD = {0: torch.uint8, 1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
-TORCH_DT = {0: torch.uint8, 1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
-WORD_BYTES = {0: 1, 1: 2, 2: 2, 3: 4, 4: 8}
-FT_IDS = {0: "bytes", 1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
-ALL_FT = [0, 1, 2, 3, 4]
+ALL_FT = [0, 1, 2, 3, 4]  # ft 0 = the byte codec
 FILL = 0xA5
 PAD = 128  # canary bytes on each side of a carved region: 16 words of the widest type
 I32 = torch.int32
 
-
-@pytest.fixture(scope="module")
-def C():
-    from dietgpu_fork_amd import codec
-
-    return codec
-
-
-@pytest.fixture(scope="module")
-def ws(C):
-    return C.Workspace(64 << 20)
+ws = workspace_fixture(64 << 20)
+dev = partial(to_dev, as_float=True)  # a device tensor of the codec's dtype holding the words
 
 
 @pytest.fixture(scope="module")
@@ -64,13 +49,7 @@ def tmp():
 # ---------------------------------------------------------------------------
 # inputs and oracle archives: computed once, shared, left unchanged
 # ---------------------------------------------------------------------------
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
+_CACHE = Cache()
 
 
 def elem(ft, n, seed=0):
@@ -78,29 +57,15 @@ def elem(ft, n, seed=0):
     def make():
         s = 1000 * seed + 10 * (n % 97) + ft
         return exp_bytes(n, lam=20.0, seed=s + 1) if ft == 0 else float_words(ft, n, seed=s)
-    return cached(("elem", ft, n, seed), make)
+    return _CACHE.get(("elem", ft, n, seed), make)
 
 
 def oracle(ft, words, checksum=False):
     """The oracle's archive of `words` (as bytes when ft == 0)."""
     key = ("oracle", ft, words.dtype.str, words.size, hash(words.tobytes()), checksum)
     if ft == 0:
-        return cached(key, lambda: O.ans_encode(words.view(np.uint8), 10, checksum))
-    return cached(key, lambda: O.float_compress(words, ft, 10, checksum))
-
-
-def dev(words, ft, off=0):
-    """A device tensor of the codec's dtype holding `words`, starting `off`
-    words after a 16 B boundary."""
-    room = torch.empty(words.size + off, dtype=TORCH_WORD[ft], device=DEV)
-    assert room.data_ptr() % 16 == 0
-    t = room[off:]
-    t.copy_(torch.from_numpy(words.view(NP_SIGNED[ft])))
-    return t.view(TORCH_DT[ft])
-
-
-def host_words(t, ft):
-    return t.reshape(-1).view(TORCH_WORD[ft]).cpu().numpy().view(NP_W[ft])
+        return _CACHE.get(key, lambda: O.ans_encode(words.view(np.uint8), 10, checksum))
+    return _CACHE.get(key, lambda: O.float_compress(words, ft, 10, checksum))
 
 
 class Carved:
@@ -158,7 +123,7 @@ def status_tensors(n):
 
 
 def float_max(ft, n):
-    return D.max_float_compressed_size(torch.empty(0, dtype=TORCH_DT[ft]), n)
+    return D.max_float_compressed_size(torch.empty(0, dtype=TORCH_OUT[ft]), n)
 
 
 # ---------------------------------------------------------------------------
@@ -314,7 +279,7 @@ def test_split_size_operators(tmp, ft, kind):
         off = (1 if kind == "odd" else 0) * wb if ft else (4 if kind == "ragged-last" else 0)
         cv = Carved([(words.size * wb, off)])
         cv.expect_words(0, words)
-        t_out = cv.region(0, torch.int32 if as_int32 else TORCH_DT[ft])
+        t_out = cv.region(0, torch.int32 if as_int32 else TORCH_OUT[ft])
         st, sz = status_tensors(len(splits))
         D.decompress_data_split_size(bool(ft), lst, t_out, sp, checksum, tmp if use_tmp else None, st, sz)
         torch.cuda.synchronize()
@@ -326,18 +291,6 @@ def test_split_size_operators(tmp, ft, kind):
 # ---------------------------------------------------------------------------
 # d. failing members through the full decoder
 # ---------------------------------------------------------------------------
-def int_view(words, ft):
-    return torch.from_numpy(words.view(NP_SIGNED[ft]).copy()).to(DEV)
-
-
-def archive_pb9(C, ws, words, ft):
-    if ft == 0:
-        out, sizes = C.ans_encode_pointer([int_view(words, 0)], prob_bits=9, ws=ws)
-    else:
-        out, sizes = C.float_compress_pointer([int_view(words, ft)], ft=ft, prob_bits=9, ws=ws)
-    return out[0, : int(sizes[0])].clone()
-
-
 def failing_batch(C, ws, ft):
     """[(archive, words, capacity in words, offset in words, status, size)]:
     good members first, last and between the failures."""
@@ -350,7 +303,7 @@ def failing_batch(C, ws, ft):
     w3, a3 = good(4096, 8)
     # (for the byte codec: a float archive, whose magic differs)
     wrong_type = D.compress_data_simple(True, [dev(elem(2, 4096, 9), 2)], False)[0] if ft == 0 else retyped(a3, ft)
-    wrong_pb = archive_pb9(C, ws, w3, ft)
+    wrong_pb = compress_one(C, ws, w3, ft, pb=9, clone=True)
     return [
         (a0, w0, 4097, 0, 1, 4097),
         (a3, None, 4095, 0, 0, 4096),       # one word short: the size is still reported
@@ -372,7 +325,7 @@ def test_failing_members_through_decompress_data(C, ws, tmp, ft, with_status):
     members = failing_batch(C, ws, ft)
     wb = WORD_BYTES[ft]
     cv = Carved([(cap * wb, off * wb) for (_, _, cap, off, _, _) in members])
-    outs = [cv.region(i, TORCH_DT[ft]) for i in range(len(members))]
+    outs = [cv.region(i, TORCH_OUT[ft]) for i in range(len(members))]
     for i, (_, w, cap, off, ok, _) in enumerate(members):
         assert outs[i].data_ptr() % 16 == off * wb % 16
         if ok:
@@ -400,7 +353,7 @@ def test_checksum_mismatch_raises(tmp, ft):
     a, good = D.compress_data_simple(True, [dev(w, ft), dev(w7, ft)], True)
     bad = a.clone()
     bad[40] ^= 0xFF
-    out, out7 = filled(4097, TORCH_DT[ft]), filled(7, TORCH_DT[ft])
+    out, out7 = filled(4097, TORCH_OUT[ft]), filled(7, TORCH_OUT[ft])
     for op, args in ((D.decompress_data, (True, [good, bad], [out7, out], True, tmp)),
                      (D.decompress_data_simple, (True, [good, bad], True)),
                      (D.decompress_data_split_size, (True, [bad], out, isplit(4097), True, tmp))):
@@ -410,8 +363,8 @@ def test_checksum_mismatch_raises(tmp, ft):
     D.decompress_data(True, [good, bad], [out7, out], False, tmp, st, sz)
     torch.cuda.synchronize()
     assert st.cpu().tolist() == [1, 1] and sz.cpu().tolist() == [7, 4097]
-    np.testing.assert_array_equal(host_words(out7, ft), w7)
-    assert int((host_words(out, ft) != w).sum()) == 1
+    np.testing.assert_array_equal(to_host_words(out7, ft), w7)
+    assert int((to_host_words(out, ft) != w).sum()) == 1
 
 
 # ---------------------------------------------------------------------------
@@ -435,8 +388,8 @@ def test_simple_operators(ft, tm):
     torch.cuda.synchronize()
     assert len(dts) == len(words)
     for w, t in zip(words, dts):
-        assert t.dtype == TORCH_DT[ft] and t.dim() == 1 and t.numel() == w.size
-        np.testing.assert_array_equal(host_words(t, ft), w)
+        assert t.dtype == TORCH_OUT[ft] and t.dim() == 1 and t.numel() == w.size
+        np.testing.assert_array_equal(to_host_words(t, ft), w)
 
 
 def test_simple_rejects_archives_of_two_float_types():
@@ -462,7 +415,7 @@ def test_input_forms(tmp, ft):
     x3 = dev(w3, ft).view(5, 3, 823)
     xv = dev(np.concatenate([wv[:1], wv]), ft)[1:]
     assert xv.data_ptr() % 16 == wb and xv.is_contiguous()
-    xe = torch.empty([0], dtype=TORCH_DT[ft], device=DEV)
+    xe = torch.empty([0], dtype=TORCH_OUT[ft], device=DEV)
     ts = [x2, x3, xv, xe, dev(w1, ft)]
     words = [w2, w3, wv, we, w1]
     refs = [oracle(ft, w) for w in words]
@@ -471,7 +424,7 @@ def test_input_forms(tmp, ft):
     check_list(D.compress_data_simple(bool(ft), ts, False), refs)
     # decode into outputs of the same shapes
     cv = Carved([(w.size * wb, (i % 2) * wb) for i, w in enumerate(words)])
-    outs = [cv.region(i, TORCH_DT[ft]).view(t.shape) for i, t in enumerate(ts)]
+    outs = [cv.region(i, TORCH_OUT[ft]).view(t.shape) for i, t in enumerate(ts)]
     for i, w in enumerate(words):
         cv.expect_words(i, w)
     st, sz = status_tensors(len(ts))
@@ -504,7 +457,7 @@ def test_side_stream(tmp, ft):
         ts = []
         for p in pinned:
             raw = p.to(DEV, non_blocking=True)
-            ts.append(((raw ^ key) ^ key).view(TORCH_DT[ft]))
+            ts.append(((raw ^ key) ^ key).view(TORCH_OUT[ft]))
         comp, sizes, _ = D.compress_data(bool(ft), ts, False, tmp)
         rows = [comp[i, : r.size] for i, r in enumerate(refs)]
         outs = [torch.empty_like(t) for t in ts]
@@ -514,7 +467,7 @@ def test_side_stream(tmp, ft):
     check_rows(comp, sizes, refs)
     assert st.cpu().tolist() == [1] * len(ts)
     for w, o in zip(words, outs):
-        np.testing.assert_array_equal(host_words(o, ft), w)
+        np.testing.assert_array_equal(to_host_words(o, ft), w)
 
 
 # ---------------------------------------------------------------------------
@@ -529,7 +482,7 @@ def test_size_operators_equal_the_codec_bounds(C):
         for ft in (1, 2, 3, 4):
             assert float_max(ft, n) == C.max_float_compressed_size(ft, n)
     for ft in ALL_FT:
-        ts = [torch.empty(n, dtype=TORCH_DT[ft], device=DEV) for n in (7, 12345, 4097)]
+        ts = [torch.empty(n, dtype=TORCH_OUT[ft], device=DEV) for n in (7, 12345, 4097)]
         if ft:
             assert tuple(D.max_float_compressed_output_size(ts)) == (3, C.max_float_compressed_size(ft, 12345))
         assert tuple(D.max_any_compressed_output_size(ts)) == (3, C.max_compressed_size(12345 * WORD_BYTES[ft]))
@@ -546,7 +499,7 @@ def test_size_bounds_cover_max_rate_archives():
         words = float_members(ft)
         for w, ref in zip(words, ref_archives(ft, "members", words, 10)):
             assert float_max(ft, w.size) >= ref.size
-            assert D.max_float_compressed_output_size([torch.empty(w.size, dtype=TORCH_DT[ft])])[1] >= ref.size
+            assert D.max_float_compressed_output_size([torch.empty(w.size, dtype=TORCH_OUT[ft])])[1] >= ref.size
 
 
 @pytest.mark.parametrize("size", [-1, 1 << 32, 1 << 40])

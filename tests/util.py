@@ -1,8 +1,23 @@
-"""Shared input generators for the parity tests (seeded, numpy only)."""
+"""Shared type tables and input generators for the parity tests (seeded; the
+generators are numpy only)."""
 import numpy as np
+import torch
 
 NP_WORD = {1: np.uint16, 2: np.uint16, 3: np.uint32, 4: np.uint64}
 FT_NAME = {1: "fp16", 2: "bf16", 3: "fp32", 4: "fp64"}
+
+# The same per float type (ft) tables with ft 0, the byte codec, where a byte
+# entry makes sense.  Words travel to torch as signed integers of their width
+# (torch has no unsigned 16 / 32 / 64-bit arithmetic): NP_SIGNED / TORCH_WORD
+# name that view, NP_W the unsigned one the archives and the oracle use.
+NP_W = {0: np.uint8, **NP_WORD}
+NP_SIGNED = {0: np.uint8, 1: np.int16, 2: np.int16, 3: np.int32, 4: np.int64}
+TORCH_WORD = {0: torch.uint8, 1: torch.int16, 2: torch.int16, 3: torch.int32, 4: torch.int64}
+TORCH_FLOAT = {1: torch.float16, 2: torch.bfloat16, 3: torch.float32, 4: torch.float64}
+TORCH_OUT = {0: torch.uint8, **TORCH_FLOAT}  # what a decode's output holds
+WORD_BYTES = {0: 1, 1: 2, 2: 2, 3: 4, 4: 8}
+FT_IDS = {0: "bytes", **FT_NAME}
+FT_OF = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
 
 def exp_bytes(n, lam=100.0, seed=1):
