@@ -1,25 +1,40 @@
 // Native PyTorch-ROCm operator library: TORCH_LIBRARY(dietgpu), loadable with
 // torch.ops.load_library("dietgpu_fork_amd/_lib/libdietgpu_torch.so").
 //
-// Mirror of the reference's operator surface (dietgpu/DietGpu.cpp:921-978):
-// the same ten operators, schemas, argument meaning, validation (TORCH_CHECK
-// -> RuntimeError) and return values.  Every op runs on the current HIP
-// stream of the inputs' device and calls the C++ codec API of
-// libdietgpu_amd.so (include/dietgpu/*.h); all compute is in its HIP kernels.
+// Every operator runs on the current HIP stream of its inputs' device and
+// calls the C++ codec API of libdietgpu_amd.so (include/dietgpu/*.h); all
+// compute is in its HIP kernels.  "ref": one of the reference's ten operators
+// (dietgpu/DietGpu.cpp:921-978) with its schema, argument meaning, validation
+// (TORCH_CHECK -> RuntimeError) and return values; "ext": not in the reference.
 //
-// Extensions over the reference: fp64 tensors are accepted on decompression
-// too (the reference rejects them at DietGpu.cpp:569-573 / 742-746 although
-// its compressor produces them), and an archive the compressor had to abandon
-// (outSize 0, see dietgpu_device_error_count in include/dietgpu_c.h) raises
-// instead of being returned as an empty tensor.  An eleventh operator,
-// decompress_data_range, is not in the reference at all: it decodes a word
-// range of each archive (floatDecompressRange / ansDecodeBatchRange).  Nor is
-// the twelfth, decompress_data_accumulate: it adds each archive's element to
-// an accumulator tensor in place (floatDecompressAccumulate).  A thirteenth,
-// gather_rows, gathers rows of a table held by one archive, named by an index
-// tensor on the device (floatGatherRows / ansGatherRows).  A fourteenth,
-// reduce_data, decodes several archives per member and sums them in one
-// kernel (floatReduceArchives).
+//   operator                          from  codec entry points (float / byte mode)
+//   max_float_compressed_output_size  ref   getMaxFloatCompressedSize
+//   max_float_compressed_size         ref   getMaxFloatCompressedSize
+//   max_any_compressed_output_size    ref   getMaxCompressedSize
+//   max_any_compressed_size           ref   getMaxCompressedSize
+//   compress_data                     ref   floatCompress / ansEncodeBatchPointer
+//   compress_data_split_size          ref   floatCompressSplitSize / ansEncodeBatchSplitSize
+//   compress_data_simple              ref   compress_data's
+//   decompress_data                   ref   floatDecompress / ansDecodeBatchPointer
+//   decompress_data_split_size        ref   floatDecompressSplitSize / ansDecodeBatchSplitSize
+//   decompress_data_simple            ref   float / ansGetCompressedInfo, then decompress_data's
+//   decompress_data_range             ext   floatDecompressRange / ansDecodeBatchRange
+//   decompress_data_accumulate        ext   floatDecompressAccumulate (*)
+//   gather_rows                       ext   floatGatherRows / ansGatherRows
+//   reduce_data                       ext   floatReduceArchives (*)
+//   (*) after floatGetCompressedInfo on ts_in[0] where only float32 tensors
+//       would name the archives' type (peekArchiveType)
+//
+// An operator builds one CallContext (device guard, stream, arena over
+// temp_mem and the high-water mark it returns), fills its Members columns
+// (archive() / dest(), both on checkDeviceTensor), takes its config from
+// floatConfig / byteConfig and makes its codec call.
+//
+// Other extensions over the reference: fp64 tensors are accepted on
+// decompression too (the reference rejects them at DietGpu.cpp:569-573 /
+// 742-746 although its compressor produces them), and an archive the
+// compressor had to abandon (outSize 0, see dietgpu_device_error_count in
+// include/dietgpu_c.h) raises instead of being returned as an empty tensor.
 //
 // Argument checks the reference lacks (its DietGpu.cpp says "FIXME: total
 // range checking" where they belong); each raises before any temp-memory
@@ -89,7 +104,11 @@ at::ScalarType dtypeOf(uint32_t ft) {
   }
 }
 
-hipStream_t currentStream(int dev) { return c10::hip::getCurrentHIPStream(dev).stream(); }
+// The codec configs of every operator (the only users of kDefaultPrecision).
+FloatCodecConfig floatConfig(FloatType ft, bool checksum) {
+  return FloatCodecConfig(ft, ANSCodecConfig(kDefaultPrecision), false, checksum);
+}
+ANSCodecConfig byteConfig(bool checksum) { return ANSCodecConfig(kDefaultPrecision, checksum); }
 
 // getTotalAndMaxSize, DietGpu.cpp:63-80 (elements)
 std::pair<uint64_t, uint64_t> totalAndMax(const std::vector<at::Tensor>& ts) {
@@ -151,6 +170,11 @@ struct SplitSizes {
   const uint32_t* data() const { return sizes.data(); }
 };
 
+// A contiguous GPU tensor on the operator's device, or `message`.
+void checkDeviceTensor(const at::Tensor& t, int dev, const char* message) {
+  TORCH_CHECK(t.device().type() == at::kCUDA && t.get_device() == dev && t.is_contiguous(), message);
+}
+
 // An archive on the device: contiguous uint8, 4-byte aligned (k_decode reads
 // the headers with scalar loads, which drop the low two address bits: the
 // header of an archive off 4 B alignment would be read from up to three
@@ -161,26 +185,39 @@ struct SplitSizes {
 // header is on the device.)
 constexpr int64_t kArchiveHeaderBytes = 32;
 void checkArchiveTensor(const at::Tensor& t, int dev) {
-  TORCH_CHECK(t.device().type() == at::kCUDA && t.get_device() == dev && t.is_contiguous(),
-              "compressed inputs must be contiguous GPU tensors on one device");
+  checkDeviceTensor(t, dev, "compressed inputs must be contiguous GPU tensors on one device");
   TORCH_CHECK(t.scalar_type() == at::kByte, "compressed inputs must be uint8");
   TORCH_CHECK(t.numel() >= kArchiveHeaderBytes, "compressed inputs must hold at least the ", kArchiveHeaderBytes,
               "-byte archive header");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 4 == 0, "compressed inputs must be 4-byte aligned");
 }
 
-// The arena over the caller's temp_mem tensor (DietGpu.cpp:303-315), or an
-// empty one whose every allocation overflows to hipMalloc.
-StackDeviceMemory makeStack(int dev, const std::optional<at::Tensor>& tempMem) {
-  if (tempMem) {
-    TORCH_CHECK(tempMem->device().type() == at::kCUDA, "temp_mem must be a GPU tensor");
-    TORCH_CHECK(tempMem->is_contiguous(), "temp_mem must be contiguous");
-    TORCH_CHECK(tempMem->get_device() == dev, "temp_mem must be on the input device");
-    const size_t bytes = size_t(tempMem->numel()) * tempMem->element_size();
-    return StackDeviceMemory(dev, bytes ? tempMem->data_ptr() : nullptr, bytes);
+// What every launching operator holds: the guard of its device, the current
+// stream there and the arena over the caller's temp_mem tensor
+// (DietGpu.cpp:303-315), or an empty one whose every allocation overflows to
+// hipMalloc.  The temp_mem checks run where the arena is built: at once, or
+// where an operator that checks other arguments first calls stack().
+struct CallContext {
+  const int dev;
+  c10::hip::HIPGuard guard;
+  const hipStream_t stream;
+  std::optional<StackDeviceMemory> res;
+  explicit CallContext(int d) : dev(d), guard(d), stream(c10::hip::getCurrentHIPStream(d).stream()) {}
+  CallContext(int d, const std::optional<at::Tensor>& tempMem) : CallContext(d) { stack(tempMem); }
+  void stack(const std::optional<at::Tensor>& tempMem) {
+    if (tempMem) {
+      TORCH_CHECK(tempMem->device().type() == at::kCUDA, "temp_mem must be a GPU tensor");
+      TORCH_CHECK(tempMem->is_contiguous(), "temp_mem must be contiguous");
+      TORCH_CHECK(tempMem->get_device() == dev, "temp_mem must be on the input device");
+      const size_t bytes = size_t(tempMem->numel()) * tempMem->element_size();
+      res.emplace(dev, bytes ? tempMem->data_ptr() : nullptr, bytes);
+    } else {
+      res.emplace(dev, nullptr, 0);
+    }
   }
-  return StackDeviceMemory(dev, nullptr, 0);
-}
+  // what the operators return: the arena's high-water mark
+  int64_t used() const { return int64_t(res->getMaxMemoryUsage()); }
+};
 
 // Sizes of archives the compressor could not finish are 0: never hand one out.
 void checkArchiveSizes(const int32_t* sizes, int64_t n) {
@@ -275,23 +312,22 @@ std::vector<at::Tensor> narrowRows(const at::Tensor& matrix, const int32_t* h, i
 }
 
 // compress_data_res, DietGpu.cpp:161-287
-std::tuple<at::Tensor, at::Tensor, int64_t> compressRes(bool asFloat, StackDeviceMemory& res,
-                                                        const std::vector<at::Tensor>& ts, bool checksum,
-                                                        const std::optional<at::Tensor>& outCompressed,
-                                                        const std::optional<at::Tensor>& outSizes) {
-  TORCH_CHECK(!ts.empty(), "the tensor list must not be empty");
-  const int dev = ts.front().get_device();
+std::tuple<at::Tensor, at::Tensor, int64_t> compress_data(bool asFloat, const std::vector<at::Tensor>& ts,
+                                                          bool checksum, const std::optional<at::Tensor>& tempMem,
+                                                          const std::optional<at::Tensor>& outCompressed,
+                                                          const std::optional<at::Tensor>& outSizes) {
+  CallContext cx(inputDevice(ts), tempMem);
   const auto rc = asFloat ? max_float_compressed_output_size(ts) : max_any_compressed_output_size(ts);
   const int64_t cols = std::get<1>(rc);
   for (const auto& t : ts) {
-    checkGpuTensor(t, dev);
+    checkGpuTensor(t, cx.dev);
     if (asFloat) {
       TORCH_CHECK(t.scalar_type() == ts.front().scalar_type(), "float inputs must share a dtype");
       floatTypeOf(t.scalar_type());
     }
   }
   const auto n = int64_t(ts.size());
-  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, ts.front());
+  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, cx.dev, ts.front());
   std::vector<const void*> in(ts.size());
   std::vector<uint32_t> inSize(ts.size());
   std::vector<void*> out(ts.size());
@@ -301,28 +337,15 @@ std::tuple<at::Tensor, at::Tensor, int64_t> compressRes(bool asFloat, StackDevic
     inSize[i] = uint32_t(asFloat ? ts[i].numel() : ts[i].numel() * ts[i].element_size());
     out[i] = base + int64_t(i) * comp.size(1);
   }
-  const hipStream_t s = currentStream(dev);
+  auto* osz = reinterpret_cast<uint32_t*>(sizes.data_ptr<int32_t>());
   if (asFloat) {
-    const FloatCompressConfig cfg(floatTypeOf(ts.front().scalar_type()), ANSCodecConfig(kDefaultPrecision), false,
-                                  checksum);
-    floatCompress(res, cfg, uint32_t(n), in.data(), inSize.data(), out.data(),
-                  reinterpret_cast<uint32_t*>(sizes.data_ptr<int32_t>()), s);
+    floatCompress(*cx.res, floatConfig(floatTypeOf(ts.front().scalar_type()), checksum), uint32_t(n), in.data(),
+                  inSize.data(), out.data(), osz, cx.stream);
   } else {
-    const ANSCodecConfig cfg(kDefaultPrecision, checksum);
-    ansEncodeBatchPointer(res, cfg, uint32_t(n), in.data(), inSize.data(), nullptr, out.data(),
-                          reinterpret_cast<uint32_t*>(sizes.data_ptr<int32_t>()), s);
+    ansEncodeBatchPointer(*cx.res, byteConfig(checksum), uint32_t(n), in.data(), inSize.data(), nullptr, out.data(),
+                          osz, cx.stream);
   }
-  return {comp, sizes, int64_t(res.getMaxMemoryUsage())};
-}
-
-std::tuple<at::Tensor, at::Tensor, int64_t> compress_data(bool asFloat, const std::vector<at::Tensor>& tsIn,
-                                                          bool checksum, const std::optional<at::Tensor>& tempMem,
-                                                          const std::optional<at::Tensor>& outCompressed,
-                                                          const std::optional<at::Tensor>& outSizes) {
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
-  auto res = makeStack(dev, tempMem);
-  return compressRes(asFloat, res, tsIn, checksum, outCompressed, outSizes);
+  return {comp, sizes, cx.used()};
 }
 
 // compressedMatrixToTensors, DietGpu.cpp:84-108
@@ -337,8 +360,7 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
     const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& outCompressed,
     const std::optional<at::Tensor>& outSizes) {
   TORCH_CHECK(tIn.device().type() == at::kCUDA && tIn.is_contiguous(), "t_in must be a contiguous GPU tensor");
-  const int dev = tIn.get_device();
-  c10::hip::HIPGuard guard(dev);
+  CallContext cx(tIn.get_device());
   const FloatType ft = asFloat ? floatTypeOf(tIn.scalar_type()) : FloatType::kUndefined;
   if (!asFloat) {
     TORCH_CHECK(reinterpret_cast<uintptr_t>(tIn.data_ptr()) % 4 == 0,
@@ -357,21 +379,18 @@ std::tuple<std::vector<at::Tensor>, at::Tensor, int64_t> compress_data_split_siz
   checkSplitSum(split.sum, tIn, asFloat, "t_in");
   const uint32_t mx = split.mx;
   const int64_t cols = asFloat ? int64_t(getMaxFloatCompressedSize(ft, mx)) : int64_t(getMaxCompressedSize(mx));
-  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, dev, tIn);
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
+  const auto [comp, sizes] = outputTensors(outCompressed, outSizes, n, cols, cx.dev, tIn);
+  cx.stack(tempMem);
   auto* osz = reinterpret_cast<uint32_t*>(sizes.data_ptr<int32_t>());
   if (asFloat) {
-    const FloatCompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, checksum);
-    floatCompressSplitSize(res, cfg, uint32_t(n), tIn.data_ptr(), split.data(), comp.data_ptr(),
-                           uint32_t(comp.size(1)), osz, s);
+    floatCompressSplitSize(*cx.res, floatConfig(ft, checksum), uint32_t(n), tIn.data_ptr(), split.data(),
+                           comp.data_ptr(), uint32_t(comp.size(1)), osz, cx.stream);
   } else {
-    const ANSCodecConfig cfg(kDefaultPrecision, checksum);
-    ansEncodeBatchSplitSize(res, cfg, uint32_t(n), tIn.data_ptr(), split.data(), nullptr, comp.data_ptr(),
-                            uint32_t(comp.size(1)), osz, s);
+    ansEncodeBatchSplitSize(*cx.res, byteConfig(checksum), uint32_t(n), tIn.data_ptr(), split.data(), nullptr,
+                            comp.data_ptr(), uint32_t(comp.size(1)), osz, cx.stream);
   }
   auto lst = matrixToTensors(n, comp, sizes);
-  return {lst, sizes, int64_t(res.getMaxMemoryUsage())};
+  return {lst, sizes, cx.used()};
 }
 
 // DietGpu.cpp:472-526
@@ -390,10 +409,26 @@ std::vector<at::Tensor> compress_data_simple(bool asFloat, const std::vector<at:
 
 // ----------------------------------------------------------- decompress ----
 
-void checkOutDtype(const at::Tensor& t) {
+// The dtype rule of a list of float tensors: `subject` must be float16,
+// bfloat16, float32 or (with fp64) float64, and `sharers` must share a dtype,
+// the list's first (a lone tensor is its own first).
+struct DtypeRule {
+  bool fp64;
+  const char* subject;
+  const char* sharers;
+};
+constexpr DtypeRule kFloatOutputs{true, "float outputs", "float outputs (ts_out)"};
+
+void checkDtype(const at::Tensor& t, at::ScalarType first, const DtypeRule& r) {
   const auto d = t.scalar_type();
-  TORCH_CHECK(d == at::kHalf || d == at::kBFloat16 || d == at::kFloat || d == at::kDouble,
-              "float outputs must be float16, bfloat16, float32 or float64");
+  TORCH_CHECK(d == at::kHalf || d == at::kBFloat16 || d == at::kFloat || (r.fp64 && d == at::kDouble), r.subject,
+              " must be float16, bfloat16", r.fp64 ? ", float32 or float64" : " or float32");
+  TORCH_CHECK(d == first, r.sharers, " must share a dtype");
+}
+
+at::ScalarType sharedDtype(const std::vector<at::Tensor>& ts, const DtypeRule& r) {
+  for (const auto& t : ts) checkDtype(t, ts.front().scalar_type(), r);
+  return ts.front().scalar_type();
 }
 
 // The device pointers of the optional out_status / out_decompressed_words
@@ -416,42 +451,38 @@ std::pair<uint8_t*, uint32_t*> statusPointers(const std::optional<at::Tensor>& s
           sizes ? reinterpret_cast<uint32_t*>(sizes->data_ptr<int32_t>()) : nullptr};
 }
 
-// The member columns of a decode-side operator: archives tsIn[i] into the
-// destinations tsOut[i] (argument `outName`), whose capacities count words of
-// their dtype when asFloat and bytes otherwise.  perMember(i) follows member
-// i's checks.
-struct DecodeMembers {
+// The member columns of a decode-side operator on device `dev`, filled one
+// checked tensor at a time, so that an operator keeps the order of its
+// members' checks: archive(t) appends a compressed input, dest(t, ...) a
+// destination (`message` if it is no contiguous tensor on the device) with its
+// capacity, which counts words of its dtype when asFloat and bytes otherwise.
+// Under a `rule` the destinations share the first one's dtype: the config's
+// float type is that one and every capacity is counted in words of it.
+struct Members {
+  const int dev;
   std::vector<const void*> in;
   std::vector<void*> out;
   std::vector<uint32_t> cap;
-};
-template <typename F>
-DecodeMembers decodeMembers(const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsOut, bool asFloat,
-                            int dev, const char* outName, F&& perMember) {
-  const size_t n = tsIn.size();
-  DecodeMembers m{std::vector<const void*>(n), std::vector<void*>(n), std::vector<uint32_t>(n)};
-  for (size_t i = 0; i < n; ++i) {
-    const auto& ti = tsIn[i];
-    const auto& to = tsOut[i];
-    checkArchiveTensor(ti, dev);
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(), outName,
-                " must be contiguous GPU tensors on the input device");
-    if (asFloat) {
-      checkOutDtype(to);
-      // the config's float type is the first destination's and every
-      // capacity is counted in words of it
-      TORCH_CHECK(to.scalar_type() == tsOut.front().scalar_type(), "float outputs (", outName,
-                  ") must share a dtype");
-    }
-    const uint64_t c = asFloat ? uint64_t(to.numel()) : uint64_t(to.numel()) * to.element_size();
-    TORCH_CHECK(c <= kU32Max);
-    perMember(i);
-    m.in[i] = ti.data_ptr();
-    m.out[i] = to.data_ptr();
-    m.cap[i] = uint32_t(c);
+  at::ScalarType first = at::ScalarType::Undefined;
+  Members(int d, size_t archives, size_t dests) : dev(d) {
+    in.reserve(archives);
+    out.reserve(dests);
+    cap.reserve(dests);
   }
-  return m;
-}
+  void archive(const at::Tensor& t) {
+    checkArchiveTensor(t, dev);
+    in.push_back(t.data_ptr());
+  }
+  void dest(const at::Tensor& t, bool asFloat, const char* message, const DtypeRule* rule = nullptr) {
+    checkDeviceTensor(t, dev, message);
+    if (out.empty()) first = t.scalar_type();
+    if (rule) checkDtype(t, first, *rule);
+    const uint64_t c = asFloat ? uint64_t(t.numel()) : uint64_t(t.numel()) * t.element_size();
+    TORCH_CHECK(c <= kU32Max);
+    out.push_back(t.data_ptr());
+    cap.push_back(uint32_t(c));
+  }
+};
 
 void raiseOnChecksum(bool asFloat, bool mismatch) {
   if (!mismatch) return;
@@ -459,38 +490,36 @@ void raiseOnChecksum(bool asFloat, bool mismatch) {
   TORCH_CHECK(false, "ANSDecode: checksum mismatch seen on decoded data; archive cannot be unpacked");
 }
 
-// decompress_data_res, DietGpu.cpp:536-650
-int64_t decompressRes(bool asFloat, StackDeviceMemory& res, const std::vector<at::Tensor>& tsIn,
-                      const std::vector<at::Tensor>& tsOut, bool checksum, const std::optional<at::Tensor>& status,
-                      const std::optional<at::Tensor>& sizes) {
-  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
-  const int dev = tsIn.front().get_device();
-  DecodeMembers m = decodeMembers(tsIn, tsOut, asFloat, dev, "ts_out", [](size_t) {});
-  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
-  const hipStream_t s = currentStream(dev);
+// decompress_data_res, DietGpu.cpp:536-650: the full decode of the checked members
+int64_t decompressRes(bool asFloat, CallContext& cx, Members& m, bool checksum, uint8_t* st, uint32_t* sz) {
+  const auto n = uint32_t(m.in.size());
   if (asFloat) {
-    const FloatDecompressConfig cfg(floatTypeOf(tsOut.front().scalar_type()), ANSCodecConfig(kDefaultPrecision),
-                                    false, checksum);
-    const auto r =
-        floatDecompress(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(), st, sz, s);
+    const auto r = floatDecompress(*cx.res, floatConfig(floatTypeOf(m.first), checksum), n, m.in.data(),
+                                   m.out.data(), m.cap.data(), st, sz, cx.stream);
     raiseOnChecksum(true, r.error != FloatDecompressError::None);
   } else {
-    const ANSCodecConfig cfg(kDefaultPrecision, checksum);
-    const auto r = ansDecodeBatchPointer(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(),
-                                         st, sz, s);
+    const auto r = ansDecodeBatchPointer(*cx.res, byteConfig(checksum), n, m.in.data(), m.out.data(), m.cap.data(),
+                                         st, sz, cx.stream);
     raiseOnChecksum(false, r.error != ANSDecodeError::None);
   }
-  return int64_t(res.getMaxMemoryUsage());
+  return cx.used();
 }
+
+constexpr const char* kTsOutMessage = "ts_out must be contiguous GPU tensors on the input device";
 
 // DietGpu.cpp:652-683
 int64_t decompress_data(bool asFloat, const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsOut,
                         bool checksum, const std::optional<at::Tensor>& tempMem,
                         const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
-  auto res = makeStack(dev, tempMem);
-  return decompressRes(asFloat, res, tsIn, tsOut, checksum, status, sizes);
+  CallContext cx(inputDevice(tsIn), tempMem);
+  TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
+  Members m(cx.dev, tsIn.size(), tsIn.size());
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    m.archive(tsIn[i]);
+    m.dest(tsOut[i], asFloat, kTsOutMessage, asFloat ? &kFloatOutputs : nullptr);
+  }
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), cx.dev);
+  return decompressRes(asFloat, cx, m, checksum, st, sz);
 }
 
 // Extension (no reference counterpart): words [t_first[i], t_first[i] +
@@ -501,31 +530,46 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
                               const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
                               const std::optional<at::Tensor>& sizes) {
   TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsOut.size(), "ts_in and ts_out must have the same, nonzero length");
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
+  CallContext cx(inputDevice(tsIn));
   TORCH_CHECK(tFirst.is_contiguous() && tFirst.device().type() == at::kCPU && tFirst.scalar_type() == at::kLong,
               "t_first must be a contiguous CPU int64 tensor");
   TORCH_CHECK(tFirst.numel() == int64_t(tsIn.size()), "one t_first entry per compressed input");
   const int64_t* fp = tFirst.data_ptr<int64_t>();
   std::vector<uint32_t> first(tsIn.size());
   // (the members' capacities are the ranges' counts)
-  DecodeMembers m = decodeMembers(tsIn, tsOut, asFloat, dev, "ts_out", [&](size_t i) {
+  Members m(cx.dev, tsIn.size(), tsIn.size());
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    m.archive(tsIn[i]);
+    m.dest(tsOut[i], asFloat, kTsOutMessage, asFloat ? &kFloatOutputs : nullptr);
     TORCH_CHECK(fp[i] >= 0 && uint64_t(fp[i]) <= kU32Max, "t_first[", i, "] = ", fp[i], " is outside [0, 2^32)");
     first[i] = uint32_t(fp[i]);
-  });
-  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
-  if (asFloat) {
-    const FloatDecompressConfig cfg(floatTypeOf(tsOut.front().scalar_type()), ANSCodecConfig(kDefaultPrecision),
-                                    false, false);
-    floatDecompressRange(res, cfg, uint32_t(tsIn.size()), m.in.data(), first.data(), m.cap.data(), m.out.data(), st,
-                         sz, s);
-  } else {
-    ansDecodeBatchRange(res, ANSCodecConfig(kDefaultPrecision, false), uint32_t(tsIn.size()), m.in.data(),
-                        first.data(), m.cap.data(), m.out.data(), st, sz, s);
   }
-  return int64_t(res.getMaxMemoryUsage());
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), cx.dev);
+  cx.stack(tempMem);
+  if (asFloat) {
+    floatDecompressRange(*cx.res, floatConfig(floatTypeOf(m.first), false), uint32_t(tsIn.size()), m.in.data(),
+                         first.data(), m.cap.data(), m.out.data(), st, sz, cx.stream);
+  } else {
+    ansDecodeBatchRange(*cx.res, byteConfig(false), uint32_t(tsIn.size()), m.in.data(), first.data(), m.cap.data(),
+                        m.out.data(), st, sz, cx.stream);
+  }
+  return cx.used();
+}
+
+// float32 accumulators or outputs do not name their archives' type: fp32, or
+// fp16 / bf16 with the sum kept in fp32.  Which of the three is read from the
+// header of ts_in[0] = m.in[0]: one k_info launch and a 4-byte copy to the
+// host, so such a call synchronises the stream once.  `who` ("... take")
+// begins the refusal of a float64 archive.  Anything that is no float archive
+// is taken as fp32 and fails on the device with status 0, like any other
+// invalid member.
+FloatType peekArchiveType(CallContext& cx, Members& m, const at::Tensor& tsIn0, const char* who) {
+  at::Tensor type = at::zeros({1}, tsIn0.options().dtype(at::kInt));
+  floatGetCompressedInfo(*cx.res, m.in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()),
+                         nullptr, cx.stream);
+  const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
+  TORCH_CHECK(t0 != 4, who, " float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
+  return t0 == 1 || t0 == 2 ? FloatType(t0) : FloatType::kFloat32;
 }
 
 // Extension (no reference counterpart): ts_acc[i] += the element that dense
@@ -533,42 +577,28 @@ int64_t decompress_data_range(bool asFloat, const std::vector<at::Tensor>& tsIn,
 // (floatDecompressAccumulate).  The accumulators share one dtype, which
 // selects the mode: float16 / bfloat16 / float64 accumulators take archives
 // of their own type; float32 accumulators take fp32 archives or, with the
-// sum kept in fp32, fp16 / bf16 ones -- which of the three is read from
-// ts_in[0]'s header (one k_info launch and a 4-byte copy to the host), so a
-// float32 call synchronises the stream once.  A member whose archive has
-// another type fails with status 0, as in decompress_data.  No checksum flag:
-// none can be verified, and archives written with one are accepted.
+// sum kept in fp32, fp16 / bf16 ones (peekArchiveType tells which).  A member
+// whose archive has another type fails with status 0, as in decompress_data.
+// No checksum flag: none can be verified, and archives written with one are
+// accepted.
 int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const std::vector<at::Tensor>& tsAcc,
                                    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status,
                                    const std::optional<at::Tensor>& sizes) {
   TORCH_CHECK(!tsIn.empty() && tsIn.size() == tsAcc.size(), "ts_in and ts_acc must have the same, nonzero length");
-  for (const auto& ta : tsAcc) {
-    checkOutDtype(ta);
-    TORCH_CHECK(ta.scalar_type() == tsAcc.front().scalar_type(), "the accumulators (ts_acc) must share a dtype");
+  const FloatType accType = floatTypeOf(sharedDtype(tsAcc, {true, "float outputs", "the accumulators (ts_acc)"}));
+  CallContext cx(inputDevice(tsIn));
+  Members m(cx.dev, tsIn.size(), tsIn.size());
+  for (size_t i = 0; i < tsIn.size(); ++i) {
+    m.archive(tsIn[i]);
+    m.dest(tsAcc[i], /*asFloat=*/true, "ts_acc must be contiguous GPU tensors on the input device");
   }
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
-  // (the dtype checks above come first; in the loop they pass again)
-  DecodeMembers m = decodeMembers(tsIn, tsAcc, /*asFloat=*/true, dev, "ts_acc", [](size_t) {});
-  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), dev);
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
-  const FloatType accType = floatTypeOf(tsAcc.front().scalar_type());
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(tsIn.size()), cx.dev);
+  cx.stack(tempMem);
   FloatType ft = accType;
-  if (accType == FloatType::kFloat32) {
-    at::Tensor type = at::zeros({1}, tsIn.front().options().dtype(at::kInt));
-    floatGetCompressedInfo(res, m.in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
-                           s);
-    const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
-    TORCH_CHECK(t0 != 4, "float32 accumulators take float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
-    // (anything that is no float archive is decoded as fp32 and fails on the
-    // device with status 0, like any other invalid member)
-    if (t0 == 1 || t0 == 2) ft = FloatType(t0);
-  }
-  const FloatDecompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, false);
-  floatDecompressAccumulate(res, cfg, uint32_t(tsIn.size()), m.in.data(), m.out.data(), m.cap.data(), accType, st, sz,
-                            s);
-  return int64_t(res.getMaxMemoryUsage());
+  if (ft == FloatType::kFloat32) ft = peekArchiveType(cx, m, tsIn.front(), "float32 accumulators take");
+  floatDecompressAccumulate(*cx.res, floatConfig(ft, false), uint32_t(tsIn.size()), m.in.data(), m.out.data(),
+                            m.cap.data(), accType, st, sz, cx.stream);
+  return cx.used();
 }
 
 // Extension (no reference counterpart): the fused multi-archive reduce
@@ -578,11 +608,9 @@ int64_t decompress_data_accumulate(const std::vector<at::Tensor>& tsIn, const st
 // in one kernel pass over the K archives (without ts_init the sum starts as
 // x_1).  The outputs share one dtype, as do the inits: float16 / bfloat16
 // name the archives' type themselves; when both are float32 (or there is no
-// init and the outputs are float32) the archives' type is read from ts_in[0]'s
-// header, as decompress_data_accumulate does, and the call synchronises the
-// stream once.  ts_out[b] may be ts_init[b].  A member with an invalid
-// archive, archives of different sizes or a short output fails as a whole
-// with status 0 and is left untouched.
+// init and the outputs are float32) peekArchiveType reads it.  ts_out[b] may
+// be ts_init[b].  A member with an invalid archive, archives of different
+// sizes or a short output fails as a whole with status 0 and is left untouched.
 int64_t reduce_data(const std::vector<at::Tensor>& tsIn, int64_t numSources, const std::vector<at::Tensor>& tsOut,
                     const std::optional<std::vector<at::Tensor>>& tsInit, const std::optional<at::Tensor>& tempMem,
                     const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
@@ -590,65 +618,35 @@ int64_t reduce_data(const std::vector<at::Tensor>& tsIn, int64_t numSources, con
   TORCH_CHECK(!tsOut.empty() && int64_t(tsIn.size()) == numSources * int64_t(tsOut.size()),
               "ts_in must hold num_sources archives for each of the (one or more) ts_out");
   TORCH_CHECK(!tsInit || tsInit->size() == tsOut.size(), "ts_init and ts_out must have the same length");
-  auto sharedDtype = [](const std::vector<at::Tensor>& ts, const char* name) {
-    for (const auto& t : ts) {
-      const auto d = t.scalar_type();
-      TORCH_CHECK(d == at::kHalf || d == at::kBFloat16 || d == at::kFloat, name,
-                  " must be float16, bfloat16 or float32");
-      TORCH_CHECK(d == ts.front().scalar_type(), name, " must share a dtype");
-    }
-    return ts.front().scalar_type();
-  };
-  const at::ScalarType outD = sharedDtype(tsOut, "ts_out");
-  const at::ScalarType initD = tsInit ? sharedDtype(*tsInit, "ts_init") : outD;
+  const at::ScalarType outD = sharedDtype(tsOut, {false, "ts_out", "ts_out"});
+  const at::ScalarType initD = tsInit ? sharedDtype(*tsInit, {false, "ts_init", "ts_init"}) : outD;
   TORCH_CHECK(outD == at::kFloat || initD == at::kFloat || outD == initD,
               "ts_init and ts_out name different 16-bit archive types");
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
+  CallContext cx(inputDevice(tsIn));
   const size_t nb = tsOut.size();
-  std::vector<const void*> in(tsIn.size()), init(tsInit ? nb : 0);
-  std::vector<void*> out(nb);
-  std::vector<uint32_t> cap(nb);
-  for (size_t i = 0; i < tsIn.size(); ++i) {
-    checkArchiveTensor(tsIn[i], dev);
-    in[i] = tsIn[i].data_ptr();
-  }
+  Members m(cx.dev, tsIn.size(), nb);
+  std::vector<const void*> init(tsInit ? nb : 0);
+  for (const auto& ti : tsIn) m.archive(ti);
   for (size_t b = 0; b < nb; ++b) {
-    const auto& to = tsOut[b];
-    TORCH_CHECK(to.device().type() == at::kCUDA && to.get_device() == dev && to.is_contiguous(),
-                "ts_out must be contiguous GPU tensors on the input device");
-    TORCH_CHECK(uint64_t(to.numel()) <= kU32Max);
-    out[b] = to.data_ptr();
-    cap[b] = uint32_t(to.numel());
+    m.dest(tsOut[b], /*asFloat=*/true, kTsOutMessage);
     if (tsInit) {
       const auto& ti = (*tsInit)[b];
-      TORCH_CHECK(ti.device().type() == at::kCUDA && ti.get_device() == dev && ti.is_contiguous(),
-                  "ts_init must be contiguous GPU tensors on the input device");
+      checkDeviceTensor(ti, cx.dev, "ts_init must be contiguous GPU tensors on the input device");
       // (a member whose element is longer than its init fails like one whose
       // output is short: the capacity covers both)
-      cap[b] = uint32_t(std::min<int64_t>(to.numel(), ti.numel()));
+      m.cap[b] = uint32_t(std::min<int64_t>(tsOut[b].numel(), ti.numel()));
       init[b] = ti.data_ptr();
     }
   }
-  const auto [st, sz] = statusPointers(status, sizes, int64_t(nb), dev);
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
+  const auto [st, sz] = statusPointers(status, sizes, int64_t(nb), cx.dev);
+  cx.stack(tempMem);
   const FloatType outType = floatTypeOf(outD), initType = floatTypeOf(initD);
   FloatType ft = outType != FloatType::kFloat32 ? outType : initType;
-  if (ft == FloatType::kFloat32) {
-    at::Tensor type = at::zeros({1}, tsIn.front().options().dtype(at::kInt));
-    floatGetCompressedInfo(res, in.data(), 1, nullptr, reinterpret_cast<uint32_t*>(type.data_ptr<int32_t>()), nullptr,
-                           s);
-    const int32_t t0 = type.to(at::kCPU).data_ptr<int32_t>()[0];
-    TORCH_CHECK(t0 != 4, "reduce_data takes float16, bfloat16 or float32 archives; ts_in[0] is a float64 one");
-    // (anything that is no float archive is reduced as fp32 and fails on the
-    // device with status 0, like any other invalid member)
-    if (t0 == 1 || t0 == 2) ft = FloatType(t0);
-  }
-  const FloatDecompressConfig cfg(ft, ANSCodecConfig(kDefaultPrecision), false, false);
-  floatReduceArchives(res, cfg, uint32_t(nb), uint32_t(numSources), in.data(), tsInit ? init.data() : nullptr,
-                      initType, out.data(), cap.data(), outType, st, sz, s);
-  return int64_t(res.getMaxMemoryUsage());
+  if (ft == FloatType::kFloat32) ft = peekArchiveType(cx, m, tsIn.front(), "reduce_data takes");
+  floatReduceArchives(*cx.res, floatConfig(ft, false), uint32_t(nb), uint32_t(numSources), m.in.data(),
+                      tsInit ? init.data() : nullptr, initType, m.out.data(), m.cap.data(), outType, st, sz,
+                      cx.stream);
+  return cx.used();
 }
 
 // Extension (no reference counterpart): rows t_idx[...] of the [R, row_words]
@@ -667,7 +665,7 @@ int64_t gather_rows(bool asFloat, const at::Tensor& tIn, int64_t rowWords, const
   TORCH_CHECK(tIdx.scalar_type() == at::kInt || tIdx.scalar_type() == at::kLong, "t_idx must be int32 or int64, not ",
               tIdx.scalar_type());
   if (asFloat) {
-    checkOutDtype(tOut);
+    checkDtype(tOut, tOut.scalar_type(), kFloatOutputs);
   } else {
     TORCH_CHECK(tOut.scalar_type() == at::kByte, "t_out must be uint8 in byte mode, not ", tOut.scalar_type());
   }
@@ -694,79 +692,69 @@ int64_t gather_rows(bool asFloat, const at::Tensor& tIn, int64_t rowWords, const
   const int dev = tIdx.get_device();
   checkArchiveTensor(tIn, dev);
   TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
-  c10::hip::HIPGuard guard(dev);
+  CallContext cx(dev);
   const auto st = statusPointers(status, std::nullopt, tIdx.numel(), dev).first;
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
+  cx.stack(tempMem);
   const bool is64 = tIdx.scalar_type() == at::kLong;
   if (asFloat) {
-    const FloatDecompressConfig cfg(floatTypeOf(tOut.scalar_type()), ANSCodecConfig(kDefaultPrecision), false, false);
-    floatGatherRows(res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(tIdx.numel()), tIdx.data_ptr(), is64,
-                    tOut.data_ptr(), uint64_t(rowStride), st, s);
+    floatGatherRows(*cx.res, floatConfig(floatTypeOf(tOut.scalar_type()), false), tIn.data_ptr(), uint32_t(rowWords),
+                    uint32_t(tIdx.numel()), tIdx.data_ptr(), is64, tOut.data_ptr(), uint64_t(rowStride), st,
+                    cx.stream);
   } else {
-    ansGatherRows(res, ANSCodecConfig(kDefaultPrecision, false), tIn.data_ptr(), uint32_t(rowWords),
-                  uint32_t(tIdx.numel()), tIdx.data_ptr(), is64, tOut.data_ptr(), uint64_t(rowStride), st, s);
+    ansGatherRows(*cx.res, byteConfig(false), tIn.data_ptr(), uint32_t(rowWords), uint32_t(tIdx.numel()),
+                  tIdx.data_ptr(), is64, tOut.data_ptr(), uint64_t(rowStride), st, cx.stream);
   }
-  return int64_t(res.getMaxMemoryUsage());
+  return cx.used();
 }
 
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
                                    const std::optional<at::Tensor>& status, const std::optional<at::Tensor>& sizes) {
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
+  CallContext cx(inputDevice(tsIn));
   SplitSizes split(tSplit, "t_out_split_sizes");
   const int64_t n = split.n;
   TORCH_CHECK(n == int64_t(tsIn.size()), "one split size per compressed input");
-  std::vector<const void*> in(static_cast<size_t>(n));
+  Members m(cx.dev, tsIn.size(), 0);
   for (int64_t i = 0; i < n; ++i) {
-    const auto& ti = tsIn[size_t(i)];
-    checkArchiveTensor(ti, dev);
+    m.archive(tsIn[size_t(i)]);
     split.take(i);
-    in[size_t(i)] = ti.data_ptr();
   }
-  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev && tOut.is_contiguous(),
-              "t_out must be a contiguous GPU tensor on the input device");
-  if (asFloat) checkOutDtype(tOut);
+  checkDeviceTensor(tOut, cx.dev, "t_out must be a contiguous GPU tensor on the input device");
+  if (asFloat) checkDtype(tOut, tOut.scalar_type(), kFloatOutputs);
   checkSplitSum(split.sum, tOut, asFloat, "t_out");
-  const auto [st, sz] = statusPointers(status, sizes, n, dev);
-  auto res = makeStack(dev, tempMem);
-  const hipStream_t s = currentStream(dev);
+  const auto [st, sz] = statusPointers(status, sizes, n, cx.dev);
+  cx.stack(tempMem);
   if (asFloat) {
-    const FloatDecompressConfig cfg(floatTypeOf(tOut.scalar_type()), ANSCodecConfig(kDefaultPrecision), false,
-                                    checksum);
-    const auto r = floatDecompressSplitSize(res, cfg, uint32_t(n), in.data(), tOut.data_ptr(), split.data(), st, sz, s);
+    const auto r = floatDecompressSplitSize(*cx.res, floatConfig(floatTypeOf(tOut.scalar_type()), checksum),
+                                            uint32_t(n), m.in.data(), tOut.data_ptr(), split.data(), st, sz, cx.stream);
     raiseOnChecksum(true, r.error != FloatDecompressError::None);
   } else {
-    const ANSCodecConfig cfg(kDefaultPrecision, checksum);
-    const auto r = ansDecodeBatchSplitSize(res, cfg, uint32_t(n), in.data(), tOut.data_ptr(), split.data(), st, sz, s);
+    const auto r = ansDecodeBatchSplitSize(*cx.res, byteConfig(checksum), uint32_t(n), m.in.data(), tOut.data_ptr(),
+                                           split.data(), st, sz, cx.stream);
     raiseOnChecksum(false, r.error != ANSDecodeError::None);
   }
-  return int64_t(res.getMaxMemoryUsage());
+  return cx.used();
 }
 
 // DietGpu.cpp:834-917
 std::vector<at::Tensor> decompress_data_simple(bool asFloat, const std::vector<at::Tensor>& tsIn, bool checksum,
                                                std::optional<int64_t> tempMem) {
-  const int dev = inputDevice(tsIn);
-  c10::hip::HIPGuard guard(dev);
-  for (const auto& t : tsIn) checkArchiveTensor(t, dev);  // (before k_info reads the headers)
-  std::optional<at::Tensor> scratch;
+  std::optional<at::Tensor> scratch;  // (declared first: it outlives the arena over it)
+  CallContext cx(inputDevice(tsIn));
+  const auto n = int64_t(tsIn.size());
+  Members m(cx.dev, tsIn.size(), tsIn.size());
+  for (const auto& t : tsIn) m.archive(t);  // (checked once, before k_info reads the headers)
   if (tempMem && *tempMem >= int64_t(kSDMAlignment)) {
     scratch = at::empty({*tempMem}, tsIn.front().options().dtype(at::kByte));
   }
-  const auto n = int64_t(tsIn.size());
   at::Tensor info = at::zeros({2, n}, tsIn.front().options().dtype(at::kInt));
-  auto res = makeStack(dev, scratch);
-  std::vector<const void*> in(tsIn.size());
-  for (size_t i = 0; i < tsIn.size(); ++i) in[i] = tsIn[i].data_ptr();
-  const hipStream_t s = currentStream(dev);
+  cx.stack(scratch);
   auto* sizesDev = reinterpret_cast<uint32_t*>(info.data_ptr<int32_t>());
   if (asFloat) {
-    floatGetCompressedInfo(res, in.data(), uint32_t(n), sizesDev, sizesDev + n, nullptr, s);
+    floatGetCompressedInfo(*cx.res, m.in.data(), uint32_t(n), sizesDev, sizesDev + n, nullptr, cx.stream);
   } else {
-    ansGetCompressedInfo(res, in.data(), uint32_t(n), sizesDev, nullptr, s);
+    ansGetCompressedInfo(*cx.res, m.in.data(), uint32_t(n), sizesDev, nullptr, cx.stream);
   }
   const at::Tensor host = info.to(at::kCPU);
   const int32_t* h = host.data_ptr<int32_t>();
@@ -781,8 +769,9 @@ std::vector<at::Tensor> decompress_data_simple(bool asFloat, const std::vector<a
     } else {
       outs.push_back(at::empty({size}, tsIn.front().options().dtype(at::kByte)));
     }
+    m.dest(outs.back(), asFloat, kTsOutMessage);
   }
-  decompressRes(asFloat, res, tsIn, outs, checksum, std::nullopt, std::nullopt);
+  decompressRes(asFloat, cx, m, checksum, nullptr, nullptr);
   return outs;
 }
 

@@ -3,16 +3,26 @@
 The operators are native: ``TORCH_LIBRARY(dietgpu)`` in
 ``csrc/torch_ops.cpp``, built into ``_lib/libdietgpu_torch.so`` and loaded
 with ``torch.ops.load_library`` exactly as the reference's harnesses load its
-``DietGpu.cpp`` extension (dietgpu/DietGpu.cpp:921-978: its ten operators
-with the same schemas, validation and return values).  An eleventh,
-``decompress_data_range``, is an extension the reference does not have: it
-decodes a word range of each archive.  A twelfth,
-``decompress_data_accumulate``, adds each archive's element to an accumulator
-tensor in place.  ``gather_rows`` (``MORE_OPS``) gathers rows of a table held
-by one archive, named by an index tensor on the device; ``reduce_data``
-(``REDUCE_OPS``) sums several archives per member in one kernel.  This module only
-loads that library
-and forwards ``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.
+``DietGpu.cpp`` extension.  This module only loads that library and forwards
+``ops.<name>(...)`` to ``torch.ops.dietgpu.<name>``.  "ref": one of the
+reference's ten operators (dietgpu/DietGpu.cpp:921-978) with its schema,
+validation and return values; "ext": not in the reference.
+
+    operator                          from  list        what it does
+    max_float_compressed_output_size  ref   OPS         rows and row bytes for a float list
+    max_float_compressed_size         ref   OPS         archive bound of `size` words
+    max_any_compressed_output_size    ref   OPS         rows and row bytes for a byte list
+    max_any_compressed_size           ref   OPS         archive bound of `bytes` bytes
+    compress_data                     ref   OPS         a tensor list into archive rows
+    compress_data_split_size          ref   OPS         the splits of one tensor
+    compress_data_simple              ref   OPS         a tensor list, own scratch, fresh archives
+    decompress_data                   ref   OPS         archives into the given tensors
+    decompress_data_split_size        ref   OPS         archives into the splits of one tensor
+    decompress_data_simple            ref   OPS         archives into fresh tensors
+    decompress_data_range             ext   OPS         a word range of each archive
+    decompress_data_accumulate        ext   OPS         adds each archive's element to an accumulator
+    gather_rows                       ext   MORE_OPS    rows of a table held by one archive, by device indices
+    reduce_data                       ext   REDUCE_OPS  sums several archives per member in one kernel
 """
 import os
 

@@ -299,6 +299,16 @@ def test_write_lines(tmp_path, capsys):
     assert [json.loads(ln) for ln in capsys.readouterr().out.splitlines()] == lines
 
 
+def test_ops_bench_times_every_launching_operator():
+    """tools/ops_bench.py's case table names every torch operator but the
+    four size operators, which launch nothing."""
+    from dietgpu_fork_amd import ops
+
+    sizes = {"max_float_compressed_output_size", "max_float_compressed_size", "max_any_compressed_output_size",
+             "max_any_compressed_size"}
+    assert {case.split()[0] for case in _load("ops_bench").CASES} == set(ops.OPS + ops.MORE_OPS + ops.REDUCE_OPS) - sizes
+
+
 # ---- variants ----
 
 def test_every_variant_applies():
