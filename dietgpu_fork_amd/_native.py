@@ -85,6 +85,8 @@ def _declare(L):
         "dietgpu_float_decompress_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
         "dietgpu_float_decompress_sparse_accumulate": (c_int, [vp, c_int, c_int, c_u32, P, P, P, c_int, P, P, P]),
         "dietgpu_float_reduce": (c_int, [vp, c_int, c_int, c_u32, c_u32, P, P, c_int, P, P, c_int, P, P, P]),
+        "dietgpu_float_reduce_sparse": (c_int, [vp, c_int, c_int, c_u32, c_u32, P, P, c_int, P, P, c_int, P, P, P]),
+        "dietgpu_float_reduce_sparse_scratch_bytes": (c_u64, [c_int, c_u32, c_u32, c_u32]),
         "dietgpu_ans_gather_rows": (c_int, [vp, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_float_gather_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
@@ -131,6 +133,8 @@ def testlib():
                "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
                "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
+               "dietgpu_test_sparse_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_int, P, c_u32, c_int, P,
+                                                             P, P]),
                "dietgpu_test_compress_plan": (c_int, [c_int, c_u32, c_u32, c_int, c_int, c_int, P])}
         for name, (res, args) in sig.items():
             f = getattr(T, name)

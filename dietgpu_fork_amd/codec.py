@@ -309,9 +309,9 @@ REDUCE_MAX_SOURCES = 64
 
 
 def set_reduce_max_sources(ns):
-    """Test / tuning hook: the most sources one k_reduce launch takes (0: the
-    largest instance, the default); more sources chain passes through an fp32
-    partial.  The results are the same bits."""
+    """Test / tuning hook: the most sources one k_reduce or k_sparseReduce
+    launch takes (0: the largest instance, the default); more sources chain
+    passes through an fp32 partial.  The results are the same bits."""
     N.lib().dietgpu_set_reduce_max_sources(int(ns))
 
 
@@ -340,10 +340,9 @@ def float_reduce(sources, outs, inits=None, ft=None, prob_bits=10, ws=None):
     return ok, sz
 
 
-def _reduce_types(sources, outs, inits, ft):
-    """float_reduce's argument checks, before the library is touched -> (the
-    archives' float type, the inits' (0: none), the outs')."""
-    who = "float_reduce"
+def _reduce_types(sources, outs, inits, ft, who="float_reduce"):
+    """float_reduce's and sparse_reduce's argument checks, before the library
+    is touched -> (the archives' float type, the inits' (0: none), the outs')."""
     K, nb = len(sources), len(outs)
     if not 1 <= K <= REDUCE_MAX_SOURCES:
         raise ValueError(f"{who}: the number of sources ({K}) must be in 1 .. {REDUCE_MAX_SOURCES}")
@@ -563,6 +562,42 @@ def sparse_decompress_accumulate(archives, accs, ft=None, prob_bits=10, ws=None)
     ft, acc_ft = _accumulate_types("sparse_decompress_accumulate", archives, accs, ft)
     return _pointer_decode(N.lib().dietgpu_float_decompress_sparse_accumulate, (ft, prob_bits), archives, accs, ws,
                            tail=(acc_ft,))
+
+
+def sparse_reduce(sources, outs, inits=None, ft=None, prob_bits=10, ws=None):
+    """float_reduce for sparse float archives (16-byte aligned), in one fused
+    kernel per pass (k_sparseReduce) -> (ok, sz): a = float(inits[b][i]); for
+    each source k in order, a = a + float(x_k[i]) in fp32 where bit i of x_k's
+    bitmap is set (the word is not +0.0 bitwise), a unchanged where it is
+    clear; outs[b][i] = round(a).  A clear bit is skipped, never added as
+    +0.0, so an init word of -0.0 under clear bits stays -0.0: the bits of
+    own.float(), one sparse_decompress_accumulate per source, one rounding.
+    inits=None: the sum starts as the decoded word x_1[i] and runs over
+    x_2 .. x_K.  Arguments, dtype rules and checks as float_reduce; sz is n of
+    the first source for every member."""
+    ft, init_ft, out_ft = _reduce_types(sources, outs, inits, ft, who="sparse_reduce")
+    K, nb = len(sources), len(outs)
+    dev = outs[0].device
+    ok = torch.empty([nb], dtype=torch.uint8, device=dev)
+    sz = torch.empty([nb], dtype=torch.int32, device=dev)
+    ws = _ws(ws, dev)
+    N.check(N.lib().dietgpu_float_reduce_sparse(
+        ws.h, ft, prob_bits, nb, K, N.ptr_array([a.data_ptr() for row in sources for a in row]),
+        N.ptr_array([t.data_ptr() for t in inits]) if inits is not None else None, init_ft,
+        N.ptr_array([o.data_ptr() for o in outs]), N.u32_array([o.numel() for o in outs]), out_ft,
+        ok.data_ptr(), sz.data_ptr(), _s()))
+    return ok, sz
+
+
+def sparse_reduce_scratch_bytes(ft, nb, num_sources, max_capacity):
+    """The workspace bytes a sparse_reduce call of nb members, num_sources
+    sources and outs of at most max_capacity words takes at most (the plan's,
+    csrc/sparse_plan.h planSparseReduce; host arithmetic only).  It is bounded
+    by the sources of one kernel launch, not by num_sources."""
+    v = N.lib().dietgpu_float_reduce_sparse_scratch_bytes(int(ft), int(nb), int(num_sources), int(max_capacity))
+    if v == 0:
+        raise N.DietGpuError(N.lib().dietgpu_last_error().decode(errors="replace"))
+    return v
 
 
 def profile(on=True):

@@ -360,6 +360,30 @@ int dietgpu_float_reduce(dietgpu_stack* res, int ft, int pb, uint32_t nb, uint32
   });
 }
 
+int dietgpu_float_reduce_sparse(dietgpu_stack* res, int ft, int pb, uint32_t nb, uint32_t num_sources,
+                                const void** in, const void** init, int init_type, void** out, const uint32_t* cap,
+                                int out_type, uint8_t* succ, uint32_t* sizes, void* stream) {
+  return guarded([&] {
+    // (the same order of checks as dietgpu_float_reduce)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkReduceShape(ft, num_sources, init != nullptr, init_type, out_type);
+    checkProbBits(pb);
+    floatReduceSparseArchives(R(res), cfg, nb, num_sources, in, init, FloatType(init_type), out, cap,
+                              FloatType(out_type), succ, sizes, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
+uint64_t dietgpu_float_reduce_sparse_scratch_bytes(int ft, uint32_t nb, uint32_t num_sources, uint32_t max_capacity) {
+  uint64_t v = 0;
+  guarded([&] {
+    checkReduceShape(ft, num_sources, false, ft, ft);
+    v = floatReduceSparseScratchBytes(FloatType(ft), nb, num_sources, max_capacity);
+    return DIETGPU_OK;
+  });
+  return v;
+}
+
 // (the gather entry points check the flattened config and the row shape
 // before they look at the stack or any pointer)
 int dietgpu_ans_gather_rows(dietgpu_stack* res, int pb, const void* archive_dev, uint32_t row_words,

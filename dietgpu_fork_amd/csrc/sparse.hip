@@ -22,7 +22,10 @@
 // element is added to an accumulator without a temporary
 // (floatDecompressSparseAccumulate, an extension): k_sparseExpand<FT, ACC>
 // adds the nonzero words where the full decode stores them and touches no
-// other accumulator word.
+// other accumulator word.  K archives are summed without any accumulator in
+// memory (floatReduceSparseArchives, an extension): k_sparseReduce<FT, NS>
+// expands the same chunk of NS archives side by side and keeps the fp32
+// running sum in registers, a clear bit a select and never an add of +0.0.
 //
 // Wire format: 16 B header {u32 N, 12 B zero}, bitmap
 // ceil(N/8) bytes (bit 7 of byte k <-> element 8k) padded to 16, then a dense
@@ -554,6 +557,175 @@ __global__ __launch_bounds__(kThreads) void k_sparseExpand(BatchDesc in, BatchDe
   }
 }
 
+// What a pass of the fused sparse reduce reads and writes beside its archives.
+struct SparseRedArgs {
+  uint32_t batchOffset;  // first member of this grid slice
+  uint32_t nb;           // members: source s of member b is row s * nb + b of the pass
+  uint32_t chunksPerElem, blocksPerElem;
+  uint32_t initKind;  // 0: none (the sum starts as float(x_1)), 1: the archives' 16-bit type, 2: fp32
+  uint32_t outF32;    // out words are fp32 (always for fp32 archives and for the partial)
+  uint32_t first;     // the call's first pass: no earlier verdict, n is this pass's first source's
+  uint32_t last;      // the call's last pass writes outSuccess / outSize, the others the verdict
+};
+
+// Fused sparse reduce: one pass over sources s < NS of every
+// member on top of `init`,
+//   a = float(init[i])  (initKind 0: the decoded word x_0[i], +0.0 under a clear bit)
+//   a = bit i of source s set ? a + float(x_s[i]) : a,  sources in order
+//   out[i] = round(a),
+// the running sum in 16 fp32 registers per lane.  One wave per 1024-word chunk
+// like k_sparseExpand, no LDS and no barrier: per source lanes 0-15 load the
+// chunk's 16 bitmap words beside its list offset, then the NS x 16 list
+// gathers (expandRows) and the 16 init loads (source 0's row hook) are issued
+// back to back before one counted wait (landed), the sums, and 16 row stores.
+// A clear bit is a select of `a`, never an add of +0.0: an init of -0.0 or a
+// signalling NaN under clear bits keeps its bits.  PART: `out` is the fp32
+// partial that the next pass reads (plain stores); otherwise the caller's out
+// (streaming stores; a compile-time choice, as for Join::vec).
+//
+// A member goes on iff every source so far had a valid dense part
+// (denseOk) and the same n as the call's first source, and out.size(b) >= n:
+// `verdictIn` carries that from the earlier passes, `verdictOut` (another
+// array) to the next one, firstN the first source's n.  A failing member
+// returns before any list, bitmap, init or out word is touched; for the others
+// every list index lies below the row's popcount + 1 <= n + 1 words.
+template <int FT, int NS, bool PART>
+__global__ __launch_bounds__(kThreads) void k_sparseReduce(BatchDesc in, BatchDesc init, BatchDesc out,
+                                                           SparseRedArgs a, const uint32_t* __restrict__ sizes,
+                                                           const uint32_t* __restrict__ chunkPre,
+                                                           const uint32_t* __restrict__ blockTot, BatchDesc lists,
+                                                           const uint8_t* __restrict__ denseOk,
+                                                           const uint8_t* __restrict__ verdictIn,
+                                                           uint8_t* __restrict__ verdictOut, uint32_t* firstN,
+                                                           uint8_t* __restrict__ outSuccess,
+                                                           uint32_t* __restrict__ outSize) {
+  static_assert(FT >= 1 && FT <= 3 && NS >= 1 && NS <= int(kSparseReduceMaxNS), "fp16, bf16 and fp32; 1 .. 4 sources");
+  using W = WordOf<FT>;
+  using J = Join<FT>;
+  const uint32_t b = a.batchOffset + blockIdx.y;
+  const uint32_t n = readfirst(a.first ? sizes[b] : G(firstN)[b]);
+  bool good = a.first || verdictIn[b] != 0;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) good = good && denseOk[s * a.nb + b] != 0 && sizes[s * a.nb + b] == n;
+  const bool ok = good && out.size(b) >= n;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (a.last) {
+      if (outSuccess) outSuccess[b] = ok ? 1 : 0;
+      if (outSize) outSize[b] = n;  // the first source's, as the sparse decode reports it
+    } else {
+      verdictOut[b] = good ? 1 : 0;
+      if (a.first) G(firstN)[b] = n;
+    }
+  }
+  const uint32_t lane = threadIdx.x & 63, w = readfirst(threadIdx.x >> 6);
+  const uint32_t c = blockIdx.x * kWaves + w;
+  const uint32_t i0 = c * kChunkWords;
+  if (!ok || c >= a.chunksPerElem || i0 >= n) return;
+
+  uint64_t mv[NS];
+  uint32_t base[NS];
+  bool gap[NS];
+  gp<const W> list[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const uint32_t row = s * a.nb + b;
+    gp<const uint8_t> bm = (gp<const uint8_t>)in.start(row) + kSparseHeaderBytes;
+    mv[s] = chunkBitmapWord(bm, c, n - i0, lane);
+    base[s] = chunkListOffset(G(chunkPre) + uint64_t(row) * a.chunksPerElem,
+                              G(blockTot) + uint64_t(row) * a.blocksPerElem, c, lane);
+    // only the chunk holding word n-1 looks; per source
+    gap[s] = n - 1 - i0 < kChunkWords && gapBit(bm, n);
+    list[s] = (gp<const W>)lists.start(row);
+  }
+
+  const uint32_t initKind = a.initKind;
+  gp<const uint8_t> initB = initKind ? (gp<const uint8_t>)init.start(b) : nullptr;
+  W v[NS][kChunkRows];
+  uint32_t d[kChunkRows];  // the init words' bits
+  uint32_t taken[NS];      // bit j: this lane's word of row j has its bitmap bit set in source s
+#pragma unroll
+  for (uint32_t j = 0; j < kChunkRows; ++j) d[j] = 0;
+  // (mv holds no bit at or past n, so every gather of a set bit is wanted)
+  auto inside = [](uint32_t) { return true; };
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    taken[s] = 0;
+    auto mark = [&](uint32_t j, bool set) __attribute__((always_inline)) {
+      taken[s] |= (set ? 1u : 0u) << j;
+    };
+    // (the init loads test i < n: the last chunk's rows may end early)
+    if (s == 0 && initKind == 2) {
+      expandRows(mv[s], base[s], i0, n, gap[s], list[s], lane, inside, v[s],
+                 [&](uint32_t j, uint32_t i, bool set) __attribute__((always_inline)) {
+                   d[j] = i < n ? ((gp<const uint32_t>)initB)[i] : 0u;
+                   mark(j, set);
+                 });
+    } else if (FT != 3 && s == 0 && initKind == 1) {
+      expandRows(mv[s], base[s], i0, n, gap[s], list[s], lane, inside, v[s],
+                 [&](uint32_t j, uint32_t i, bool set) __attribute__((always_inline)) {
+                   d[j] = i < n ? uint32_t(((gp<const uint16_t>)initB)[i]) : 0u;
+                   mark(j, set);
+                 });
+    } else {
+      expandRows(mv[s], base[s], i0, n, gap[s], list[s], lane, inside, v[s],
+                 [&](uint32_t j, uint32_t, bool set) __attribute__((always_inline)) { mark(j, set); });
+    }
+  }
+  // one wait for the NS x 16 gathers and the 16 init loads, where the wave has
+  // converged (k_sparseExpand's accumulate form, DESIGN.md 5.2f "One wait")
+#pragma unroll
+  for (uint32_t j = 0; j < kChunkRows; ++j) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) landed(v[s][j]);
+    landed(d[j]);
+  }
+
+  auto asFloat = [](W x) __attribute__((always_inline)) {
+    if constexpr (FT == 3) return __builtin_bit_cast(float, x);
+    else return J::widen(x);
+  };
+  float acc[kChunkRows];
+#pragma unroll
+  for (uint32_t j = 0; j < kChunkRows; ++j) {
+    const float x0 = asFloat(v[0][j]);
+    float t = x0;
+    if (initKind != 0) {
+      float i32 = __builtin_bit_cast(float, d[j]);
+      if constexpr (FT != 3) i32 = initKind == 2 ? i32 : J::widen(d[j]);
+      t = (taken[0] >> j) & 1 ? i32 + x0 : i32;
+    }
+#pragma unroll
+    for (int s = 1; s < NS; ++s) t = (taken[s] >> j) & 1 ? t + asFloat(v[s][j]) : t;
+    acc[j] = t;
+  }
+
+  // each lane stores one word per row: no alignment of `out` matters
+  gp<uint8_t> y = startOf(out, b);
+  if constexpr (PART) {
+#pragma unroll
+    for (uint32_t j = 0; j < kChunkRows; ++j) {
+      const uint32_t i = i0 + 64 * j + lane;
+      if (i < n) ((gp<float>)y)[i] = acc[j];  // plain: the next pass reads it
+    }
+  } else if (FT == 3 || a.outF32 != 0) {
+#pragma unroll
+    for (uint32_t j = 0; j < kChunkRows; ++j) {
+      const uint32_t i = i0 + 64 * j + lane;
+      if (i < n) __builtin_nontemporal_store(acc[j], (gp<float>)y + i);
+    }
+  } else if constexpr (FT != 3) {
+    // one rounding to nearest even
+#pragma unroll
+    for (uint32_t j = 0; j < kChunkRows; ++j) {
+      const uint32_t i = i0 + 64 * j + lane;
+      uint16_t h;
+      if constexpr (FT == 1) h = __builtin_bit_cast(uint16_t, _Float16(acc[j]));
+      else h = uint16_t(J::bf16Of(acc[j]));
+      if (i < n) __builtin_nontemporal_store(h, (gp<uint16_t>)y + i);
+    }
+  }
+}
+
 // c: the sparse inputs (sizes = N, at most c.maxSize) -> the sparse archives
 // c.out; denseOut: where each dense archive starts; c.sparseN: a device array
 // holding each element's N (the dense archive's size writer adds the sparse
@@ -706,6 +878,109 @@ FloatDecompressStatus sparseDecompressT(const FloatDecompressConfig& config, con
     if constexpr (FT == 1 || FT == 2) expand(std::integral_constant<int, 2>{});
   }
   return status;
+}
+
+// One fused reduce call: `in` holds the K * nb archives
+// source-major, `partial` the fp32 rows between the passes.
+struct SparseReduceCall {
+  StackDeviceMemory& res;
+  hipStream_t s;
+  uint32_t nb;
+  const SparseReducePlan& plan;
+  const uint64_t* inPtrs;  // device column of the K * nb archive addresses
+  BatchDesc init, out, partial;
+  uint32_t initKind;
+  bool outF32;
+  uint8_t* outSuccess_dev;
+  uint32_t* outSize_dev;
+};
+
+template <int FT, int NS>
+void launchSparseReduce(const SparseReduceCall& c, const ReducePass& ps, const BatchDesc& in, const BatchDesc& lists,
+                        SparseRedArgs a, const uint32_t* sizes, const uint32_t* chunkPre, const uint32_t* blockTot,
+                        const uint8_t* denseOk, const uint8_t* verdictIn, uint8_t* verdictOut, uint32_t* firstN) {
+  forGridYSlices(c.nb, [&](uint32_t y0, uint32_t ny) {
+    prof::Scope p("sparse_reduce", c.s);
+    a.batchOffset = y0;
+    const BatchDesc& init = ps.initIsPartial ? c.partial : c.init;
+    const dim3 grid(c.plan.d.gridX, ny);
+    if (ps.outIsPartial) {
+      k_sparseReduce<FT, NS, true><<<grid, kThreads, 0, c.s>>>(in, init, c.partial, a, sizes, chunkPre, blockTot,
+                                                               lists, denseOk, verdictIn, verdictOut, firstN,
+                                                               c.outSuccess_dev, c.outSize_dev);
+    } else {
+      k_sparseReduce<FT, NS, false><<<grid, kThreads, 0, c.s>>>(in, init, c.out, a, sizes, chunkPre, blockTot, lists,
+                                                                denseOk, verdictIn, verdictOut, firstN,
+                                                                c.outSuccess_dev, c.outSize_dev);
+    }
+    HIP_LAUNCH_CHECK();
+  });
+}
+
+// The passes of planReduce, each: the chunk counts of the pass's NS * nb
+// archives, one dense full decode of their nonzero lists into the scratch
+// rows, one k_sparseReduce launch.  Rows, counts and totals are sized for the
+// widest pass and reused by the next one (everything is stream-ordered), so
+// the scratch is bounded by the sources per launch, not by K.
+template <int FT>
+void sparseReduceT(const FloatDecompressConfig& config, const SparseReduceCall& c) {
+  static_assert(kSparseReduceMaxNS == 4, "one case per instance");
+  StackDeviceMemory& res = c.res;
+  const hipStream_t s = c.s;
+  const SparseReducePlan& plan = c.plan;
+  const uint32_t nb = c.nb, chunks = plan.d.chunks, cblocks = plan.d.cblocks;
+  auto densePtrs = res.alloc<uint64_t>(s, plan.densePtrs);
+  auto sizes = res.alloc<uint32_t>(s, plan.sizes);
+  auto denseOk = res.alloc<uint8_t>(s, plan.denseOk);
+  auto list = res.alloc<uint8_t>(s, plan.d.listBytes);
+  auto chunkPre = res.alloc<uint32_t>(s, plan.d.chunkPre);
+  auto blockTot = res.alloc<uint32_t>(s, plan.d.blockTot);
+  auto verdict = res.alloc<uint8_t>(s, plan.verdict);
+  auto firstN = res.alloc<uint32_t>(s, plan.firstN);
+  auto cfg = config;
+  cfg.useChecksum = false;
+  for (uint32_t i = 0; i < plan.passes.numPasses; ++i) {
+    const ReducePass& ps = plan.passes.passes[i];
+    const uint32_t rows = ps.count * nb;
+    const BatchDesc in = BatchDesc::pointers(c.inPtrs + uint64_t(ps.first) * nb, nullptr);
+    forGridYSlices(rows, [&](uint32_t y0, uint32_t ny) {
+      prof::Scope p("sparse_reduce", s);
+      k_sparseChunks<<<dim3(cblocks, ny), kThreads, 0, s>>>(in, y0, chunks, cblocks, densePtrs.data(), sizes.data(),
+                                                            chunkPre.data(), blockTot.data());
+      HIP_LAUNCH_CHECK();
+    });
+    DecodeCall dense{res, s};
+    dense.nb = rows;
+    dense.in = BatchDesc::pointers(densePtrs.data(), nullptr);
+    dense.out = BatchDesc::strided(list.data(), plan.d.listStride, plan.d.denseCapacity);
+    dense.maxCapacity = plan.d.denseCapacity;
+    dense.outSuccess_dev = denseOk.data();
+    dense.streamOut = false;  // the reduce reads it
+    dense.capacityOnly = true;
+    floatDecompressDescs(cfg, dense);
+    SparseRedArgs a{};
+    a.nb = nb;
+    a.chunksPerElem = chunks;
+    a.blocksPerElem = cblocks;
+    a.initKind = ps.initIsPartial ? 2u : c.initKind;
+    a.outF32 = ps.outIsPartial || c.outF32 ? 1u : 0u;
+    a.first = i == 0 ? 1u : 0u;
+    a.last = ps.outIsPartial ? 0u : 1u;
+    const uint8_t* verdictIn = verdict.data() + size_t((i + 1) & 1) * nb;
+    uint8_t* verdictOut = verdict.data() + size_t(i & 1) * nb;
+    auto launch = [&](auto ns) {
+      launchSparseReduce<FT, decltype(ns)::value>(c, ps, in, dense.out, a, sizes.data(), chunkPre.data(),
+                                                  blockTot.data(), denseOk.data(), verdictIn, verdictOut,
+                                                  firstN.data());
+    };
+    switch (ps.count) {
+      case 1: launch(std::integral_constant<int, 1>{}); break;
+      case 2: launch(std::integral_constant<int, 2>{}); break;
+      case 3: launch(std::integral_constant<int, 3>{}); break;
+      case 4: launch(std::integral_constant<int, 4>{}); break;
+      default: DG_CHECK(false, "no k_sparseReduce instance of " << ps.count << " sources");
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1029,6 +1304,75 @@ void floatDecompressSparseAccumulate(StackDeviceMemory& res, const FloatDecompre
                     dispatchFloatType(config.floatType,
                                       [&](auto f) { sparseDecompressT<decltype(f)::value>(config, c); });
                   });
+}
+
+// The most sources one k_sparseReduce launch takes: the tuning hook of the
+// dense reduce (dietgpu_set_reduce_max_sources), capped at the largest instance.
+static uint32_t sparseReduceNsMax() {
+  const uint32_t hook = reduceMaxSources();
+  return hook >= 1 && hook < kSparseReduceMaxNS ? hook : kSparseReduceMaxNS;
+}
+
+uint64_t floatReduceSparseScratchBytes(FloatType floatType, uint32_t numInBatch, uint32_t numSources,
+                                       uint32_t maxCapacity) {
+  const int ft = int(floatType);
+  checkReduceShape(ft, numSources, false, ft, ft);
+  return planSparseReduce(floatWordBytes(ft), numInBatch, numSources, sparseReduceNsMax(), maxCapacity, true)
+      .scratchBytes;
+}
+
+// Fused sparse reduce: floatReduceArchives' checks, with
+// 16-byte aligned archives; every host check before the first allocation,
+// upload or launch.
+void floatReduceSparseArchives(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,
+                               uint32_t numSources, const void** in, const void** init, FloatType initType,
+                               void** out, const uint32_t* outCapacity, FloatType outType, uint8_t* outSuccess_dev,
+                               uint32_t* outSize_dev, hipStream_t stream) {
+  checkFloatConfig(config);
+  checkNoChecksum(config.useChecksum, PartialDecode::kReduce);
+  const int ft = int(config.floatType);
+  checkReduceShape(ft, numSources, init != nullptr, int(initType), int(outType));
+  checkProbBits(config.ansConfig.probBits);
+  const uint32_t nb = numInBatch, K = numSources;
+  if (nb == 0) return;
+  DG_CHECK(uint64_t(nb) * K < (1ull << 32), "numInBatch x numSources must be below 2^32");
+  DG_CHECK(in && out && outCapacity, "in, out and outCapacity must not be null");
+  const bool outF32 = outType == FloatType::kFloat32;
+  const uint32_t initKind = !init ? 0u : (initType == FloatType::kFloat32 ? 2u : 1u);
+  const auto ip = addressColumn(in, nb * K), op = addressColumn(out, nb);
+  const auto np = init ? addressColumn(init, nb) : std::vector<uint64_t>();
+  for (uint32_t i = 0; i < nb * K; ++i) checkArchiveAligned(ip[i], i, 16);
+  for (uint32_t i = 0; i < nb; ++i) {
+    DG_CHECK(op[i] % (outF32 ? 4 : 2) == 0, "float output " << i << " not aligned to its word size");
+    DG_CHECK(!init || np[i] % (initKind == 2 ? 4 : 2) == 0, "init " << i << " not aligned to its word size");
+  }
+  const SizeColumn cap(outCapacity, nb);
+  const SparseReducePlan plan =
+      planSparseReduce(floatWordBytes(ft), nb, K, sparseReduceNsMax(), cap.maxSize, init != nullptr);
+  DG_CHECK(plan.valid, "numSources (" << K << ") must be in 1 .. " << kReduceMaxSources);
+
+  // device columns (the sparse kernels take no InlineTable), then the fp32
+  // partial of a chained call: nb rows of the largest capacity
+  const DeviceTables t = uploadTables(res, stream, {&ip, &op, &np}, cap.sizes);
+  auto partial = res.alloc<float>(stream, size_t(plan.partialWords));
+  BatchDesc partD = BatchDesc::strided(partial.data(), plan.partialWords / nb * sizeof(float), 0);
+  partD.sizes = t.u32;
+  const SparseReduceCall c{res,
+                           stream,
+                           nb,
+                           plan,
+                           t.u64[0],
+                           BatchDesc::pointers(t.u64[2], nullptr),
+                           BatchDesc::pointers(t.u64[1], t.u32),
+                           partD,
+                           initKind,
+                           outF32,
+                           outSuccess_dev,
+                           outSize_dev};
+  dispatchFloatType(config.floatType, [&](auto f) {
+    constexpr int FT = decltype(f)::value;
+    if constexpr (FT <= 3) sparseReduceT<FT>(config, c);
+  });
 }
 
 // Every host check precedes the first allocation, upload or launch.

@@ -1,10 +1,11 @@
-// The host arithmetic of the three sparse drivers (sparse.hip sparseCompressT,
-// sparseDecompressT, sparseRangeT): tiles, chunks, rows, strides, grids and the
-// element counts of every allocation, and for a range call the member sort
-// and the packed host columns.  Host only and free of HIP headers, as
+// The host arithmetic of the four sparse drivers (sparse.hip sparseCompressT,
+// sparseDecompressT, sparseReduceT, sparseRangeT): tiles, chunks, rows, strides,
+// grids and the element counts of every allocation, for a reduce call its
+// passes and total scratch, and for a range call the member sort and the
+// packed host columns.  Host only and free of HIP headers, as
 // compress_plan.h and decode_plan.h are, so that it is stated once and swept
-// without a GPU (tests/test_sparse_plan.py).  The drivers allocate what a plan
-// names and launch; they compute nothing else.
+// without a GPU (tests/test_sparse_plan.py, tests/test_sparse_reduce_plan.py).
+// The drivers allocate what a plan names and launch; they compute nothing else.
 //
 // Sizes and capacities are combined in 32 bits where the drivers always did
 // (div32 / round32 below): a size within 4,095 words of 2^32 wraps.  No
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "compress_plan.h"
+#include "decode_plan.h"
 
 namespace dietgpu {
 
@@ -100,6 +102,60 @@ inline SparseDecodePlan planSparseDecode(uint32_t wordBytes, uint32_t nb, uint32
   p.listBytes = uint64_t(nb) * p.listStride;
   p.chunkPre = uint64_t(nb) * p.chunks;
   p.blockTot = uint64_t(nb) * p.cblocks;
+  return p;
+}
+
+// ---------------------------------------------------------------------------
+// fused reduce: nb members of K sparse archives each,
+// capacities at most maxCap, at most nsMax sources per k_sparseReduce launch
+// ---------------------------------------------------------------------------
+// The largest k_sparseReduce instance (sparse.hip static_asserts it).
+constexpr uint32_t kSparseReduceMaxNS = 4;
+
+struct SparseReducePlan {
+  bool valid = false;  // planReduce's: 1 <= K <= 64, nsMax >= 1
+  ReducePlan passes{};  // which sources go in which pass, which passes touch the fp32 partial
+  uint32_t ns = 0;      // sources of the widest pass (the first)
+  uint32_t rows = 0;    // ns * nb: the archives one pass counts, decodes and expands
+  // per pass: k_sparseChunks grid (d.cblocks, rows) in grid-y slices, one dense
+  // decode of `rows` lists (capacity d.denseCapacity), k_sparseReduce grid
+  // (d.gridX, nb) in grid-y slices
+  SparseDecodePlan d;
+  // element counts of the allocations; the per-pass ones are sized for the
+  // widest pass and reused by every pass (d.listBytes, d.chunkPre and
+  // d.blockTot count `rows` archives)
+  uint64_t tableBytes = 0;    // u8: the address columns in (K nb), out (nb), init (nb, if any), then the capacities
+  uint64_t partialWords = 0;  // fp32: nb rows of maxCap rounded up to 4 words; 0 for one pass
+  uint64_t densePtrs = 0;     // u64 [rows]
+  uint64_t sizes = 0;         // u32 [rows]
+  uint64_t denseOk = 0;       // u8 [rows]
+  uint64_t verdict = 0;       // u8 [2][nb]: the members still good after the even / odd passes
+  uint64_t firstN = 0;        // u32 [nb]: n of each member's first source
+  // the arena bytes of the whole call: every allocation above rounded up to
+  // the arena's 256-byte granule (an empty one takes a granule too)
+  uint64_t scratchBytes = 0;
+};
+
+inline SparseReducePlan planSparseReduce(uint32_t wordBytes, uint32_t nb, uint32_t K, uint32_t nsMax,
+                                         uint32_t maxCap, bool hasInit) {
+  SparseReducePlan p;
+  const uint64_t rowWords = uint64_t(splan::round32(maxCap, 4));
+  p.passes = planReduce(K, std::min(nsMax, kSparseReduceMaxNS), uint64_t(nb) * rowWords);
+  p.valid = p.passes.valid;
+  if (!p.valid) return p;
+  p.ns = p.passes.passes[0].count;
+  p.rows = p.ns * nb;
+  p.d = planSparseDecode(wordBytes, p.rows, maxCap);
+  p.tableBytes = (uint64_t(K) * nb + nb + (hasInit ? nb : 0)) * 8 + uint64_t(nb) * 4;
+  p.partialWords = p.passes.partialBytes / 4;
+  p.densePtrs = p.sizes = p.denseOk = p.rows;
+  p.verdict = 2 * uint64_t(nb);
+  p.firstN = nb;
+  auto granules = [](uint64_t bytes) { return std::max<uint64_t>((bytes + 255) / 256, 1) * 256; };
+  p.scratchBytes = granules(p.tableBytes) + granules(4 * p.partialWords) + granules(8 * p.densePtrs) +
+                   granules(4 * p.sizes) + granules(p.denseOk) + granules(p.d.listBytes) +
+                   granules(4 * p.d.chunkPre) + granules(4 * p.d.blockTot) + granules(p.verdict) +
+                   granules(4 * p.firstN);
   return p;
 }
 

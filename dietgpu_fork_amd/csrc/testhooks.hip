@@ -189,6 +189,22 @@ int dietgpu_test_reduce_config(dietgpu_stack* res, int float_type, int use_check
   });
 }
 
+int dietgpu_test_sparse_reduce_config(dietgpu_stack* res, int float_type, int use_checksum, uint32_t num_sources,
+                                      const void** in, const void* init, int init_type, void* out,
+                                      uint32_t out_capacity, int out_type, uint8_t* out_success_dev,
+                                      uint32_t* out_size_dev, void* stream) {
+  return guardedTest([&] {
+    using namespace dietgpu;
+    DG_CHECK(res && res->mem, "null dietgpu_stack");
+    DG_CHECK(float_type >= 1 && float_type <= 4, "float_type must be 1..4");
+    const FloatDecompressConfig cfg(FloatType(float_type), ANSCodecConfig(kANSDefaultProbBits), false,
+                                    use_checksum != 0);
+    floatReduceSparseArchives(*res->mem, cfg, 1, num_sources, in, init ? &init : nullptr, FloatType(init_type), &out,
+                              &out_capacity, FloatType(out_type), out_success_dev, out_size_dev,
+                              reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
 int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
                                uint32_t row_words, uint32_t num_idx, const void* idx_dev, void* out,
                                uint8_t* out_success_dev, void* stream) {

@@ -110,8 +110,8 @@ class GpuFloatCodec(_GpuCodec):
 
 class GpuSparseFloatCodec(_GpuCodec):
     """The sparse float codec on the local GPU (codec.sparse_compress /
-    sparse_decompress / sparse_decompress_accumulate: bitmap + the dense codec
-    on the nonzero words) for the compressed collectives, for tensors that are
+    sparse_decompress / sparse_decompress_accumulate / sparse_reduce: bitmap +
+    the dense codec on the nonzero words) for the compressed collectives, for tensors that are
     mostly exact zeros (MoE, embedding or pruned gradients).  Lossless like
     GpuFloatCodec, so the moving collectives return the same bits.
 
@@ -157,6 +157,36 @@ class GpuSparseFloatCodec(_GpuCodec):
         ft = self.info(archives[0])[1] if accs[0].dtype == torch.float32 else accs[0].dtype
         ok, _ = self._run(codec.sparse_decompress_accumulate, accs[0].device, archives, accs, ft=codec.FLOAT_TYPE[ft])
         self._raise_on_failure(ok)
+
+    def sparse_reduce(self, own, archives, out_dtype):
+        """This codec's fused reduction (_fused_entry).  Not named `reduce`:
+        that name promises GpuFloatCodec's sum, in which a peer's +0.0 is
+        added; here it is skipped, as in `accumulate`.
+        round_out_dtype of own.float() with the elements of `archives` added
+        in order, every add in float32 and only where the peer's word is
+        nonzero (accumulate's rule), in one fused call (k_sparseReduce;
+        codec.sparse_reduce): no accumulator between the peers.  own=None: the
+        sum starts as the first archive's element.  float16, bfloat16 and
+        float32; the same bits as the per-peer loop."""
+        from . import codec
+
+        device = archives[0].device
+        n = own.numel() if own is not None else self.info(archives[0])[0]
+        out = torch.empty(n, dtype=out_dtype, device=device)
+        ok, _ = self._run(codec.sparse_reduce, device, [[a] for a in archives], [out],
+                          inits=None if own is None else [own], ft=codec.FLOAT_TYPE[out_dtype])
+        self._raise_on_failure(ok)
+        return out
+
+    def reduce_fits(self, numel, dtype, num_archives):
+        """Whether one fused reduce of num_archives archives of numel words
+        takes its scratch from this codec's workspace (the plan's bytes,
+        codec.sparse_reduce_scratch_bytes): a call that does not would fall to
+        the arena's hipMalloc path every time."""
+        from . import codec
+
+        need = codec.sparse_reduce_scratch_bytes(codec.FLOAT_TYPE[dtype], 1, num_archives, numel)
+        return need <= max(int(self.workspace_bytes), 256)
 
     def info(self, archive):
         """(numel, dtype) of the element a sparse float archive encodes: numel
@@ -343,15 +373,29 @@ def _acc_dtype(dtype, acc_dtype):
 _FUSED_REDUCE_MAX = 64  # sources of one fused call (codec.REDUCE_MAX_SOURCES)
 
 
-def _fused_reduce(codec, dtype, acc_dtype, num_archives):
-    """The routing rule of reduce_archives: the fused kernel
-    takes the reduction when the codec has one (`reduce`), the adds are
-    float32 adds of float16, bfloat16 or float32 tensors, and there are 1 ..
-    64 archives; everything else (a codec without `reduce`, a 16-bit
-    accumulator that rounds at every add, float64) keeps the per-peer loop.
-    Both give the same bits."""
-    return (hasattr(codec, "reduce") and acc_dtype == torch.float32
-            and dtype in (torch.float16, torch.bfloat16, torch.float32) and 1 <= num_archives <= _FUSED_REDUCE_MAX)
+def _fused_entry(codec):
+    """The codec's fused reduction f(own, archives, out_dtype), or None: its
+    `reduce` (every peer's word added: GpuFloatCodec) or its `sparse_reduce`
+    (a peer's zero words skipped: GpuSparseFloatCodec)."""
+    return getattr(codec, "reduce", None) or getattr(codec, "sparse_reduce", None)
+
+
+def _fused_reduce(codec, dtype, acc_dtype, num_archives, numel=None):
+    """The routing rule of reduce_archives: the fused
+    kernel takes the reduction when the codec has one (_fused_entry), the adds
+    are float32 adds of float16, bfloat16 or float32 tensors, there are 1 ..
+    64 archives, and the call's scratch fits the codec's workspace
+    (codec.reduce_fits(numel, dtype, num_archives), where the codec has such a
+    bound: GpuSparseFloatCodec decodes the nonzero lists of one launch's
+    sources into its workspace; GpuFloatCodec has none, for it the clause is
+    always true).  Everything else (a codec without a fused reduction, a
+    16-bit accumulator that rounds at every add, float64, a shard too large
+    for the workspace) keeps the per-peer loop.  Both give the same bits."""
+    if not (_fused_entry(codec) is not None and acc_dtype == torch.float32
+            and dtype in (torch.float16, torch.bfloat16, torch.float32) and 1 <= num_archives <= _FUSED_REDUCE_MAX):
+        return False
+    fits = getattr(codec, "reduce_fits", None)
+    return fits is None or numel is None or bool(fits(numel, dtype, num_archives))
 
 
 def reduce_archives(own, archives, codec, acc_dtype=None):
@@ -364,8 +408,9 @@ def reduce_archives(own, archives, codec, acc_dtype=None):
     every add correctly rounded in acc_dtype (default: float32 for float16 /
     bfloat16 tensors, else the tensors' dtype) and the result rounded once to
     the tensors' dtype.  With float32 adds and a codec that has a fused
-    `reduce` (GpuFloatCodec) the whole sum is one codec.reduce call, the
-    running sum in registers (_fused_reduce states the rule); otherwise one
+    reduction (GpuFloatCodec.reduce; GpuSparseFloatCodec.sparse_reduce while
+    the call's scratch fits its workspace) the whole sum is one call of it,
+    the running sum in registers (_fused_reduce states the rule); otherwise one
     codec.accumulate call per peer.  No decoded temporary either way, and the
     same bits.  The accumulator starts as `own` converted to acc_dtype, not as
     +0.0: with no archives the result is `own` bit for bit (-0.0 included).
@@ -377,10 +422,11 @@ def reduce_archives(own, archives, codec, acc_dtype=None):
     a running sum of -0.0 stays -0.0 where a peer holds +0.0."""
     if own is None and not archives:
         raise ValueError("reduce_archives: nothing to reduce")
-    dtype = own.dtype if own is not None else getattr(codec, "info", _archive_info)(archives[0])[1]
-    if _fused_reduce(codec, dtype, _acc_dtype(dtype, acc_dtype), len(archives)):
+    numel, dtype = ((own.numel(), own.dtype) if own is not None
+                    else getattr(codec, "info", _archive_info)(archives[0]))
+    if _fused_reduce(codec, dtype, _acc_dtype(dtype, acc_dtype), len(archives), numel):
         flat = None if own is None else own.contiguous().view(-1)
-        return codec.reduce(flat, archives, dtype)
+        return _fused_entry(codec)(flat, archives, dtype)
     if own is None:
         n, dtype = getattr(codec, "info", _archive_info)(archives[0])
         own = torch.empty(n, dtype=dtype, device=archives[0].device)

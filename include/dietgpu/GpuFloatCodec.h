@@ -245,6 +245,57 @@ void floatDecompressSparseAccumulate(StackDeviceMemory& res,
                                      FloatType accType, uint8_t* outSuccess_dev,
                                      uint32_t* outSize_dev, hipStream_t stream);
 
+// Fused sparse reduce: floatReduceArchives for sparse float archives.  For
+// member b, the numSources sparse archives x_1 .. x_K = in[k * numInBatch + b]
+// (source-major), each of n words, and 0 <= i < n:
+//   a = float(init[b][i]);
+//   for k = 1 .. K in source order: if bit i of x_k's bitmap is set (the word
+//     is not +0.0 bitwise, so -0.0 is added), a = a + float(x_k[i]), one
+//     correctly rounded fp32 add with denormals kept; if it is clear, a keeps
+//     its bits;
+//   out[b][i] = a rounded to nearest even to outType (not rounded for kFloat32).
+// A clear bit is skipped, never added as +0.0 (floatDecompressSparseAccumulate's
+// rule): an init word of -0.0 or a signalling NaN under clear bits comes out
+// with its bits.  init may be null: the sum then starts as a = float(x_1[i]),
+// the decoded word (+0.0 where its bit is clear, the element's -0.0 where it
+// holds one), and runs over x_2 .. x_K; K = 1 returns the decoded element.
+// The result equals, bit for bit, own.to(fp32), one
+// floatDecompressSparseAccumulate per archive in order, and one rounding; a
+// NaN result is some NaN.  One kernel pass over all K archives with the
+// running sum in registers (K above the kernel's source limit: chained passes
+// through an fp32 partial taken from `res`; the split never changes the order
+// or the bits).  config.floatType is kFloat16, kBFloat16 or kFloat32; initType
+// and outType are config.floatType or kFloat32; numSources in 1 .. 64;
+// anything else throws.  out[b] may be init[b] itself when the types agree;
+// any other overlap is undefined and not checked.  in[.] 16-byte aligned,
+// init[b] / out[b] aligned to their words, outCapacity[b] in out words.
+// outSuccess_dev[b] = 1 iff the dense parts of all K archives are valid for
+// this config, all K sparse headers hold the same n, and outCapacity[b] >= n;
+// outSize_dev[b] = n of the first source always (it comes from the sparse
+// header).  A member fails as a whole: its out and init are not written and,
+// in a call of one pass, not read (a chained call learns of a bad later source
+// only in that source's pass; the earlier passes have read init into the
+// partial), and nothing outside out[b][0 .. n) ever is written.
+// config.useChecksum must be false, for
+// floatDecompressAccumulate's reason (archives written with a checksum reduce
+// normally).  No host synchronisation, no allocation outside `res`: the call
+// can be captured in a graph and replayed on new archive bytes.
+void floatReduceSparseArchives(StackDeviceMemory& res,
+                               const FloatDecompressConfig& config,
+                               uint32_t numInBatch, uint32_t numSources,
+                               const void** in, const void** init,
+                               FloatType initType, void** out,
+                               const uint32_t* outCapacity, FloatType outType,
+                               uint8_t* outSuccess_dev, uint32_t* outSize_dev,
+                               hipStream_t stream);
+
+// The bytes of `res` that a floatReduceSparseArchives call of numInBatch
+// members, numSources sources and capacities of at most maxCapacity words
+// takes at most (with an init; the scratch is bounded by the sources of one
+// kernel launch, not by numSources).  Host only: no device is touched.
+uint64_t floatReduceSparseScratchBytes(FloatType floatType, uint32_t numInBatch,
+                                       uint32_t numSources, uint32_t maxCapacity);
+
 // Row gather with device-resident indices from a dense float archive that
 // holds a table [R, rowWords] (see ansGatherRows, GpuANSCodec.h: the same
 // rules, in float words; out_dev word-aligned).  Sparse archives are not

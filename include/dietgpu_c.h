@@ -235,6 +235,26 @@ int dietgpu_float_decompress_sparse_accumulate(dietgpu_stack* res, int float_typ
                                                uint8_t* out_success_dev, uint32_t* out_size_dev,
                                                void* stream);
 
+/* Fused reduce of sparse float archives (floatReduceSparseArchives,
+ * GpuFloatCodec.h; in[.] 16-byte aligned): dietgpu_float_reduce's arguments.
+ * a = float(init[b][i]); for every source k in order whose bitmap bit i is
+ * set (its word is not +0.0 bitwise), a = a + float(x_k[i]) in fp32; a clear
+ * bit is skipped, never added as +0.0, so an init word of -0.0 under clear
+ * bits stays -0.0; out[b][i] = round(a).  init may be null: the sum starts as
+ * the decoded word x_1[i] and runs over x_2 .. x_K.  A member succeeds iff
+ * all its archives' dense parts are valid, all sparse headers hold the same n
+ * and out_capacity[b] >= n; out_size_dev[b] = n of the first source always. */
+int dietgpu_float_reduce_sparse(dietgpu_stack* res, int float_type, int prob_bits, uint32_t num_in_batch,
+                                uint32_t num_sources, const void** in, const void** init, int init_type,
+                                void** out, const uint32_t* out_capacity, int out_type,
+                                uint8_t* out_success_dev, uint32_t* out_size_dev, void* stream);
+/* The bytes of the stack that such a call takes at most, for capacities of at
+ * most max_capacity words (host only; 0 for arguments the call would refuse:
+ * see dietgpu_last_error).  The scratch is bounded by the sources of one
+ * kernel launch (dietgpu_set_reduce_max_sources), not by num_sources. */
+uint64_t dietgpu_float_reduce_sparse_scratch_bytes(int float_type, uint32_t num_in_batch, uint32_t num_sources,
+                                                   uint32_t max_capacity);
+
 /* Row gather with device-resident indices (ansGatherRows / floatGatherRows,
  * GpuANSCodec.h): the archive holds a table [R, row_words]; idx_dev holds
  * num_idx row indices in device memory, int32 or (idx_is_64 != 0) int64.
@@ -255,7 +275,8 @@ int dietgpu_float_gather_rows(dietgpu_stack* res, int float_type, int prob_bits,
 
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "hist", "coalesce", "sparse", "sparse_accumulate") is bracketed
+ * "decode_gather", "hist", "coalesce", "sparse", "sparse_accumulate",
+ * "sparse_reduce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);
@@ -311,7 +332,8 @@ void dietgpu_set_compress_path(int mode);
 /* Test / tuning hook: the most sources one launch of the fused reduce's kernel
  * takes; a call with more chains passes through an fp32 partial.  0 (default)
  * and anything above the largest kernel instance (4) mean that instance.
- * Results are the same bits whatever the value. */
+ * The fused sparse reduce's kernel obeys the same cap.  Results are the same
+ * bits whatever the value. */
 void dietgpu_set_reduce_max_sources(uint32_t sources);
 
 #ifdef __cplusplus

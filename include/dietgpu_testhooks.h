@@ -73,6 +73,16 @@ int dietgpu_test_reduce_config(dietgpu_stack* res, int float_type, int use_check
                                const void** in, void* out, uint32_t out_capacity, uint8_t* out_success_dev,
                                uint32_t* out_size_dev, void* stream);
 
+/* Calls floatReduceSparseArchives for one member of num_sources sparse
+ * archives `in` with `use_checksum` set in its config and any init / out types
+ * (FloatType values; the C ABI refuses bad types itself and carries no
+ * checksum flag); init may be null.  DIETGPU_ERR_INVALID when the entry point
+ * throws, DIETGPU_OK after a reduce. */
+int dietgpu_test_sparse_reduce_config(dietgpu_stack* res, int float_type, int use_checksum, uint32_t num_sources,
+                                      const void** in, const void* init, int init_type, void* out,
+                                      uint32_t out_capacity, int out_type, uint8_t* out_success_dev,
+                                      uint32_t* out_size_dev, void* stream);
+
 /* The same for the row gather's C++ entry points (floatGatherRows,
  * ansGatherRows; float_type 0 = the byte codec): num_idx int64 indices at
  * idx_dev, rows of row_words words at a stride of row_words. */
