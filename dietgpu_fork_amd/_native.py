@@ -89,6 +89,8 @@ def _declare(L):
         "dietgpu_float_reduce_sparse_scratch_bytes": (c_u64, [c_int, c_u32, c_u32, c_u32]),
         "dietgpu_ans_gather_rows": (c_int, [vp, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_float_gather_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
+        "dietgpu_float_gather_rows_sum": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, c_u32, P, P, c_int, P, c_int,
+                                                  c_u64, P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),
@@ -131,6 +133,8 @@ def testlib():
                "dietgpu_test_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
+               "dietgpu_test_gather_sum_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, c_u32, P, P, P, c_int, P,
+                                                          P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
                "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
                "dietgpu_test_sparse_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_int, P, c_u32, c_int, P,

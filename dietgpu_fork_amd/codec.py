@@ -539,6 +539,69 @@ def gather_rows_device(archive, row_words, idx, dtype, out=None, out_status=None
     return out, ok
 
 
+def gather_rows_sum(archive, row_words, idx, offsets, dtype, out=None, out_dtype=None, out_status=None,
+                    prob_bits=10, ws=None, check=False):
+    """embedding_bag(mode="sum") on a [R, row_words] table stored as one dense
+    float16 / bfloat16 / float32 archive of `dtype` -> (out, ok).  Bag b is
+    idx[offsets[b] : offsets[b + 1]] (offsets holds B + 1 boundaries; idx and
+    offsets are contiguous 1-d CUDA tensors, both int32 or both int64) and
+    out[b] the sum of the bag's rows: fp32 adds in list order, started from
+    the first row (a one-row bag returns the row, -0.0 included), rounded once
+    to out_dtype, which is `dtype` (the default) or torch.float32.  An empty
+    bag gives a row of +0.0.  ok[b] = 1 where the bag's offsets are ordered and
+    inside idx, all its rows lie inside the table and the archive matches
+    dtype / prob_bits; 0 where not, and such a row of `out` is untouched.  One
+    kernel launch on the current stream: nothing is uploaded or read back, so
+    the call can be captured in a graph and replayed on new indices, offsets
+    and archive bytes, and the result is the same bits on every run.  A
+    caller's `out` [B, row_words] may have its rows at a stride.  check=True
+    reads ok back and raises DietGpuError on any failing bag.  Not offered:
+    mean / max pooling, per-sample weights, sparse archives, float64."""
+    who = "gather_rows_sum"
+    for name, t in (("idx", idx), ("offsets", offsets)):
+        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64) and t.dim() == 1
+                and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous 1-d int32 or int64 tensor")
+    if idx.dtype != offsets.dtype:
+        raise ValueError(f"{who}: idx and offsets must share a dtype, not {idx.dtype} and {offsets.dtype}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{who}: offsets must hold B + 1 >= 1 entries")
+    if dtype == torch.uint8:
+        raise ValueError(f"{who}: byte archives hold no floats to sum")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16, bfloat16 or float32 archives)")
+    out_dtype = out_dtype if out_dtype is not None else (out.dtype if out is not None else dtype)
+    if out_dtype not in (dtype, torch.float32):
+        raise ValueError(f"{who}: out dtype {out_dtype} does not go with {dtype} archives (their own dtype, or "
+                         "torch.float32)")
+    row_words = int(row_words)
+    if row_words < 1:
+        raise ValueError(f"{who}: row_words must be at least 1")
+    if not (idx.is_cuda and offsets.is_cuda and idx.device == offsets.device):
+        raise ValueError(f"{who}: idx and offsets must be CUDA tensors on one device")
+    bags = offsets.numel() - 1
+    shape = [bags, row_words]
+    out = out if out is not None else torch.empty(shape, dtype=out_dtype, device=idx.device)
+    if list(out.shape) != shape or out.dtype != out_dtype or out.device != idx.device:
+        raise ValueError(f"{who}: out must be a {out_dtype} tensor of shape {shape} on idx's device")
+    stride = _row_stride(out, row_words)
+    if stride is None or stride < row_words:
+        raise ValueError(f"{who}: out's last dimension must be contiguous and its rows must lie at a constant "
+                         "stride of at least row_words")
+    ok = out_status if out_status is not None else torch.empty([bags], dtype=torch.uint8, device=idx.device)
+    if not (ok.dtype == torch.uint8 and ok.is_contiguous() and list(ok.shape) == [bags] and ok.device == idx.device):
+        raise ValueError(f"{who}: out_status must be a contiguous uint8 tensor of {bags} entries")
+    ws = _ws(ws, idx.device)
+    N.check(N.lib().dietgpu_float_gather_rows_sum(
+        ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, bags, idx.numel(), idx.data_ptr(),
+        offsets.data_ptr(), int(idx.dtype == torch.int64), out.data_ptr(), int(out_dtype == torch.float32), stride,
+        ok.data_ptr(), _s()))
+    if check and not bool(ok.all()):
+        raise N.DietGpuError(f"{who}: a bag's offsets or rows lie outside idx or the table, or the archive does "
+                             "not match dtype / prob_bits")
+    return out, ok
+
+
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
     return _pointer_compress(N.lib().dietgpu_float_compress_sparse, (ft, prob_bits, int(checksum)), ts,

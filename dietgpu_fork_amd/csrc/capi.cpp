@@ -411,6 +411,22 @@ int dietgpu_float_gather_rows(dietgpu_stack* res, int ft, int pb, const void* ar
   });
 }
 
+int dietgpu_float_gather_rows_sum(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
+                                  uint32_t num_bags, uint32_t num_idx, const void* idx_dev, const void* offsets_dev,
+                                  int idx_is_64, void* out_dev, int out_is_fp32, uint64_t out_row_stride,
+                                  uint8_t* succ, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at; floatGatherRowsSum makes
+    // these checks for C++ callers, after R(res) has looked at the stack)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkProbBits(pb);
+    checkGatherSumShape(ft, out_is_fp32 != 0, row_words, out_row_stride);
+    floatGatherRowsSum(R(res), cfg, archive_dev, row_words, num_bags, num_idx, idx_dev, offsets_dev, idx_is_64 != 0,
+                       out_dev, out_is_fp32 != 0, out_row_stride, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

@@ -25,6 +25,7 @@
 #include "pcompress.h"
 #include "decode.h"
 #include "gather.h"
+#include "gather_sum.h"
 #include "encode.h"
 #include "profile.h"
 
@@ -433,6 +434,39 @@ void gatherRowsDevice(int pb, const void* archive_dev, uint32_t rowWords, uint32
   HIP_LAUNCH_CHECK();
 }
 
+// A pooled row gather (k_gatherSum, gather_sum.h): bag b =
+// idx_dev[offsets_dev[b] .. offsets_dev[b + 1]) of the [R, rowWords] table that
+// the archive holds, summed in fp32 into out row b.  One launch of a persistent
+// grid (planGatherSum, decode_plan.h); as gatherRowsDevice, nothing is
+// uploaded, allocated or read back, and the argument checks come before the
+// device is touched.
+template <int FT, bool OUT32>
+void gatherRowsSumDevice(int pb, const void* archive_dev, uint32_t rowWords, uint32_t numBags, uint32_t numIdx,
+                         const void* idx_dev, const void* offsets_dev, bool idxIs64, void* out_dev,
+                         uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t s) {
+  // (probability bits, types and the row shape: floatGatherRowsSum's checks)
+  const GatherSumPlan bound = planGatherSum(numBags, rowWords, 1);
+  DG_CHECK(bound.valid, "too many bags: numBags (" << numBags << ") times the " << bound.tiles
+                                                   << " column tiles of a row of " << rowWords
+                                                   << " words must be below 2^32");
+  if (numBags == 0) return;
+  DG_CHECK(archive_dev && offsets_dev && out_dev && (idx_dev || numIdx == 0),
+           "archive_dev, idx_dev, offsets_dev and out_dev must not be null");
+  checkArchiveAligned(reinterpret_cast<uintptr_t>(archive_dev), 0, 4);
+  const uintptr_t ib = idxIs64 ? 8 : 4;
+  DG_CHECK(reinterpret_cast<uintptr_t>(idx_dev) % ib == 0 && reinterpret_cast<uintptr_t>(offsets_dev) % ib == 0,
+           "idx_dev / offsets_dev not aligned to their index size");
+  DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % (OUT32 ? 4 : 2) == 0, "out_dev not aligned to its word size");
+  const uint32_t lds = DecCfg<FT>::ldsBytes(pb);
+  const uint32_t slots = residentSlots(reinterpret_cast<const void*>(&k_gatherSum<FT, OUT32>), dec::kThreads, lds);
+  const GatherSumPlan plan = planGatherSum(numBags, rowWords, slots);
+  prof::Scope p("decode_gather_sum", s);
+  k_gatherSum<FT, OUT32><<<plan.gridX, dec::kThreads, lds, s>>>(
+      static_cast<const uint8_t*>(archive_dev), idx_dev, offsets_dev, idxIs64 ? 1u : 0u, numBags, numIdx, rowWords,
+      plan.tiles, static_cast<uint8_t*>(out_dev), outRowStrideWords, pb, outSuccess_dev);
+  HIP_LAUNCH_CHECK();
+}
+
 // Verify stored checksums against `unitBytes * out.size(b)` decoded bytes
 // (ansDecodeBatch :557-591 / floatDecompressDevice :1077-1112; the float
 // codec checksums `capacity` bytes, float words treated as bytes).  Host sync.
@@ -794,6 +828,33 @@ void floatGatherRows(StackDeviceMemory& res, const FloatDecompressConfig& config
     gatherRowsDevice<decltype(ft)::value>(config.ansConfig.probBits, archive_dev, rowWords, numIdx, idx_dev, idxIs64,
                                           out_dev, outRowStrideWords, outSuccess_dev, stream);
   });
+}
+
+void floatGatherRowsSum(StackDeviceMemory& res, const FloatDecompressConfig& config, const void* archive_dev,
+                        uint32_t rowWords, uint32_t numBags, uint32_t numIdx, const void* idx_dev,
+                        const void* offsets_dev, bool idxIs64, void* out_dev, bool outIsFp32,
+                        uint64_t outRowStrideWords, uint8_t* outSuccess_dev, hipStream_t stream) {
+  checkFloatConfig(config);
+  checkNoChecksum(config.useChecksum, PartialDecode::kGatherSum);
+  checkProbBits(config.ansConfig.probBits);
+  checkGatherSumShape(int(config.floatType), outIsFp32, rowWords, outRowStrideWords);
+  (void)res;  // nothing is allocated: the call can be captured in a graph
+  const int pb = config.ansConfig.probBits;
+  auto run = [&](auto ft, auto out32) {
+    gatherRowsSumDevice<decltype(ft)::value, decltype(out32)::value>(pb, archive_dev, rowWords, numBags, numIdx,
+                                                                     idx_dev, offsets_dev, idxIs64, out_dev,
+                                                                     outRowStrideWords, outSuccess_dev, stream);
+  };
+  constexpr std::true_type f32;
+  constexpr std::false_type own;
+  switch (config.floatType) {
+    case FloatType::kFloat16:
+      return outIsFp32 ? run(std::integral_constant<int, 1>{}, f32) : run(std::integral_constant<int, 1>{}, own);
+    case FloatType::kBFloat16:
+      return outIsFp32 ? run(std::integral_constant<int, 2>{}, f32) : run(std::integral_constant<int, 2>{}, own);
+    default:
+      return run(std::integral_constant<int, 3>{}, f32);
+  }
 }
 
 void floatDecompressAccumulate(StackDeviceMemory& res, const FloatDecompressConfig& config, uint32_t numInBatch,

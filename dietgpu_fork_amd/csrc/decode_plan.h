@@ -3,7 +3,8 @@
 // their waves run with remaining-work priorities.  Host only and free of HIP
 // headers, so that the rule -- performance policy, DESIGN.md 5.2 -- is stated
 // once and tested without a GPU (tests/test_decode_plan.py).  Below it the
-// grid rule of k_gather (gather.h; tests/test_gather_plan.py) and the pass and
+// grid rule of k_gather (gather.h; tests/test_gather_plan.py), that of
+// k_gatherSum (gather_sum.h; tests/test_gather_sum_plan.py) and the pass and
 // grid rules of k_reduce (reduce.h; tests/test_reduce_plan.py).
 #pragma once
 
@@ -92,6 +93,35 @@ inline GatherPlan planGather(uint32_t numIdx, uint32_t rowWords, uint32_t slots)
   if (tasks >= (1ull << 32)) return {false, K, 0, 0};
   const uint32_t groups = uint32_t((tasks + kGatherTasksPerWG - 1) / kGatherTasksPerWG);
   return {true, K, groups, std::min(std::max(1u, slots), groups)};
+}
+
+// The grid rule of k_gatherSum (gather_sum.h, DESIGN.md 5.2i;
+// tests/test_gather_sum_plan.py): numBags bags of rows of rowWords words, each
+// summed into one output row.  A task is a (bag, column tile) pair; a
+// half-wave keeps a tile's running sum in registers, a column per lane and
+// register, so the tile is 32 lanes x 4 registers wide and a wider row becomes
+// several tasks (each decodes the row's blocks again).  4 registers, not 8:
+// at 256 columns the kernel took 78 VGPRs, 6 workgroups per CU; at 128 it
+// takes 60 and keeps k_decode's 8.
+constexpr uint32_t kGatherSumTile = 128;
+
+struct GatherSumPlan {
+  bool valid;          // rowWords >= 1 and numBags * tiles < 2^32
+  uint32_t tileWords;  // kGatherSumTile
+  uint32_t tiles;      // column tiles (tasks) per bag
+  uint64_t tasks;      // numBags * tiles
+  uint32_t groups;     // task groups (of kGatherTasksPerWG tasks)
+  uint32_t gridX;      // persistent workgroups; 0: nothing to launch
+};
+
+// slots: as planGather's.
+inline GatherSumPlan planGatherSum(uint32_t numBags, uint32_t rowWords, uint32_t slots) {
+  if (rowWords == 0) return {false, kGatherSumTile, 0, 0, 0, 0};
+  const uint32_t tiles = uint32_t((uint64_t(rowWords) + kGatherSumTile - 1) / kGatherSumTile);
+  const uint64_t tasks = uint64_t(numBags) * tiles;
+  if (tasks >= (1ull << 32)) return {false, kGatherSumTile, tiles, tasks, 0, 0};
+  const uint32_t groups = uint32_t((tasks + kGatherTasksPerWG - 1) / kGatherTasksPerWG);
+  return {true, kGatherSumTile, tiles, tasks, groups, std::min(std::max(1u, slots), groups)};
 }
 
 // The pass rule of the fused reduce (k_reduce, reduce.h; DESIGN.md 5.2g;

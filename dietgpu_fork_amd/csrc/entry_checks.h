@@ -24,7 +24,7 @@ inline void checkFloatConfig(const FloatCodecConfig& c) {
 
 // The forms that decode part of an element, or add it to something: none can
 // verify the archive's checksum, and a config that asks for it is refused.
-enum class PartialDecode { kRange, kGather, kAccumulate, kReduce };
+enum class PartialDecode { kRange, kGather, kAccumulate, kReduce, kGatherSum };
 
 inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
   switch (what) {
@@ -41,6 +41,9 @@ inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
       break;
     case PartialDecode::kReduce:
       DG_CHECK(!useChecksum, "a fused reduce cannot verify a checksum (the decoded words are never stored)");
+      break;
+    case PartialDecode::kGatherSum:
+      DG_CHECK(!useChecksum, "a pooled row gather cannot verify a checksum (the decoded words are never stored)");
       break;
   }
 }
@@ -87,6 +90,16 @@ inline void checkGatherRows(uint32_t rowWords, uint64_t outRowStrideWords) {
   DG_CHECK(rowWords >= 1, "rowWords must be at least 1");
   DG_CHECK(outRowStrideWords >= rowWords,
            "outRowStrideWords (" << outRowStrideWords << ") must be at least rowWords (" << rowWords << ")");
+}
+
+// The pooled row gather (floatGatherRowsSum; float types as FloatType's
+// values): fp16, bf16 and fp32 archives, an out of the archive's type or fp32.
+// The C ABI makes the same checks before it looks at the stack or any pointer.
+inline void checkGatherSumShape(int floatType, bool outIsFp32, uint32_t rowWords, uint64_t outRowStrideWords) {
+  DG_CHECK(floatType >= 1 && floatType <= 3,
+           "a pooled row gather takes fp16, bf16 or fp32 archives (float type 1..3), not " << floatType);
+  DG_CHECK(outIsFp32 || floatType != 3, "the pooled rows of an fp32 archive are fp32 (outIsFp32 must be set)");
+  checkGatherRows(rowWords, outRowStrideWords);
 }
 
 }  // namespace dietgpu

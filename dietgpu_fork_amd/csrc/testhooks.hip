@@ -224,6 +224,21 @@ int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_check
   });
 }
 
+int dietgpu_test_gather_sum_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                   uint32_t row_words, uint32_t num_bags, uint32_t num_idx, const void* idx_dev,
+                                   const void* offsets_dev, void* out, int out_is_fp32, uint8_t* out_success_dev,
+                                   void* stream) {
+  return guardedTest([&] {
+    using namespace dietgpu;
+    DG_CHECK(res && res->mem, "null dietgpu_stack");
+    DG_CHECK(float_type >= 1 && float_type <= 4, "float_type must be 1..4");
+    const FloatDecompressConfig cfg(FloatType(float_type), ANSCodecConfig(kANSDefaultProbBits), false,
+                                    use_checksum != 0);
+    floatGatherRowsSum(*res->mem, cfg, in, row_words, num_bags, num_idx, idx_dev, offsets_dev, true, out,
+                       out_is_fp32 != 0, row_words, out_success_dev, reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
 int dietgpu_test_compress_plan(int float_type, uint32_t nb, uint32_t max_size, int checksum, int user_hist,
                                int aligned16, dietgpu_test_plan* out) {
   return guardedTest([&] {

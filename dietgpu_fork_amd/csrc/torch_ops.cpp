@@ -22,7 +22,8 @@
 //   decompress_data_accumulate        ext   floatDecompressAccumulate (*)
 //   gather_rows                       ext   floatGatherRows / ansGatherRows
 //   reduce_data                       ext   floatReduceArchives (*)
-//   (*) after floatGetCompressedInfo on ts_in[0] where only float32 tensors
+//   gather_rows_sum                   ext   floatGatherRowsSum (*)
+//   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
 // An operator builds one CallContext (device guard, stream, arena over
@@ -707,6 +708,58 @@ int64_t gather_rows(bool asFloat, const at::Tensor& tIn, int64_t rowWords, const
   return cx.used();
 }
 
+// Extension (no reference counterpart): embedding_bag(mode="sum") on a
+// compressed table (floatGatherRowsSum).  Bag b is t_idx[t_offsets[b] ..
+// t_offsets[b + 1]) (t_offsets holds B + 1 boundaries; both tensors int32 or
+// both int64, on the archive's device) and t_out [B, row_words] row b the fp32
+// sum of the bag's rows in list order, started from the first row and rounded
+// once to t_out's dtype; an empty bag gives +0.0.  float16 / bfloat16 outputs
+// name the archive's type themselves; for float32 outputs peekArchiveType
+// reads it (fp32, or fp16 / bf16 summed into fp32), which synchronises the
+// stream once.  out_status[b] = 1 iff the archive is valid, the bag's offsets
+// are ordered and inside t_idx and all its rows lie inside the element; a
+// failing bag's row is left untouched.  t_out's rows may lie at a stride.  The
+// checks that need no device come first.
+int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx, const at::Tensor& tOffsets,
+                        const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
+                        const std::optional<at::Tensor>& status) {
+  TORCH_CHECK(rowWords >= 1 && uint64_t(rowWords) <= kU32Max, "row_words must be at least 1 (and below 2^32), not ",
+              rowWords);
+  TORCH_CHECK(tIdx.scalar_type() == at::kInt || tIdx.scalar_type() == at::kLong, "t_idx must be int32 or int64, not ",
+              tIdx.scalar_type());
+  TORCH_CHECK(tOffsets.scalar_type() == tIdx.scalar_type(), "t_offsets must have t_idx's dtype (", tIdx.scalar_type(),
+              "), not ", tOffsets.scalar_type());
+  TORCH_CHECK(tIdx.dim() == 1 && tOffsets.dim() == 1 && tOffsets.numel() >= 1,
+              "t_idx and t_offsets must be 1-d, t_offsets with B + 1 >= 1 entries");
+  checkDtype(tOut, tOut.scalar_type(), {false, "t_out", "t_out"});
+  const int64_t bags = tOffsets.numel() - 1;
+  TORCH_CHECK(tOut.dim() == 2 && tOut.size(0) == bags && tOut.size(1) == rowWords,
+              "t_out must have the shape [t_offsets.numel() - 1, row_words] = [", bags, ", ", rowWords, "], not ",
+              tOut.sizes());
+  TORCH_CHECK(rowWords == 1 || tOut.stride(1) == 1, "t_out's last dimension must be contiguous");
+  const int64_t rowStride = bags > 1 ? tOut.stride(0) : rowWords;
+  TORCH_CHECK(rowStride >= rowWords, "t_out's rows must not overlap (row stride ", rowStride, " < row_words)");
+  TORCH_CHECK(uint64_t(tIdx.numel()) <= kU32Max && uint64_t(bags) <= kU32Max, "too many indices or bags");
+  TORCH_CHECK(tOffsets.device().type() == at::kCUDA && tOffsets.is_contiguous() &&
+                  tIdx.device().type() == at::kCUDA && tIdx.is_contiguous() &&
+                  tIdx.get_device() == tOffsets.get_device(),
+              "t_idx and t_offsets must be contiguous GPU tensors (on the archive's device)");
+  const int dev = tOffsets.get_device();
+  CallContext cx(dev);
+  Members m(dev, 1, 0);
+  m.archive(tIn);
+  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
+  const auto st = statusPointers(status, std::nullopt, bags, dev).first;
+  cx.stack(tempMem);
+  const FloatType outType = floatTypeOf(tOut.scalar_type());
+  FloatType ft = outType;
+  if (ft == FloatType::kFloat32) ft = peekArchiveType(cx, m, tIn, "gather_rows_sum takes");
+  floatGatherRowsSum(*cx.res, floatConfig(ft, false), tIn.data_ptr(), uint32_t(rowWords), uint32_t(bags),
+                     uint32_t(tIdx.numel()), tIdx.data_ptr(), tOffsets.data_ptr(), tIdx.scalar_type() == at::kLong,
+                     tOut.data_ptr(), outType == FloatType::kFloat32, uint64_t(rowStride), st, cx.stream);
+  return cx.used();
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -817,6 +870,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "reduce_data(Tensor[] ts_in, int num_sources, Tensor[] ts_out, Tensor[]? ts_init=None, Tensor? temp_mem=None, "
       "Tensor? out_status=None, Tensor? out_sizes=None) -> int");
+  m.def(
+      "gather_rows_sum(Tensor t_in, int row_words, Tensor t_idx, Tensor t_offsets, Tensor t_out, Tensor? "
+      "temp_mem=None, Tensor? out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -834,4 +890,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("decompress_data_accumulate", &dietgpu::decompress_data_accumulate);
   m.impl("gather_rows", &dietgpu::gather_rows);
   m.impl("reduce_data", &dietgpu::reduce_data);
+  m.impl("gather_rows_sum", &dietgpu::gather_rows_sum);
 }

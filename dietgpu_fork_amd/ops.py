@@ -23,6 +23,7 @@ validation and return values; "ext": not in the reference.
     decompress_data_accumulate        ext   OPS         adds each archive's element to an accumulator
     gather_rows                       ext   MORE_OPS    rows of a table held by one archive, by device indices
     reduce_data                       ext   REDUCE_OPS  sums several archives per member in one kernel
+    gather_rows_sum                   ext   POOL_OPS    sums bags of rows of a table held by one archive
 """
 import os
 
@@ -56,6 +57,10 @@ MORE_OPS = ("gather_rows",)
 # kernel (the fused reduce of the reducing collectives)
 REDUCE_OPS = ("reduce_data",)
 
+# gather_rows_sum sums bags of rows of a table held by one archive in one
+# kernel: embedding_bag(mode="sum") on a compressed table
+POOL_OPS = ("gather_rows_sum",)
+
 _LOADED = False
 
 
@@ -74,7 +79,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS or name in MORE_OPS or name in REDUCE_OPS:
+    if name in OPS or name in MORE_OPS or name in REDUCE_OPS or name in POOL_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

@@ -307,4 +307,33 @@ void floatGatherRows(StackDeviceMemory& res,
                      uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
                      hipStream_t stream);
 
+// Pooled row gather (embedding_bag(mode="sum") on a compressed table): the
+// dense fp16 / bf16 / fp32 archive holds a table [R, rowWords]; idx_dev holds
+// numIdx row indices and offsets_dev numBags + 1 bag boundaries in device
+// memory, both int32 or (idxIs64) both int64.  Bag b is
+// idx[offsets[b] .. offsets[b + 1]), and for 0 <= j < rowWords
+//   out[b * outRowStrideWords + j] =
+//       round_out((..(f(x_1[j]) + f(x_2[j])) + ..) + f(x_m[j]))
+// with x_t the row named by the bag's t-th index, f the exact conversion to
+// fp32, every add a correctly rounded fp32 add in list order, the running sum
+// started as f(x_1) (a one-row bag returns the row, -0.0 included) and one
+// rounding to the output type: fp32 when outIsFp32 (always for fp32
+// archives), else the archive's 16-bit type.  An empty bag gives a row of
+// +0.0.  outSuccess_dev[b] (optional) = 1 iff the archive is valid for this
+// config, 0 <= offsets[b] <= offsets[b + 1] <= numIdx and every index of the
+// bag lies in [0, n / rowWords); a failing bag's row is untouched, and nothing
+// but the rowWords words of succeeding bags is written.  One launch, no host
+// synchronisation, no allocation, no atomics: the call can be captured in a
+// graph, and its result is the same bits on every run.  Refused before any
+// launch: fp64 archives, a config with useChecksum, rowWords == 0, a stride
+// below rowWords, and numBags * ceil(rowWords / 128) >= 2^32.  Not offered:
+// mean / max pooling, per-sample weights, sparse archives, a backward pass.
+void floatGatherRowsSum(StackDeviceMemory& res,
+                        const FloatDecompressConfig& config,
+                        const void* archive_dev, uint32_t rowWords,
+                        uint32_t numBags, uint32_t numIdx, const void* idx_dev,
+                        const void* offsets_dev, bool idxIs64, void* out_dev,
+                        bool outIsFp32, uint64_t outRowStrideWords,
+                        uint8_t* outSuccess_dev, hipStream_t stream);
+
 } // namespace dietgpu

@@ -35,6 +35,8 @@
  *   bitmap rank, then a range decode of the nonzero list's slice)
  *   dietgpu_ans_gather_rows, dietgpu_float_gather_rows (rows of a table held
  *   by one archive, named by indices in device memory; one launch)
+ *   dietgpu_float_gather_rows_sum (bags of such rows, each summed in fp32
+ *   into one output row: embedding_bag(mode="sum"); one launch)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -273,10 +275,28 @@ int dietgpu_float_gather_rows(dietgpu_stack* res, int float_type, int prob_bits,
                               uint64_t out_row_stride_words, uint8_t* out_success_dev,
                               void* stream);
 
+/* Pooled row gather (floatGatherRowsSum, GpuFloatCodec.h): bag b =
+ * idx_dev[offsets_dev[b] .. offsets_dev[b + 1]) of the [R, row_words] table,
+ * num_bags + 1 offsets and num_idx indices in device memory, both int32 or
+ * (idx_is_64 != 0) both int64.  out_dev[b * out_row_stride_words + j] = the
+ * fp32 sum, in list order and started from the first row, of word j of the
+ * bag's rows, rounded once to fp32 (out_is_fp32 != 0; required for float_type
+ * 3) or to the archive's 16-bit type; an empty bag gives +0.0.
+ * out_success_dev[b] (optional) = 1 iff the archive is valid, the bag's
+ * offsets are ordered and inside [0, num_idx] and all its rows lie inside the
+ * element; else 0 and the row is untouched.  float_type 1..3.  One launch, no
+ * host synchronisation, no allocation.  No checksum flag. */
+int dietgpu_float_gather_rows_sum(dietgpu_stack* res, int float_type, int prob_bits,
+                                  const void* archive_dev, uint32_t row_words, uint32_t num_bags,
+                                  uint32_t num_idx, const void* idx_dev, const void* offsets_dev,
+                                  int idx_is_64, void* out_dev, int out_is_fp32,
+                                  uint64_t out_row_stride_words, uint8_t* out_success_dev,
+                                  void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "hist", "coalesce", "sparse", "sparse_accumulate",
- * "sparse_reduce") is bracketed
+ * "decode_gather", "decode_gather_sum", "hist", "coalesce", "sparse",
+ * "sparse_accumulate", "sparse_reduce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);

@@ -90,6 +90,15 @@ int dietgpu_test_gather_config(dietgpu_stack* res, int float_type, int use_check
                                uint32_t row_words, uint32_t num_idx, const void* idx_dev, void* out,
                                uint8_t* out_success_dev, void* stream);
 
+/* The same for the pooled row gather's C++ entry point (floatGatherRowsSum),
+ * whose C ABI carries no checksum flag and refuses float_type 4 itself:
+ * num_bags + 1 int64 offsets at offsets_dev, num_idx int64 indices at idx_dev,
+ * rows of row_words words (fp32 when out_is_fp32) at a stride of row_words. */
+int dietgpu_test_gather_sum_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                   uint32_t row_words, uint32_t num_bags, uint32_t num_idx, const void* idx_dev,
+                                   const void* offsets_dev, void* out, int out_is_fp32, uint8_t* out_success_dev,
+                                   void* stream);
+
 /* The compress plan (csrc/compress_plan.h) of a dense compress call with no
  * caller-counted rows: which compressor takes the batch and what it launches.
  * Enumerations as in that header. */
