@@ -173,6 +173,62 @@ def place_words(dtype, caps, offs, init, guard=GUARD, device=DEV):
     return [buf[st:st + cap] for st, cap in zip(starts, caps)], buf, init_cpu, starts
 
 
+# ------------------------------------------------------------- large batches ----
+# Batches of tens of thousands of members (tests/test_gpu_slices.py): the
+# destinations are placed by word_starts() as above, but the buffer, what it
+# must hold afterwards and the comparison all stay on the device, and the
+# call's pointer columns are numpy arrays, not lists of tensor views.
+
+SENTINEL = 0xAB  # every byte of a buffer nothing has written yet
+
+
+def sentinel_words(shape, dtype, device=DEV):
+    """A tensor of `shape` and `dtype` whose every byte is SENTINEL."""
+    shape = [shape] if isinstance(shape, int) else list(shape)
+    flat = torch.full([int(np.prod(shape)) * dtype.itemsize], SENTINEL, dtype=torch.uint8, device=device)
+    return flat.view(dtype).view(shape)
+
+
+def host_ptrs(base, starts, itemsize):
+    """The addresses base + starts[i] * itemsize as a numpy uint64 column."""
+    return np.uint64(base) + np.asarray(starts, dtype=np.uint64) * np.uint64(itemsize)
+
+
+def scatter_rows(buf, starts, firsts, counts, row):
+    """buf[starts[m] + j] = row[firsts[m] + j] for j < counts[m] and every m:
+    1-d tensors on buf's device; starts an int64 tensor, firsts and counts
+    int64 tensors of its length or plain ints."""
+    m = starts.numel()
+    if m == 0:
+        return
+    most = int(counts.max()) if torch.is_tensor(counts) else int(counts)
+    if most == 0:
+        return
+    j = torch.arange(most, device=buf.device)
+    dst = starts[:, None] + j
+    src = (firsts[:, None] if torch.is_tensor(firsts) else firsts) + j.expand(m, most)
+    if torch.is_tensor(counts):
+        keep = j < counts[:, None]
+        dst, src = dst[keep], src[keep]
+    buf[dst.reshape(-1)] = row[src.reshape(-1)]
+
+
+def placed_mismatch(got, want, starts):
+    """None, or what differs between two placed buffers (integer words on one
+    device) and in which member's slice or guard: starts is word_starts()'s,
+    ascending, as a numpy array."""
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return f"buffers of {got.shape} {got.dtype} and {want.shape} {want.dtype}"
+    bad = (got != want).nonzero().view(-1)
+    if bad.numel() == 0:
+        return None
+    first = int(bad[0])
+    member = int(np.searchsorted(starts, first, side="right")) - 1
+    at = f"{first - int(starts[member])} words into member {member}" if member >= 0 else "before member 0"
+    return (f"{bad.numel()} words differ, the first is buffer word {first}, {at}: got "
+            f"{int(got[first]):#x}, want {int(want[first]):#x}")
+
+
 # ---------------------------------------------------- accumulate-style calls ----
 
 class Member:

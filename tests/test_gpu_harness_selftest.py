@@ -9,8 +9,9 @@ import torch
 
 from tests import accumulate_cases as A
 from tests import sparse_accumulate_cases as S
-from tests.gpu_harness import (GUARD, Cache, Member, check_placed, dense_at, pack_bytes, place_members, place_words,
-                               retyped, word_starts)
+from tests.gpu_harness import (GUARD, SENTINEL, Cache, Member, check_placed, dense_at, host_ptrs, pack_bytes,
+                               place_members, place_words, placed_mismatch, retyped, scatter_rows, sentinel_words,
+                               word_starts)
 from tests.util import NP_WORD, float_words
 
 SIZES = (0, 1, 7, 8, 9)
@@ -276,3 +277,52 @@ def test_retyped_changes_the_type_nibble_alone(ft, at, as_torch):
     got = p.numpy() if as_torch else p
     assert np.flatnonzero(got != keep).tolist() == [at]
     assert got[at] >> 4 == 0xA and got[at] & 0xF in (1, 2, 3, 4) and got[at] & 0xF != ft
+
+
+# ------------------------------------------------------------- large batches ----
+
+def test_large_batch_helpers_place_and_locate():
+    """sentinel_words / host_ptrs / scatter_rows / placed_mismatch (the
+    device-side placement of tests/test_gpu_slices.py) on the CPU: the rows
+    land in their slices and nowhere else, and a wrong word is named with its
+    member."""
+    caps = [3, 0, 5, 1, 4]
+    starts, total = word_starts(torch.int16, caps, [0] * len(caps))
+    starts_np = np.array(starts, dtype=np.int64)
+    buf = sentinel_words(total, torch.int16, device="cpu")
+    assert buf.shape == (total,) and buf.dtype == torch.int16
+    assert bool((buf.view(torch.uint8) == SENTINEL).all())
+    assert sentinel_words([2, 3], torch.uint8, device="cpu").shape == (2, 3)
+    assert host_ptrs(1000, starts_np, 2).tolist() == [1000 + 2 * s for s in starts]
+
+    row = torch.arange(100, 110, dtype=torch.int16)
+    want = buf.clone()
+    for st, cap in zip(starts, caps):
+        want[st:st + cap] = row[:cap]
+    # whole rows (plain counts), member by member
+    got = buf.clone()
+    for st, cap in zip(starts, caps):
+        scatter_rows(got, torch.tensor([st]), 0, cap, row)
+    assert torch.equal(got, want) and placed_mismatch(got, want, starts_np) is None
+    # ragged counts and firsts in one call
+    got = buf.clone()
+    firsts = torch.tensor([0, 4, 2, 9, 1])
+    scatter_rows(got, torch.tensor(starts), firsts, torch.tensor(caps), row)
+    for st, cap, f in zip(starts, caps, firsts.tolist()):
+        assert torch.equal(got[st:st + cap], row[f:f + cap])
+    touched = torch.zeros(total, dtype=torch.bool)
+    for st, cap in zip(starts, caps):
+        touched[st:st + cap] = True
+    assert torch.equal(got[~touched], buf[~touched])
+    scatter_rows(got, torch.tensor(starts)[:0], 0, 3, row)  # no member: nothing happens
+    scatter_rows(got, torch.tensor(starts), 0, torch.zeros(5, dtype=torch.int64), row)
+
+    wrong = want.clone()
+    wrong[starts[2] + 1] += 1
+    assert "1 words into member 2" in placed_mismatch(wrong, want, starts_np)
+    wrong = want.clone()
+    wrong[starts[4] + caps[4] + 2] = 0  # a guard word
+    assert "member 4" in placed_mismatch(wrong, want, starts_np)
+    wrong = want.clone()
+    wrong[0] = 0
+    assert "before member 0" in placed_mismatch(wrong, want, starts_np)
