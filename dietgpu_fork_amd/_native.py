@@ -130,6 +130,8 @@ def testlib():
                "dietgpu_test_occupy": (c_int, [P, c_u32, c_u32, c_u32]),
                "dietgpu_test_histogram": (c_int, [P, c_u32, P, c_u32, c_u32, P, P]),
                "dietgpu_test_enc_magic": (c_int, [P, P]),
+               "dietgpu_test_upload": (c_int, [P, P, ctypes.c_size_t, P]),
+               "dietgpu_test_upload_reset": (c_int, []),
                "dietgpu_test_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_sparse_range_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),
                "dietgpu_test_gather_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, P, P, P]),

@@ -77,6 +77,12 @@ struct DietGpuError : public std::runtime_error {
 // while a kernel node is.
 void zeroAsync(void* dst, size_t bytes, hipStream_t s);
 
+// Waits for every upload still in the pinned staging ring of
+// StackDeviceMemory::copyToDevice and puts the ring's head back at 0
+// (stack_memory.cpp).  For the test hooks: a test that depends on where its
+// uploads land starts from here.
+void stagingRingReset();
+
 // ---------------------------------------------------------------------------
 // device helpers (gfx950 wave64)
 // ---------------------------------------------------------------------------

@@ -5,12 +5,12 @@
 
 #include <algorithm>
 #include <cstring>
-#include <deque>
 #include <iostream>
 #include <mutex>
 #include <sstream>
 
 #include "common.h"
+#include "staging_plan.h"
 
 namespace dietgpu {
 
@@ -115,16 +115,12 @@ std::string StackDeviceMemory::toString() const {
 // pinned staging ring for host->device parameter tables
 // ---------------------------------------------------------------------------
 namespace {
+// The ring's memory, its events and its lock; where an upload goes and what it
+// waits for is StagingPlan's (staging_plan.h).
 struct StagingRing {
-  static constexpr size_t kBytes = 8u << 20;
-  struct Use {
-    size_t off, bytes;
-    hipEvent_t ev;
-  };
   std::mutex mu;
   char* host = nullptr;
-  size_t head = 0;
-  std::deque<Use> inflight;
+  StagingPlan<hipEvent_t> plan;
   std::vector<hipEvent_t> freeEvents;
 
   hipEvent_t getEvent() {
@@ -139,21 +135,8 @@ struct StagingRing {
     HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
     return e;
   }
-  // Uses are allocated in address order around the ring, so the oldest use is
-  // the only one the new region [off, off+bytes) can run into first.
-  void retireOverlapping(size_t off, size_t bytes) {
-    while (!inflight.empty()) {
-      auto& u = inflight.front();
-      bool overlap = u.off < off + bytes && off < u.off + u.bytes;
-      if (overlap) {
-        HIP_CHECK(hipEventSynchronize(u.ev));
-      } else if (hipEventQuery(u.ev) != hipSuccess) {
-        break;
-      }
-      freeEvents.push_back(u.ev);
-      inflight.pop_front();
-    }
-  }
+  static bool complete(hipEvent_t e) { return hipEventQuery(e) == hipSuccess; }
+  static void wait(hipEvent_t e) { HIP_CHECK(hipEventSynchronize(e)); }
 };
 StagingRing& ring() {
   static StagingRing r;
@@ -167,25 +150,27 @@ void StackDeviceMemory::copyToDevice(void* dst, const void* src, size_t bytes, h
   if (!bytes) return;
   if (uploadViaKernargs(dst, src, bytes, s)) return;  // tables up to 64 KB: no blit
   auto& r = ring();
-  if (bytes > StagingRing::kBytes / 4) {
+  if (bytes > kStagingMaxUpload) {
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
     return;
   }
   std::lock_guard<std::mutex> g(r.mu);
   if (!r.host) {
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r.host), StagingRing::kBytes,
-                            hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r.host), kStagingRingBytes, hipHostMallocDefault));
   }
-  size_t n = (bytes + 255) / 256 * 256;
-  if (r.head + n > StagingRing::kBytes) r.head = 0;
-  size_t off = r.head;
-  r.retireOverlapping(off, n);
+  const size_t off = r.plan.place(bytes, StagingRing::complete, StagingRing::wait,
+                                  [&](hipEvent_t e) { r.freeEvents.push_back(e); });
   std::memcpy(r.host + off, src, bytes);
   HIP_CHECK(hipMemcpyAsync(dst, r.host + off, bytes, hipMemcpyHostToDevice, s));
   hipEvent_t ev = r.getEvent();
   HIP_CHECK(hipEventRecord(ev, s));
-  r.inflight.push_back({off, n, ev});
-  r.head = off + n;
+  r.plan.commit(off, bytes, ev);
+}
+
+void stagingRingReset() {
+  auto& r = ring();
+  std::lock_guard<std::mutex> g(r.mu);
+  r.plan.drain(StagingRing::complete, StagingRing::wait, [&](hipEvent_t e) { r.freeEvents.push_back(e); });
 }
 
 StackDeviceMemory makeStackMemory(size_t bytes) {

@@ -6,7 +6,8 @@
 // histogram of the three-kernel compressor's first pass exposed on its own,
 // as the reference's ANSStatisticsTest.cu:44-95 exercises ansHistogramBatch;
 // the C++ entry points with configurations the C ABI cannot express; the
-// compress plan (compress_plan.h) as the dense driver computes it.
+// compress plan (compress_plan.h) as the dense driver computes it; the
+// parameter-table upload (StackDeviceMemory::copyToDevice) on its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -267,6 +268,16 @@ int dietgpu_test_compress_plan(int float_type, uint32_t nb, uint32_t max_size, i
     out->encode_runs = p.encodeRuns;
     out->coalesce_from_flags = p.coalesceFromFlags;
   });
+}
+
+int dietgpu_test_upload(void* dst_dev, const void* src_host, size_t bytes, void* stream) {
+  return guardedTest([&] {
+    dietgpu::StackDeviceMemory::copyToDevice(dst_dev, src_host, bytes, reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
+int dietgpu_test_upload_reset(void) {
+  return guardedTest([] { dietgpu::stagingRingReset(); });
 }
 
 int dietgpu_test_enc_magic(uint32_t* magic_dev, void* stream) {

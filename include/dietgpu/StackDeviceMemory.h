@@ -114,8 +114,10 @@ class StackDeviceMemory {
   void resetMaxMemoryUsage() { maxSeen_ = 0; }
   std::string toString() const;
 
-  // Asynchronous host->device copy through a pinned staging ring, so pointer /
-  // size tables never force a pageable (synchronous) copy.
+  // Host->device copy of a parameter table in the order of `s`; `src` may be
+  // reused as soon as the call returns.  Up to 64 KiB in kernel arguments, up
+  // to 2 MiB through a process-wide pinned staging ring (csrc/staging_plan.h),
+  // both asynchronous; larger tables as a pageable copy, which may wait for `s`.
   static void copyToDevice(void* dst, const void* src, size_t bytes, hipStream_t s);
 
  private:

@@ -41,6 +41,18 @@ int dietgpu_test_histogram(dietgpu_stack* res, uint32_t nb, const void* in_dev, 
  * (ans/GpuANSEncode.cuh:63-89). */
 int dietgpu_test_enc_magic(uint32_t* magic_dev, void* stream);
 
+/* StackDeviceMemory::copyToDevice on its own, the upload every entry point
+ * uses for its parameter tables: `bytes` from src_host (pageable) to dst_dev
+ * in the order of `stream`.  Up to 64 KiB in whole words the bytes ride in
+ * kernel arguments, up to 2 MiB they go through the process-wide pinned
+ * staging ring (csrc/staging_plan.h), above that straight to the copy engine.
+ * As for the library's own tables, src_host may be reused as soon as the call
+ * returns.  tests/test_gpu_uploads.py. */
+int dietgpu_test_upload(void* dst_dev, const void* src_host, size_t bytes, void* stream);
+/* Waits for every upload still in the staging ring and puts the ring's head
+ * at offset 0, so that a test knows where its next uploads land. */
+int dietgpu_test_upload_reset(void);
+
 /* Calls the C++ range-decode entry points (floatDecompressRange,
  * ansDecodeBatchRange) for one element with `use_checksum` set in their
  * config (for the float codec: FloatCodecConfig.useChecksum) -- the C ABI's
