@@ -602,6 +602,75 @@ def gather_rows_sum(archive, row_words, idx, offsets, dtype, out=None, out_dtype
     return out, ok
 
 
+def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
+                check=False):
+    """y = x @ W.T for a weight table W [R, row_words] stored as one dense
+    float16 / bfloat16 / float32 archive of `dtype` -> (out [M, R], ok).  x is
+    a CUDA tensor [M, row_words] of `dtype`, 1 <= M <= 64, its rows contiguous,
+    16-byte aligned and a whole number of 16 B apart; row_words is a multiple
+    of 256 (pad W and x with zeros).  R is out.size(1) when `out` is given;
+    without one R = n // row_words, n the element's size read from the
+    archive's header, which synchronises the stream once.  Every product and
+    add is fp32 (fmaf) in an order that depends on (row_words, r) alone -- the
+    same bits on every run, for every M -- rounded once to out's dtype, which
+    is `dtype` or torch.float32.
+    The decoded matrix is never stored: the decoder multiplies each weight
+    word out of its registers.  ok is one uint8: 1 iff the archive matches
+    dtype / prob_bits and holds R * row_words words; else `out` is untouched.
+    Nothing is uploaded or read back, so the call (two launches per 4 rows of
+    x, scratch from `ws`) can be captured in a graph and replayed on new x and
+    new archive bytes.  check=True reads ok back and raises DietGpuError."""
+    who = "matmul_rows"
+    if dtype == torch.uint8:
+        raise ValueError(f"{who}: byte archives hold no floats to multiply")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16, bfloat16 or float32 archives)")
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == dtype):
+        raise ValueError(f"{who}: x must be a 2-d {dtype} tensor [M, row_words]")
+    row_words = int(row_words)
+    if row_words < 1 or row_words % 256:
+        raise ValueError(f"{who}: row_words must be a positive multiple of 256 (pad the rows with zeros)")
+    if x.size(1) != row_words:
+        raise ValueError(f"{who}: x must have row_words = {row_words} columns, not {x.size(1)}")
+    M = x.size(0)
+    if not 1 <= M <= 64:
+        raise ValueError(f"{who}: x must hold 1 .. 64 rows (for more, decompress and call a GEMM), not {M}")
+    out_dtype = out_dtype if out_dtype is not None else (out.dtype if out is not None else dtype)
+    if out_dtype not in (dtype, torch.float32):
+        raise ValueError(f"{who}: out dtype {out_dtype} does not go with {dtype} archives (their own dtype, or "
+                         "torch.float32)")
+    if out is None:
+        if not x.is_cuda:
+            raise ValueError(f"{who}: x and out must be CUDA tensors on one device")
+        n = int(archive[4:8].view(torch.int32).item()) & 0xFFFFFFFF  # float header word 1: the element's words
+        out = torch.empty([M, max(1, n // row_words)], dtype=out_dtype, device=x.device)
+    if out.dim() != 2 or out.size(0) != M or out.size(1) < 1 or out.dtype != out_dtype:
+        raise ValueError(f"{who}: out must be a {out_dtype} tensor of shape [{M}, R], R >= 1")
+    rows = out.size(1)
+    if rows * row_words >= 1 << 32:
+        raise ValueError(f"{who}: R * row_words must be below 2^32")
+    x_stride = x.stride(0) if M > 1 else row_words
+    if x.stride(1) != 1 or x_stride < row_words or (x_stride * x.element_size()) % 16 or x.data_ptr() % 16:
+        raise ValueError(f"{who}: x's rows must be contiguous, 16-byte aligned and a whole number of 16 B apart")
+    out_stride = out.stride(0) if M > 1 else rows
+    if (rows != 1 and out.stride(1) != 1) or out_stride < rows:
+        raise ValueError(f"{who}: out's last dimension must be contiguous and its rows at least R apart")
+    if not (x.is_cuda and out.is_cuda and x.device == out.device):
+        raise ValueError(f"{who}: x and out must be CUDA tensors on one device")
+    ok = out_status if out_status is not None else torch.empty([1], dtype=torch.uint8, device=x.device)
+    if not (ok.dtype == torch.uint8 and ok.is_contiguous() and ok.numel() == 1 and ok.device == x.device):
+        raise ValueError(f"{who}: out_status must be a uint8 tensor of one entry")
+    if ws is None:  # the partial sums of one pass: min(M, 4) rows of R + blocks fp32 words
+        ws = Workspace(4 * min(M, 4) * (rows + (rows * row_words + 4095) // 4096) + 256, x.device)
+    N.check(N.lib().dietgpu_float_matmul_rows(
+        ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, rows, x.data_ptr(), M, x_stride,
+        out.data_ptr(), int(out_dtype == torch.float32), out_stride, ok.data_ptr(), _s()))
+    if check and not bool(ok.all()):
+        raise N.DietGpuError(f"{who}: the archive does not match dtype / prob_bits, or holds fewer than "
+                             f"{rows} rows of {row_words} words")
+    return out, ok
+
+
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
     return _pointer_compress(N.lib().dietgpu_float_compress_sparse, (ft, prob_bits, int(checksum)), ts,

@@ -4,8 +4,9 @@
 // headers, so that the rule -- performance policy, DESIGN.md 5.2 -- is stated
 // once and tested without a GPU (tests/test_decode_plan.py).  Below it the
 // grid rule of k_gather (gather.h; tests/test_gather_plan.py), that of
-// k_gatherSum (gather_sum.h; tests/test_gather_sum_plan.py) and the pass and
-// grid rules of k_reduce (reduce.h; tests/test_reduce_plan.py).
+// k_gatherSum (gather_sum.h; tests/test_gather_sum_plan.py), the pass and grid
+// rule of k_matmulRows (matmul.h) and the pass and grid rules of k_reduce
+// (reduce.h; tests/test_reduce_plan.py).
 #pragma once
 
 #include <algorithm>
@@ -122,6 +123,55 @@ inline GatherSumPlan planGatherSum(uint32_t numBags, uint32_t rowWords, uint32_t
   if (tasks >= (1ull << 32)) return {false, kGatherSumTile, tiles, tasks, 0, 0};
   const uint32_t groups = uint32_t((tasks + kGatherTasksPerWG - 1) / kGatherTasksPerWG);
   return {true, kGatherSumTile, tiles, tasks, groups, std::min(std::max(1u, slots), groups)};
+}
+
+// The pass and grid rule of the matmul on a compressed table (k_matmulRows,
+// matmul.h): M activation rows against the R rows of rowWords
+// words that one archive holds.  A task is a 4096-word block of the table; a
+// pass takes at most rowsPerPass activation rows through all of them.  The rows
+// go to the passes in order, evenly, as planReduce deals its sources.  Every
+// (block, row) piece of a pass leaves one fp32 partial per activation row at
+// id block + row, so a pass needs pieces = R + nBlocks words per row; the next
+// pass reuses them.
+constexpr uint32_t kMatmulSegWords = 256;   // dec::kSegWords: rowWords is a multiple of it
+constexpr uint32_t kMatmulMaxRows = 64;     // more activation rows than this is a GEMM
+constexpr uint32_t kMatmulRowsPerPass = 4;  // the largest k_matmulRows instance kept
+
+struct MatmulPass {
+  uint32_t first, count;  // activation rows [first, first + count)
+};
+
+struct MatmulPlan {
+  bool valid;  // rowWords a positive multiple of 256, 1 <= M <= 64, R >= 1, R * rowWords < 2^32, rowsPerPass >= 1
+  uint32_t numPasses;
+  MatmulPass passes[kMatmulMaxRows];
+  uint32_t nBlocks;       // 4096-word blocks that hold words of the table: the tasks
+  uint32_t pieces;        // R + nBlocks: partial words per activation row
+  uint64_t partialBytes;  // of one pass (the largest, which is the first)
+  uint32_t groups;        // task groups (of kGatherTasksPerWG tasks)
+  uint32_t gridX;         // persistent workgroups
+};
+
+// slots: as planGather's.
+inline MatmulPlan planMatmul(uint32_t numRows, uint32_t rowWords, uint32_t M, uint32_t rowsPerPass, uint32_t slots) {
+  MatmulPlan p{};
+  const uint64_t words = uint64_t(numRows) * rowWords;
+  p.valid = rowWords >= 1 && rowWords % kMatmulSegWords == 0 && M >= 1 && M <= kMatmulMaxRows && numRows >= 1 &&
+            words < (1ull << 32) && rowsPerPass >= 1;
+  if (!p.valid) return p;
+  p.numPasses = (M + rowsPerPass - 1) / rowsPerPass;
+  uint32_t first = 0;
+  for (uint32_t i = 0; i < p.numPasses; ++i) {
+    const uint32_t count = M / p.numPasses + (i < M % p.numPasses ? 1 : 0);
+    p.passes[i] = {first, count};
+    first += count;
+  }
+  p.nBlocks = uint32_t((words + 4095) / 4096);
+  p.pieces = numRows + p.nBlocks;
+  p.partialBytes = 4ull * p.passes[0].count * p.pieces;
+  p.groups = (p.nBlocks + kGatherTasksPerWG - 1) / kGatherTasksPerWG;
+  p.gridX = std::min(std::max(1u, slots), p.groups);
+  return p;
 }
 
 // The pass rule of the fused reduce (k_reduce, reduce.h; DESIGN.md 5.2g;

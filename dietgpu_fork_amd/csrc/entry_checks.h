@@ -24,7 +24,7 @@ inline void checkFloatConfig(const FloatCodecConfig& c) {
 
 // The forms that decode part of an element, or add it to something: none can
 // verify the archive's checksum, and a config that asks for it is refused.
-enum class PartialDecode { kRange, kGather, kAccumulate, kReduce, kGatherSum };
+enum class PartialDecode { kRange, kGather, kAccumulate, kReduce, kGatherSum, kMatmul };
 
 inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
   switch (what) {
@@ -44,6 +44,9 @@ inline void checkNoChecksum(bool useChecksum, PartialDecode what) {
       break;
     case PartialDecode::kGatherSum:
       DG_CHECK(!useChecksum, "a pooled row gather cannot verify a checksum (the decoded words are never stored)");
+      break;
+    case PartialDecode::kMatmul:
+      DG_CHECK(!useChecksum, "a compressed matmul cannot verify a checksum (the decoded words are never stored)");
       break;
   }
 }
@@ -100,6 +103,32 @@ inline void checkGatherSumShape(int floatType, bool outIsFp32, uint32_t rowWords
            "a pooled row gather takes fp16, bf16 or fp32 archives (float type 1..3), not " << floatType);
   DG_CHECK(outIsFp32 || floatType != 3, "the pooled rows of an fp32 archive are fp32 (outIsFp32 must be set)");
   checkGatherRows(rowWords, outRowStrideWords);
+}
+
+// The matmul on a compressed table (floatMatmulRows; float types as
+// FloatType's values): fp16, bf16 and fp32 archives, an out of the archive's
+// type or fp32, rows of a multiple of 256 words, 1 .. 64 activation rows at a
+// stride of whole 16 B.  The C ABI makes the same checks before it looks at the
+// stack or any pointer.
+inline void checkMatmulShape(int floatType, bool outIsFp32, uint32_t rowWords, uint32_t numRows, uint32_t M,
+                             uint64_t xRowStrideWords, uint64_t outRowStrideWords) {
+  DG_CHECK(floatType >= 1 && floatType <= 3,
+           "a compressed matmul takes fp16, bf16 or fp32 archives (float type 1..3), not " << floatType);
+  DG_CHECK(outIsFp32 || floatType != 3, "the products of an fp32 archive are fp32 (outIsFp32 must be set)");
+  DG_CHECK(rowWords >= 1 && rowWords % kMatmulSegWords == 0,
+           "rowWords (" << rowWords << ") must be a positive multiple of " << kMatmulSegWords
+                        << " (pad the rows with zeros)");
+  DG_CHECK(M >= 1 && M <= kMatmulMaxRows, "M (" << M << ") must be in 1 .. " << kMatmulMaxRows
+                                                << " (for more activation rows, decompress and call a GEMM)");
+  DG_CHECK(numRows >= 1, "numRows must be at least 1");
+  DG_CHECK(uint64_t(numRows) * rowWords < (1ull << 32),
+           "numRows (" << numRows << ") times rowWords (" << rowWords << ") must be below 2^32");
+  DG_CHECK(xRowStrideWords >= rowWords,
+           "xRowStrideWords (" << xRowStrideWords << ") must be at least rowWords (" << rowWords << ")");
+  DG_CHECK(xRowStrideWords * (floatType == 3 ? 4 : 2) % 16 == 0,
+           "xRowStrideWords (" << xRowStrideWords << ") must be a whole number of 16 B");
+  DG_CHECK(outRowStrideWords >= numRows,
+           "outRowStrideWords (" << outRowStrideWords << ") must be at least numRows (" << numRows << ")");
 }
 
 }  // namespace dietgpu

@@ -23,6 +23,7 @@
 //   gather_rows                       ext   floatGatherRows / ansGatherRows
 //   reduce_data                       ext   floatReduceArchives (*)
 //   gather_rows_sum                   ext   floatGatherRowsSum (*)
+//   matmul_rows                       ext   floatMatmulRows
 //   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
@@ -64,6 +65,7 @@
 #include <tuple>
 #include <vector>
 
+#include "decode_plan.h"
 #include "dietgpu/GpuANSCodec.h"
 #include "dietgpu/GpuFloatCodec.h"
 #include "dietgpu/StackDeviceMemory.h"
@@ -760,6 +762,66 @@ int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tenso
   return cx.used();
 }
 
+// Extension (no reference counterpart): y = x W^T on a compressed weight table
+// (floatMatmulRows).  Archive t_in holds W [R, row_words]; t_x [*lead,
+// row_words] holds M = prod(lead) <= 64 activation rows of the archive's
+// dtype, contiguous in their last dimension, at one stride of whole 16 B and
+// 16 B-aligned; t_out [*lead, R] takes the products, in t_x's dtype or (over a
+// float16 / bfloat16 t_x too) float32.  Every product and add is fp32, in an
+// order that depends on (row_words, r) alone, with one rounding at the end.
+// out_status[0] = 1 iff the archive is valid and holds R * row_words words;
+// else t_out is left untouched.  Scratch comes from temp_mem.  The checks that
+// need no device come first.
+int64_t matmul_rows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+  TORCH_CHECK(rowWords >= 1 && rowWords % 256 == 0 && uint64_t(rowWords) <= kU32Max,
+              "row_words must be a positive multiple of 256 (pad the rows with zeros), not ", rowWords);
+  checkDtype(tX, tX.scalar_type(), {false, "t_x", "t_x"});
+  TORCH_CHECK(tOut.scalar_type() == tX.scalar_type() || tOut.scalar_type() == at::kFloat, "t_out must have t_x's dtype (",
+              tX.scalar_type(), ") or float32, not ", tOut.scalar_type());
+  const int64_t k = tX.dim() - 1;
+  TORCH_CHECK(k >= 0 && tX.size(k) == rowWords, "t_x must have the shape [*lead, row_words] = [..., ", rowWords,
+              "], not ", tX.sizes());
+  bool shapeOk = tOut.dim() == k + 1 && tOut.size(k) >= 1;
+  for (int64_t d = 0; shapeOk && d < k; ++d) shapeOk = tOut.size(d) == tX.size(d);
+  TORCH_CHECK(shapeOk, "t_out must have the shape [*lead, R] with t_x's leading dimensions and R >= 1, not ",
+              tOut.sizes(), " beside t_x ", tX.sizes());
+  const int64_t rows = tOut.size(k), M = tX.numel() / rowWords;
+  TORCH_CHECK(M >= 1 && M <= int64_t(kMatmulMaxRows), "t_x must hold 1 .. ", kMatmulMaxRows,
+              " rows (for more, decompress and call a GEMM), not ", M);
+  TORCH_CHECK(uint64_t(rows) * uint64_t(rowWords) <= kU32Max, "R * row_words must be below 2^32");
+  // rows at one stride: leading dimension d strides over the rows inside it
+  auto rowStride = [&](const at::Tensor& t, int64_t width, const char* name) {
+    TORCH_CHECK(width == 1 || t.stride(k) == 1, name, "'s last dimension must be contiguous");
+    int64_t stride = -1, inner = 1;
+    for (int64_t d = k - 1; d >= 0; --d) {
+      if (t.size(d) != 1) {
+        if (stride < 0) stride = t.stride(d);
+        else TORCH_CHECK(t.stride(d) == stride * inner, name, "'s rows must lie at a constant stride");
+      }
+      inner *= t.size(d);
+    }
+    if (stride < 0) stride = width;
+    TORCH_CHECK(stride >= width, name, "'s rows must not overlap (row stride ", stride, " < ", width, ")");
+    return stride;
+  };
+  const int64_t xStride = rowStride(tX, rowWords, "t_x"), outStride = rowStride(tOut, rows, "t_out");
+  TORCH_CHECK(xStride * tX.element_size() % 16 == 0 && reinterpret_cast<uintptr_t>(tX.data_ptr()) % 16 == 0,
+              "t_x's rows must be 16-byte aligned (its data pointer and its row stride in bytes)");
+  TORCH_CHECK(tX.device().type() == at::kCUDA, "t_x must be a GPU tensor (on the archive's device)");
+  const int dev = tX.get_device();
+  CallContext cx(dev);
+  Members m(dev, 1, 0);
+  m.archive(tIn);
+  TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
+  const auto st = statusPointers(status, std::nullopt, 1, dev).first;
+  cx.stack(tempMem);
+  floatMatmulRows(*cx.res, floatConfig(floatTypeOf(tX.scalar_type()), false), tIn.data_ptr(), uint32_t(rowWords),
+                  uint32_t(rows), tX.data_ptr(), uint32_t(M), uint64_t(xStride), tOut.data_ptr(),
+                  tOut.scalar_type() == at::kFloat, uint64_t(outStride), st, cx.stream);
+  return cx.used();
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -873,6 +935,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "gather_rows_sum(Tensor t_in, int row_words, Tensor t_idx, Tensor t_offsets, Tensor t_out, Tensor? "
       "temp_mem=None, Tensor? out_status=None) -> int");
+  m.def(
+      "matmul_rows(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, Tensor? temp_mem=None, Tensor? "
+      "out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -891,4 +956,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("gather_rows", &dietgpu::gather_rows);
   m.impl("reduce_data", &dietgpu::reduce_data);
   m.impl("gather_rows_sum", &dietgpu::gather_rows_sum);
+  m.impl("matmul_rows", &dietgpu::matmul_rows);
 }

@@ -24,6 +24,7 @@ validation and return values; "ext": not in the reference.
     gather_rows                       ext   MORE_OPS    rows of a table held by one archive, by device indices
     reduce_data                       ext   REDUCE_OPS  sums several archives per member in one kernel
     gather_rows_sum                   ext   POOL_OPS    sums bags of rows of a table held by one archive
+    matmul_rows                       ext   MATMUL_OPS  x W^T for a few rows of x, W a table held by one archive
 """
 import os
 
@@ -61,6 +62,10 @@ REDUCE_OPS = ("reduce_data",)
 # kernel: embedding_bag(mode="sum") on a compressed table
 POOL_OPS = ("gather_rows_sum",)
 
+# matmul_rows multiplies up to 64 activation rows into a weight table held by
+# one archive, out of the decoder's registers: a compressed nn.Linear forward
+MATMUL_OPS = ("matmul_rows",)
+
 _LOADED = False
 
 
@@ -79,7 +84,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS or name in MORE_OPS or name in REDUCE_OPS or name in POOL_OPS:
+    if name in OPS or name in MORE_OPS or name in REDUCE_OPS or name in POOL_OPS or name in MATMUL_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

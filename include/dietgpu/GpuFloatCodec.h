@@ -336,4 +336,32 @@ void floatGatherRowsSum(StackDeviceMemory& res,
                         bool outIsFp32, uint64_t outRowStrideWords,
                         uint8_t* outSuccess_dev, hipStream_t stream);
 
+// Matmul on a compressed weight table (y = x W^T straight from the archive):
+// the dense fp16 / bf16 / fp32 archive holds W [numRows, rowWords] row-major;
+// x_dev holds M rows of rowWords words of the archive's type, xRowStrideWords
+// apart.  For 0 <= m < M and 0 <= r < numRows
+//   out[m * outRowStrideWords + r] = round_out(sum_k f(x[m, k]) * f(W[r, k]))
+// with f the exact conversion to fp32, every product and add an fp32 fmaf in
+// an order that depends on (rowWords, r) alone -- the same bits on every run,
+// for every M and whatever other rows the table holds -- and one rounding to
+// the output type: fp32 when outIsFp32 (always for fp32 archives), else the
+// archive's 16-bit type.  The decoded matrix is never stored.
+// outSuccess_dev[0] (optional) = 1 iff the archive is valid for this config
+// and numRows * rowWords words fit its element; on failure nothing else is
+// written.  Scratch (4 * min(M, 4) * (numRows + ceil(numRows * rowWords /
+// 4096)) bytes) comes from res; two launches per 4 activation rows, no host
+// synchronisation, no upload, no atomics: the call can be captured in a graph.
+// Refused before any launch: fp64 archives, a config with useChecksum,
+// rowWords no positive multiple of 256 (pad the rows with zeros), M outside
+// 1 .. 64 (beyond that, decompress and call a GEMM), numRows == 0,
+// numRows * rowWords >= 2^32, strides below their rows, and an x whose base or
+// row stride is no multiple of 16 bytes.  out_dev may sit at any word.
+void floatMatmulRows(StackDeviceMemory& res,
+                     const FloatDecompressConfig& config,
+                     const void* archive_dev, uint32_t rowWords,
+                     uint32_t numRows, const void* x_dev, uint32_t M,
+                     uint64_t xRowStrideWords, void* out_dev, bool outIsFp32,
+                     uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                     hipStream_t stream);
+
 } // namespace dietgpu

@@ -37,6 +37,8 @@
  *   by one archive, named by indices in device memory; one launch)
  *   dietgpu_float_gather_rows_sum (bags of such rows, each summed in fp32
  *   into one output row: embedding_bag(mode="sum"); one launch)
+ *   dietgpu_float_matmul_rows (y = x W^T for up to 64 rows of x against a
+ *   weight table held by one archive; the decoded matrix is never stored)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -293,9 +295,26 @@ int dietgpu_float_gather_rows_sum(dietgpu_stack* res, int float_type, int prob_b
                                   uint64_t out_row_stride_words, uint8_t* out_success_dev,
                                   void* stream);
 
+/* Matmul on a compressed weight table (floatMatmulRows, GpuFloatCodec.h): the
+ * archive holds W [num_rows, row_words]; x_dev holds m rows of row_words words
+ * of the archive's type, x_row_stride_words apart (base and stride whole
+ * 16 B).  out_dev[i * out_row_stride_words + r] = sum_k x[i, k] * W[r, k] in
+ * fp32 (fmaf, in an order that depends on row_words and r alone), rounded once
+ * to fp32 (out_is_fp32 != 0; required for float_type 3) or to the archive's
+ * 16-bit type.  out_success_dev[0] (optional) = 1 iff the archive is valid and
+ * holds num_rows * row_words words; else 0 and out_dev is untouched.
+ * float_type 1..3, row_words a positive multiple of 256, 1 <= m <= 64.
+ * Scratch comes from res; no host synchronisation, no upload.  No checksum
+ * flag. */
+int dietgpu_float_matmul_rows(dietgpu_stack* res, int float_type, int prob_bits,
+                              const void* archive_dev, uint32_t row_words, uint32_t num_rows,
+                              const void* x_dev, uint32_t m, uint64_t x_row_stride_words,
+                              void* out_dev, int out_is_fp32, uint64_t out_row_stride_words,
+                              uint8_t* out_success_dev, void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "decode_gather_sum", "hist", "coalesce", "sparse",
+ * "decode_gather", "decode_gather_sum", "matmul_rows", "hist", "coalesce", "sparse",
  * "sparse_accumulate", "sparse_reduce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */

@@ -111,6 +111,14 @@ int dietgpu_test_gather_sum_config(dietgpu_stack* res, int float_type, int use_c
                                    const void* offsets_dev, void* out, int out_is_fp32, uint8_t* out_success_dev,
                                    void* stream);
 
+/* The same for the compressed matmul's C++ entry point (floatMatmulRows), whose
+ * C ABI carries no checksum flag and refuses float_type 4 itself: m rows of
+ * row_words words at x (stride row_words) against the archive's
+ * [num_rows, row_words] table, into out [m, num_rows] (fp32 when out_is_fp32). */
+int dietgpu_test_matmul_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                               uint32_t row_words, uint32_t num_rows, const void* x, uint32_t m, void* out,
+                               int out_is_fp32, uint8_t* out_success_dev, void* stream);
+
 /* The compress plan (csrc/compress_plan.h) of a dense compress call with no
  * caller-counted rows: which compressor takes the batch and what it launches.
  * Enumerations as in that header. */
