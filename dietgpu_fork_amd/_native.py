@@ -93,6 +93,8 @@ def _declare(L):
                                                   c_u64, P, P]),
         "dietgpu_float_matmul_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int, c_u64,
                                               P, P]),
+        "dietgpu_float_matmul_tile": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int, c_u64,
+                                              P, P]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),
@@ -140,6 +142,8 @@ def testlib():
                "dietgpu_test_gather_sum_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, c_u32, P, P, P, c_int, P,
                                                           P]),
                "dietgpu_test_matmul_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, c_u32, P, c_int, P, P]),
+               "dietgpu_test_matmul_tile_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, c_u32, P, c_int, P,
+                                                           P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
                "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
                "dietgpu_test_sparse_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_int, P, c_u32, c_int, P,

@@ -603,7 +603,7 @@ def gather_rows_sum(archive, row_words, idx, offsets, dtype, out=None, out_dtype
 
 
 def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
-                check=False):
+                check=False, _tile=False):
     """y = x @ W.T for a weight table W [R, row_words] stored as one dense
     float16 / bfloat16 / float32 archive of `dtype` -> (out [M, R], ok).  x is
     a CUDA tensor [M, row_words] of `dtype`, 1 <= M <= 64, its rows contiguous,
@@ -620,11 +620,14 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     Nothing is uploaded or read back, so the call (two launches per 4 rows of
     x, scratch from `ws`) can be captured in a graph and replayed on new x and
     new archive bytes.  check=True reads ok back and raises DietGpuError."""
-    who = "matmul_rows"
+    who = "matmul_tile" if _tile else "matmul_rows"
     if dtype == torch.uint8:
         raise ValueError(f"{who}: byte archives hold no floats to multiply")
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"{who}: unsupported dtype {dtype} (float16, bfloat16 or float32 archives)")
+    if _tile and dtype == torch.float32:
+        raise ValueError(f"{who}: float32 archives go through matmul_rows (the matrix pipe multiplies 16-bit words)")
+    if dtype not in (torch.float16, torch.bfloat16) + (() if _tile else (torch.float32,)):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16{', ' if not _tile else ' or '}bfloat16"
+                         f"{'' if _tile else ' or float32'} archives)")
     if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == dtype):
         raise ValueError(f"{who}: x must be a 2-d {dtype} tensor [M, row_words]")
     row_words = int(row_words)
@@ -660,15 +663,31 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     ok = out_status if out_status is not None else torch.empty([1], dtype=torch.uint8, device=x.device)
     if not (ok.dtype == torch.uint8 and ok.is_contiguous() and ok.numel() == 1 and ok.device == x.device):
         raise ValueError(f"{who}: out_status must be a uint8 tensor of one entry")
-    if ws is None:  # the partial sums of one pass: min(M, 4) rows of R + blocks fp32 words
-        ws = Workspace(4 * min(M, 4) * (rows + (rows * row_words + 4095) // 4096) + 256, x.device)
-    N.check(N.lib().dietgpu_float_matmul_rows(
+    if ws is None:  # the partial sums of one pass: min(M, 4) rows (tiled: all M) of R + blocks fp32 words
+        ws = Workspace(4 * (M if _tile else min(M, 4)) * (rows + (rows * row_words + 4095) // 4096) + 256, x.device)
+    N.check((N.lib().dietgpu_float_matmul_tile if _tile else N.lib().dietgpu_float_matmul_rows)(
         ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, rows, x.data_ptr(), M, x_stride,
         out.data_ptr(), int(out_dtype == torch.float32), out_stride, ok.data_ptr(), _s()))
     if check and not bool(ok.all()):
         raise N.DietGpuError(f"{who}: the archive does not match dtype / prob_bits, or holds fewer than "
                              f"{rows} rows of {row_words} words")
     return out, ok
+
+
+def matmul_tile(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
+                check=False):
+    """matmul_rows through the matrix pipe, for float16 / bfloat16 archives:
+    all 1 <= M <= 64 rows of x in ONE pass over the archive (matmul_rows
+    decodes it once per 4 rows), so this is the path of a small batch, a
+    speculative step or a short prefill.  Arguments, status, alignment and
+    refusals are matmul_rows'; a float32 `dtype` is refused.  The products are
+    exact, the sums fp32 in an order that depends on (row_words, r) alone --
+    the same bits on every run, for row r whatever other rows the table holds,
+    for row m whatever M is -- rounded once to out's dtype.  The bits are not
+    those of matmul_rows.  Two launches, scratch (4 * M * (R + blocks) bytes)
+    from `ws`; the call can be captured in a graph."""
+    return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
+                       prob_bits=prob_bits, check=check, _tile=True)
 
 
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):

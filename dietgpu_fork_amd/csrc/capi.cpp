@@ -442,6 +442,20 @@ int dietgpu_float_matmul_rows(dietgpu_stack* res, int ft, int pb, const void* ar
   });
 }
 
+int dietgpu_float_matmul_tile(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
+                              uint32_t num_rows, const void* x_dev, uint32_t m, uint64_t x_row_stride, void* out_dev,
+                              int out_is_fp32, uint64_t out_row_stride, uint8_t* succ, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at, as dietgpu_float_matmul_rows)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkProbBits(pb);
+    checkMatmulTileShape(ft, out_is_fp32 != 0, row_words, num_rows, m, x_row_stride, out_row_stride);
+    floatMatmulTile(R(res), cfg, archive_dev, row_words, num_rows, x_dev, m, x_row_stride, out_dev, out_is_fp32 != 0,
+                    out_row_stride, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

@@ -174,6 +174,48 @@ inline MatmulPlan planMatmul(uint32_t numRows, uint32_t rowWords, uint32_t M, ui
   return p;
 }
 
+// The task and grid rule of the matmul through the matrix pipe (k_matmulTile,
+// matmul_tile.h): all M <= 64 activation rows in one pass.  A
+// workgroup's eight half-waves take blocks `period` apart, period the least
+// count of 4096-word blocks that is a whole number of rows: such blocks start
+// at the same column of their rows.  The block line is tiled in runs of
+// 8 * period blocks, each run `period` task groups; a group whose first block
+// lies past the table is skipped.  The pieces are planMatmul's, one set per
+// activation row.
+struct MatmulTilePlan {
+  bool valid;             // planMatmul's rule
+  uint32_t period;        // (rowWords / 256) / gcd(rowWords / 256, 16)
+  uint32_t nBlocks;       // 4096-word blocks that hold words of the table
+  uint32_t pieces;        // R + nBlocks: partial words per activation row
+  uint64_t partialBytes;  // 4 * M * pieces
+  uint32_t groups;        // task groups: ceil(nBlocks / (8 * period)) * period
+  uint32_t gridX;         // persistent workgroups
+};
+
+// slots: as planGather's.
+inline MatmulTilePlan planMatmulTile(uint32_t numRows, uint32_t rowWords, uint32_t M, uint32_t slots) {
+  MatmulTilePlan p{};
+  const uint64_t words = uint64_t(numRows) * rowWords;
+  p.valid = rowWords >= 1 && rowWords % kMatmulSegWords == 0 && M >= 1 && M <= kMatmulMaxRows && numRows >= 1 &&
+            words < (1ull << 32);
+  if (!p.valid) return p;
+  const uint32_t segs = rowWords / kMatmulSegWords;
+  uint32_t a = segs, b = 4096 / kMatmulSegWords;
+  while (b) {
+    const uint32_t t = a % b;
+    a = b;
+    b = t;
+  }
+  p.period = segs / a;
+  p.nBlocks = uint32_t((words + 4095) / 4096);
+  p.pieces = numRows + p.nBlocks;
+  p.partialBytes = 4ull * M * p.pieces;
+  const uint64_t run = uint64_t(kGatherTasksPerWG) * p.period;
+  p.groups = uint32_t((p.nBlocks + run - 1) / run * p.period);
+  p.gridX = std::min(std::max(1u, slots), p.groups);
+  return p;
+}
+
 // The pass rule of the fused reduce (k_reduce, reduce.h; DESIGN.md 5.2g;
 // tests/test_reduce_plan.py): K sources, at most nsMax per launch.  The
 // sources go to the passes in order, evenly (the larger passes first: fewer

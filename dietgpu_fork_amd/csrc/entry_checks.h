@@ -131,4 +131,18 @@ inline void checkMatmulShape(int floatType, bool outIsFp32, uint32_t rowWords, u
            "outRowStrideWords (" << outRowStrideWords << ") must be at least numRows (" << numRows << ")");
 }
 
+// The matmul through the matrix pipe (floatMatmulTile): fp16 and bf16 archives
+// alone, each other type with its own message; everything else is
+// checkMatmulShape's.  The C ABI makes the same checks before it looks at the
+// stack or any pointer.
+inline void checkMatmulTileShape(int floatType, bool outIsFp32, uint32_t rowWords, uint32_t numRows, uint32_t M,
+                                 uint64_t xRowStrideWords, uint64_t outRowStrideWords) {
+  DG_CHECK(floatType != 3, "a tiled matmul multiplies 16-bit words (float type 1 or 2); matmul_rows is the path of "
+                           "an fp32 archive");
+  DG_CHECK(floatType != 4, "a tiled matmul takes fp16 or bf16 archives (float type 1 or 2), not fp64");
+  DG_CHECK(floatType == 1 || floatType == 2,
+           "a tiled matmul takes fp16 or bf16 archives (float type 1 or 2), not " << floatType);
+  checkMatmulShape(floatType, outIsFp32, rowWords, numRows, M, xRowStrideWords, outRowStrideWords);
+}
+
 }  // namespace dietgpu

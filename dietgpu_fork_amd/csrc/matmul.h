@@ -31,7 +31,8 @@
 //    adds is a function of (rowWords, r) alone, and the call can be captured.
 // No matrix instructions: an MFMA shares one B operand across its 16 or 32
 // output columns, and here a wave holds two weight rows, one per half, each at
-// its own k range.
+// its own k range.  k_matmulTile (matmul_tile.h) assigns the
+// blocks so that a workgroup holds eight rows at one k range, and uses them.
 #pragma once
 
 #include "decode.h"

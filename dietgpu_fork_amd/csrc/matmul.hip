@@ -1,5 +1,6 @@
-// Host driver of the matmul on a compressed weight table (k_matmulRows,
-// k_matmulFinish, matmul.h): floatMatmulRows of
+// Host drivers of the matmul on a compressed weight table: floatMatmulRows
+// (k_matmulRows, k_matmulFinish, matmul.h) and floatMatmulTile
+// (k_matmulTile, matmul_tile.h) of
 // include/dietgpu/GpuFloatCodec.h.  A translation unit of its own, as
 // reduce.hip is, so that its instances compile beside codec.hip's kernels.
 #include <algorithm>
@@ -9,14 +10,15 @@
 #include "codec_internal.h"
 #include "dietgpu/GpuFloatCodec.h"
 #include "matmul.h"
+#include "matmul_tile.h"
 #include "profile.h"
 
 namespace dietgpu {
 
 namespace {
 
-// the workgroups of a k_matmulRows instance resident on the current device at
-// once (cached per device, instance and LDS size)
+// the workgroups of a k_matmulRows or k_matmulTile instance resident on the
+// current device at once (cached per device, instance and LDS size)
 uint32_t matmulSlots(const void* kernel, uint32_t lds) {
   return cachedPerDevice<uint32_t>(std::make_tuple(kernel, lds), [&](int dev) {
     int cus = 0, perCU = 0;
@@ -117,6 +119,49 @@ void floatMatmulRows(StackDeviceMemory& res, const FloatDecompressConfig& config
     default:
       return run(std::integral_constant<int, 3>{}, f32);
   }
+}
+
+void floatMatmulTile(StackDeviceMemory& res, const FloatDecompressConfig& config, const void* archive_dev,
+                     uint32_t rowWords, uint32_t numRows, const void* x_dev, uint32_t M, uint64_t xRowStrideWords,
+                     void* out_dev, bool outIsFp32, uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                     hipStream_t stream) {
+  // every host check before the allocation and the first launch
+  checkFloatConfig(config);
+  checkNoChecksum(config.useChecksum, PartialDecode::kMatmul);
+  const int ft = int(config.floatType), pb = config.ansConfig.probBits;
+  checkProbBits(pb);
+  checkMatmulTileShape(ft, outIsFp32, rowWords, numRows, M, xRowStrideWords, outRowStrideWords);
+  DG_CHECK(planMatmulTile(numRows, rowWords, M, 1).valid,
+           "no matmul plan for " << numRows << " rows of " << rowWords << " words and M = " << M);
+  DG_CHECK(archive_dev && x_dev && out_dev, "archive_dev, x_dev and out_dev must not be null");
+  checkArchiveAligned(reinterpret_cast<uintptr_t>(archive_dev), 0, 4);
+  DG_CHECK(reinterpret_cast<uintptr_t>(x_dev) % 16 == 0, "x_dev must be 16-byte aligned");
+  DG_CHECK(reinterpret_cast<uintptr_t>(out_dev) % (outIsFp32 ? 4 : 2) == 0, "out_dev not aligned to its word size");
+
+  auto run = [&](auto tag, auto out32) {
+    constexpr int FT = decltype(tag)::value;
+    const uint32_t lds = mmt::ldsBytes(DecCfg<FT>::ldsBytes(pb));
+    const MatmulTilePlan plan = planMatmulTile(
+        numRows, rowWords, M, matmulSlots(reinterpret_cast<const void*>(&k_matmulTile<FT>), lds));
+    auto part = res.alloc<uint8_t>(stream, size_t(plan.partialBytes));
+    float* partial = reinterpret_cast<float*>(part.data());
+    const auto* archive = static_cast<const uint8_t*>(archive_dev);
+    const auto* x = static_cast<const uint8_t*>(x_dev);
+    const uint32_t finishGrid = divUp(M * numRows, uint32_t(dec::kThreads));
+    prof::Scope p("matmul_tile", stream);
+    k_matmulTile<FT><<<plan.gridX, dec::kThreads, lds, stream>>>(archive, numRows, rowWords, x, xRowStrideWords * 2, M,
+                                                                  partial, plan.pieces, plan.period, pb);
+    HIP_LAUNCH_CHECK();
+    k_matmulFinish<FT, decltype(out32)::value><<<finishGrid, dec::kThreads, 0, stream>>>(
+        archive, numRows, rowWords, M, partial, plan.pieces, static_cast<uint8_t*>(out_dev), outRowStrideWords, pb,
+        outSuccess_dev);
+    HIP_LAUNCH_CHECK();
+  };
+  constexpr std::true_type f32;
+  constexpr std::false_type own;
+  if (config.floatType == FloatType::kFloat16)
+    return outIsFp32 ? run(std::integral_constant<int, 1>{}, f32) : run(std::integral_constant<int, 1>{}, own);
+  return outIsFp32 ? run(std::integral_constant<int, 2>{}, f32) : run(std::integral_constant<int, 2>{}, own);
 }
 
 }  // namespace dietgpu

@@ -24,6 +24,7 @@
 //   reduce_data                       ext   floatReduceArchives (*)
 //   gather_rows_sum                   ext   floatGatherRowsSum (*)
 //   matmul_rows                       ext   floatMatmulRows
+//   matmul_tile                       ext   floatMatmulTile
 //   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
@@ -772,11 +773,15 @@ int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tenso
 // out_status[0] = 1 iff the archive is valid and holds R * row_words words;
 // else t_out is left untouched.  Scratch comes from temp_mem.  The checks that
 // need no device come first.
-int64_t matmul_rows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
-                    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+// tile: matmul_tile (floatMatmulTile: float16 and bfloat16 alone, all the rows
+// in one pass through the matrix pipe), with the same arguments and checks.
+int64_t matmulOp(bool tile, const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                 const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
   TORCH_CHECK(rowWords >= 1 && rowWords % 256 == 0 && uint64_t(rowWords) <= kU32Max,
               "row_words must be a positive multiple of 256 (pad the rows with zeros), not ", rowWords);
   checkDtype(tX, tX.scalar_type(), {false, "t_x", "t_x"});
+  TORCH_CHECK(!tile || tX.scalar_type() != at::kFloat,
+              "matmul_tile multiplies float16 or bfloat16 words; matmul_rows is the path of a float32 archive");
   TORCH_CHECK(tOut.scalar_type() == tX.scalar_type() || tOut.scalar_type() == at::kFloat, "t_out must have t_x's dtype (",
               tX.scalar_type(), ") or float32, not ", tOut.scalar_type());
   const int64_t k = tX.dim() - 1;
@@ -816,10 +821,21 @@ int64_t matmul_rows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& t
   TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
   const auto st = statusPointers(status, std::nullopt, 1, dev).first;
   cx.stack(tempMem);
-  floatMatmulRows(*cx.res, floatConfig(floatTypeOf(tX.scalar_type()), false), tIn.data_ptr(), uint32_t(rowWords),
-                  uint32_t(rows), tX.data_ptr(), uint32_t(M), uint64_t(xStride), tOut.data_ptr(),
-                  tOut.scalar_type() == at::kFloat, uint64_t(outStride), st, cx.stream);
+  (tile ? floatMatmulTile : floatMatmulRows)(*cx.res, floatConfig(floatTypeOf(tX.scalar_type()), false), tIn.data_ptr(),
+                                             uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(M),
+                                             uint64_t(xStride), tOut.data_ptr(), tOut.scalar_type() == at::kFloat,
+                                             uint64_t(outStride), st, cx.stream);
   return cx.used();
+}
+
+int64_t matmul_rows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+  return matmulOp(false, tIn, rowWords, tX, tOut, tempMem, status);
+}
+
+int64_t matmul_tile(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                    const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+  return matmulOp(true, tIn, rowWords, tX, tOut, tempMem, status);
 }
 
 // DietGpu.cpp:685-832
@@ -938,6 +954,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "matmul_rows(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, Tensor? temp_mem=None, Tensor? "
       "out_status=None) -> int");
+  m.def(
+      "matmul_tile(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, Tensor? temp_mem=None, Tensor? "
+      "out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -957,4 +976,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("reduce_data", &dietgpu::reduce_data);
   m.impl("gather_rows_sum", &dietgpu::gather_rows_sum);
   m.impl("matmul_rows", &dietgpu::matmul_rows);
+  m.impl("matmul_tile", &dietgpu::matmul_tile);
 }

@@ -25,6 +25,7 @@ validation and return values; "ext": not in the reference.
     reduce_data                       ext   REDUCE_OPS  sums several archives per member in one kernel
     gather_rows_sum                   ext   POOL_OPS    sums bags of rows of a table held by one archive
     matmul_rows                       ext   MATMUL_OPS  x W^T for a few rows of x, W a table held by one archive
+    matmul_tile                       ext   TILE_OPS    the same through the matrix pipe: 1 .. 64 rows, one decode
 """
 import os
 
@@ -66,6 +67,10 @@ POOL_OPS = ("gather_rows_sum",)
 # one archive, out of the decoder's registers: a compressed nn.Linear forward
 MATMUL_OPS = ("matmul_rows",)
 
+# matmul_tile is that product for float16 / bfloat16 through the matrix pipe:
+# every row of x in one pass over the archive
+TILE_OPS = ("matmul_tile",)
+
 _LOADED = False
 
 
@@ -84,7 +89,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS or name in MORE_OPS or name in REDUCE_OPS or name in POOL_OPS or name in MATMUL_OPS:
+    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

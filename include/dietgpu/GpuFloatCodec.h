@@ -364,4 +364,26 @@ void floatMatmulRows(StackDeviceMemory& res,
                      uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
                      hipStream_t stream);
 
+// The same product through the matrix pipe, for 1 <= M <= 64 activation rows
+// in ONE pass over the archive (floatMatmulRows decodes it once per 4 rows):
+// fp16 and bf16 archives alone.  The arguments, the status byte, the alignment
+// rules and the refusals are floatMatmulRows'; an fp32 archive is refused with
+// a message that names floatMatmulRows as its path.
+//   out[m * outRowStrideWords + r] = round_out(sum_k x[m, k] * W[r, k])
+// with exact products, fp32 sums (v_mfma_f32_16x16x32_{f16,bf16}: the hardware
+// fixes the order within 32 words of k) and one rounding.  The order of the
+// adds depends on (rowWords, r) alone: the same bits on every run, for row r
+// whatever other rows the table holds, and for row m whatever M is.  Nothing
+// is promised about equality with floatMatmulRows.  Scratch (4 * M * (numRows
+// + ceil(numRows * rowWords / 4096)) bytes) comes from res; two launches, no
+// host synchronisation, no upload, no atomics: the call can be captured in a
+// graph.
+void floatMatmulTile(StackDeviceMemory& res,
+                     const FloatDecompressConfig& config,
+                     const void* archive_dev, uint32_t rowWords,
+                     uint32_t numRows, const void* x_dev, uint32_t M,
+                     uint64_t xRowStrideWords, void* out_dev, bool outIsFp32,
+                     uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                     hipStream_t stream);
+
 } // namespace dietgpu

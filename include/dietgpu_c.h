@@ -312,9 +312,20 @@ int dietgpu_float_matmul_rows(dietgpu_stack* res, int float_type, int prob_bits,
                               void* out_dev, int out_is_fp32, uint64_t out_row_stride_words,
                               uint8_t* out_success_dev, void* stream);
 
+/* The same product through the matrix pipe (floatMatmulTile, GpuFloatCodec.h):
+ * every argument as dietgpu_float_matmul_rows, float_type 1 or 2 alone, all
+ * 1 <= m <= 64 rows in one pass over the archive.  Exact products, fp32 sums
+ * in an order that depends on row_words and r alone, one rounding; the bits
+ * are not those of dietgpu_float_matmul_rows. */
+int dietgpu_float_matmul_tile(dietgpu_stack* res, int float_type, int prob_bits,
+                              const void* archive_dev, uint32_t row_words, uint32_t num_rows,
+                              const void* x_dev, uint32_t m, uint64_t x_row_stride_words,
+                              void* out_dev, int out_is_fp32, uint64_t out_row_stride_words,
+                              uint8_t* out_success_dev, void* stream);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "decode_gather_sum", "matmul_rows", "hist", "coalesce", "sparse",
+ * "decode_gather", "decode_gather_sum", "matmul_rows", "matmul_tile", "hist", "coalesce", "sparse",
  * "sparse_accumulate", "sparse_reduce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */

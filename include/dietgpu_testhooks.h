@@ -119,6 +119,11 @@ int dietgpu_test_matmul_config(dietgpu_stack* res, int float_type, int use_check
                                uint32_t row_words, uint32_t num_rows, const void* x, uint32_t m, void* out,
                                int out_is_fp32, uint8_t* out_success_dev, void* stream);
 
+/* ... and for the tiled matmul's (floatMatmulTile), with the same arguments. */
+int dietgpu_test_matmul_tile_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                    uint32_t row_words, uint32_t num_rows, const void* x, uint32_t m, void* out,
+                                    int out_is_fp32, uint8_t* out_success_dev, void* stream);
+
 /* The compress plan (csrc/compress_plan.h) of a dense compress call with no
  * caller-counted rows: which compressor takes the batch and what it launches.
  * Enumerations as in that header. */

@@ -1,6 +1,6 @@
 """What a matmul on a compressed weight table costs, bf16,
 R x row_words in {4096 x 4096, 14336 x 4096, 8192 x 8192}, M in {1, 4, 8, 16,
-64}, three candidates alternating inside every window on one device:
+32, 64}, four candidates alternating inside every window on one device:
 
   (a) fused     codec.matmul_rows: k_matmulRows + k_matmulFinish per 4 rows of
                 x, no decoded matrix in memory
@@ -8,15 +8,20 @@ R x row_words in {4096 x 4096, 14336 x 4096, 8192 x 8192}, M in {1, 4, 8, 16,
                 then torch.matmul(x, W.T): the path a user had before
   (c) dense     torch.matmul alone on an uncompressed W: for information, the
                 price of keeping the weights compressed
+  (d) tile      codec.matmul_tile: k_matmulTile +
+                k_matmulFinish, every row of x in one pass through the matrix
+                pipe
 
 Device events around a window's calls; each figure is the median over the
 windows with their min and max, which is the spread to read a difference
 against.  The results are compared first, with the tolerance of
 tests/test_gpu_matmul_rows.py (the two-step and dense products, rounded to
-bf16 by torch, against the fused fp32 one within bf16's rounding on top).
-Prints one JSON line per case and writes them to --out.
+bf16 by torch, against the fp64 product within bf16's rounding on top).
+Prints one JSON line per case and writes them to --out
+(profiles/matmul_rows_bench.json holds the run before (d) existed,
+profiles/matmul_tile_bench.json the one with it).
 
-    usage: python tools/matmul_rows_bench.py [--out profiles/matmul_rows_bench.json]
+    usage: python tools/matmul_rows_bench.py [--out profiles/matmul_tile_bench.json]
 """
 import argparse
 import os
@@ -29,12 +34,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import timing  # noqa: E402  (tools/timing.py, next to this script)
 
 SHAPES = ((4096, 4096), (14336, 4096), (8192, 8192))
-MS = (1, 4, 8, 16, 64)
+MS = (1, 4, 8, 16, 32, 64)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    timing.add_args(ap, "profiles/matmul_rows_bench.json")
+    timing.add_args(ap, "profiles/matmul_tile_bench.json")
     ap.add_argument("--shapes", default=",".join(f"{r}x{k}" for r, k in SHAPES))
     a = ap.parse_args()
 
@@ -55,7 +60,7 @@ def main():
         cases, meta = {}, {}
         for M in MS:
             x = torch.randn([M, rw], generator=g).to(dt).to(dev)
-            out = torch.empty([M, R], dtype=torch.float32, device=dev)
+            out, out4 = (torch.empty([M, R], dtype=torch.float32, device=dev) for _ in range(2))
             ok = torch.empty([1], dtype=torch.uint8, device=dev)
             y2, y3 = (torch.empty([M, R], dtype=dt, device=dev) for _ in range(2))
 
@@ -69,16 +74,20 @@ def main():
             def dense(x=x, y=y3):
                 torch.matmul(x, W.T, out=y)
 
-            fused(), two_step(), dense()
+            def tile(x=x, out=out4, ok=ok):
+                C.matmul_tile(archive, rw, x, dt, out=out, out_status=ok, ws=ws)
+
+            fused(), two_step(), dense(), tile()
             torch.cuda.synchronize()
             assert int(ok) == 1 and torch.equal(tmp.view(torch.int16), W.view(torch.int16))
             xd, Wd = x.double(), W.double()
             ref, mag = xd @ Wd.T, xd.abs() @ Wd.abs().T
             bound = rw * 2.0 ** -23 * mag
-            assert bool(((out.double() - ref).abs() <= bound).all()), (shape, M)
+            for y in (out, out4):
+                assert bool(((y.double() - ref).abs() <= bound).all()), (shape, M)
             for y in (y2, y3):  # torch's own order and bf16 rounding on top
                 assert bool(((y.double() - ref).abs() <= 2 * bound + 2.0 ** -8 * ref.abs()).all()), (shape, M)
-            for path, f in (("fused", fused), ("two_step", two_step), ("dense", dense)):
+            for path, f in (("fused", fused), ("two_step", two_step), ("dense", dense), ("tile", tile)):
                 key = f"bf16_{shape}_M{M}_{path}"
                 cases[key] = (f, a.calls)
                 meta[key] = {"dtype": "bf16", "rows": R, "row_words": rw, "M": M, "path": path,
@@ -89,9 +98,10 @@ def main():
             line = {"case": key, **meta[key], **timing.summary(times[key]["stream"], "stream_us"),
                     "windows": a.windows, "archive_bytes": int(sizes[0]), "dense_bytes": R * rw * 2,
                     "device": torch.cuda.get_device_name(0)}
-            if key.endswith("_fused"):
-                base = statistics.median(times[key[:-6] + "_two_step"]["stream"])
-                line["fused_vs_two_step"] = round(statistics.median(times[key]["stream"]) / base, 4)
+            stem, path = key.rsplit("_", 1) if not key.endswith("_two_step") else (key[:-9], "two_step")
+            if path in ("fused", "tile"):
+                base = statistics.median(times[stem + "_two_step"]["stream"])
+                line[path + "_vs_two_step"] = round(statistics.median(times[key]["stream"]) / base, 4)
             lines.append(line)
         del cases, W, arch2d, archive, tmp
         torch.cuda.empty_cache()
