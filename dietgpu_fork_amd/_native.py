@@ -95,6 +95,10 @@ def _declare(L):
                                               P, P]),
         "dietgpu_float_matmul_tile": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int, c_u64,
                                               P, P]),
+        "dietgpu_float_matmul_grouped": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, c_u32, P, c_u32, c_u64, P, c_int,
+                                                 P, c_int, c_u64, P, P]),
+        "dietgpu_float_matmul_grouped_scratch_bytes": (c_u64, [c_u32, c_u32, c_u32, c_u32]),
+        "dietgpu_set_matmul_grouped_grid": (None, [c_u32]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),
@@ -144,6 +148,8 @@ def testlib():
                "dietgpu_test_matmul_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, c_u32, P, c_int, P, P]),
                "dietgpu_test_matmul_tile_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, c_u32, P, c_int, P,
                                                            P]),
+               "dietgpu_test_matmul_grouped_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, c_u32, P, c_u32, P, P,
+                                                              c_int, P, P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
                "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
                "dietgpu_test_sparse_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_int, P, c_u32, c_int, P,

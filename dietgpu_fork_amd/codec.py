@@ -690,6 +690,121 @@ def matmul_tile(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
                        prob_bits=prob_bits, check=check, _tile=True)
 
 
+MATMUL_GROUP_MAX_EXPERTS = 1024
+
+
+def set_matmul_grouped_grid(workgroups):
+    """Test / tuning hook: the most workgroups matmul_grouped's main kernel is
+    launched with (0: the plan's own grid, the default).  A small value makes
+    one workgroup cross from expert to expert.  The results are the same bits."""
+    N.lib().dietgpu_set_matmul_grouped_grid(int(workgroups))
+
+
+def archive_ptrs(archives):
+    """The int64 CUDA tensor [E] of the archives' device addresses that
+    matmul_grouped takes; build it once at load time and keep the archives
+    alive beside it."""
+    if not archives or not all(isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.uint8 for a in archives):
+        raise ValueError("archive_ptrs: a non-empty list of uint8 CUDA tensors")
+    return torch.tensor([a.data_ptr() for a in archives], dtype=torch.int64, device=archives[0].device)
+
+
+def matmul_grouped(archive_ptrs, row_words, x, offsets, dtype, out=None, out_dtype=None, out_status=None, ws=None,
+                   prob_bits=10, check=False):
+    """matmul_tile over E expert tables in one call (a mixture-of-experts
+    layer) -> (out [T, R], ok [E]).  archive_ptrs is a CUDA int64 tensor [E] of
+    the device addresses of E dense float16 / bfloat16 archives of `dtype`
+    (codec.archive_ptrs), each a table W_e [R, row_words]; x [T, row_words] of
+    `dtype` holds the rows ordered by expert and offsets [E + 1] (CUDA int32 or
+    int64) their boundaries: expert e owns rows offsets[e] .. offsets[e + 1] - 1
+    and out[t] = x[t] @ W_e.T for each of them.  Alignment and stride rules are
+    matmul_tile's; row_words is a multiple of 256.  R is out.size(1) when `out`
+    is given; without one it is read from archive 0's header, which
+    synchronises the stream once.
+    An expert's rows are served 64 at a time, each such chunk decoding the
+    archive again, and rows offsets[e] + 64 c .. of chunk c carry exactly the
+    bits of matmul_tile(archive_e, x[those rows]): a row sits at the same place
+    16 * wave + i of its tile in both calls and meets the same segments and
+    pieces in the same order.
+    ok[e] is 1 iff archive e matches dtype / prob_bits and holds R * row_words
+    words; a failing expert's rows of `out` are untouched and every other
+    expert is served.  An expert with no rows costs no decode.  Rows of `out`
+    below offsets[0] or at or past offsets[E] are untouched.  Offsets that decrease, start below 0
+    or end above T set every ok[e] to 0 and write nothing else.
+    The routing is read on the device alone: nothing is uploaded or read back
+    (three launches, scratch from `ws`), so the call can be captured in a graph
+    and replayed on new x, new offsets and new archive bytes.  check=True reads
+    ok back and raises DietGpuError."""
+    who = "matmul_grouped"
+    if dtype == torch.uint8:
+        raise ValueError(f"{who}: byte archives hold no floats to multiply")
+    if dtype == torch.float32:
+        raise ValueError(f"{who}: float32 archives go through matmul_rows (the matrix pipe multiplies 16-bit words)")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16 or bfloat16 archives)")
+    row_words = int(row_words)
+    if row_words < 1 or row_words % 256:
+        raise ValueError(f"{who}: row_words must be a positive multiple of 256 (pad the rows with zeros)")
+    p = archive_ptrs
+    if not (isinstance(p, torch.Tensor) and p.dtype == torch.int64 and p.dim() == 1 and p.is_contiguous()):
+        raise ValueError(f"{who}: archive_ptrs must be a contiguous 1-d int64 tensor (codec.archive_ptrs)")
+    E = p.numel()
+    if not 1 <= E <= MATMUL_GROUP_MAX_EXPERTS:
+        raise ValueError(f"{who}: archive_ptrs must hold 1 .. {MATMUL_GROUP_MAX_EXPERTS} addresses, not {E}")
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == dtype and x.size(0) >= 1):
+        raise ValueError(f"{who}: x must be a 2-d {dtype} tensor [T, row_words], T >= 1")
+    if x.size(1) != row_words:
+        raise ValueError(f"{who}: x must have row_words = {row_words} columns, not {x.size(1)}")
+    T = x.size(0)
+    if not (isinstance(offsets, torch.Tensor) and offsets.dtype in (torch.int32, torch.int64) and offsets.dim() == 1
+            and offsets.is_contiguous()):
+        raise ValueError(f"{who}: offsets must be a contiguous 1-d int32 or int64 tensor")
+    if offsets.numel() != E + 1:
+        raise ValueError(f"{who}: offsets must hold E + 1 = {E + 1} entries, not {offsets.numel()}")
+    out_dtype = out_dtype if out_dtype is not None else (out.dtype if out is not None else dtype)
+    if out_dtype not in (dtype, torch.float32):
+        raise ValueError(f"{who}: out dtype {out_dtype} does not go with {dtype} archives (their own dtype, or "
+                         "torch.float32)")
+    x_stride = x.stride(0) if T > 1 else row_words
+    if x.stride(1) != 1 or x_stride < row_words or (x_stride * x.element_size()) % 16 or x.data_ptr() % 16:
+        raise ValueError(f"{who}: x's rows must be contiguous, 16-byte aligned and a whole number of 16 B apart")
+    if not (x.is_cuda and p.is_cuda and offsets.is_cuda and p.device == x.device and offsets.device == x.device):
+        raise ValueError(f"{who}: archive_ptrs, x and offsets must be CUDA tensors on one device")
+    ws = _ws(ws, x.device)
+    if out is None:  # archive 0's element size, from its header on the device
+        info = torch.zeros([2], dtype=torch.int32, device=x.device)
+        N.check(N.lib().dietgpu_float_get_compressed_info_device(ws.h, p.data_ptr(), 1, info[0:].data_ptr(),
+                                                                 info[1:].data_ptr(), None, _s()))
+        n, ft0 = (int(v) & 0xFFFFFFFF for v in info.tolist())
+        if ft0 != FLOAT_TYPE[dtype] or n < row_words:
+            raise N.DietGpuError(f"{who}: archive 0 is no {dtype} archive of at least one row of {row_words} words, so "
+                                 "it does not give R; pass `out`")
+        out = torch.empty([T, n // row_words], dtype=out_dtype, device=x.device)
+    if out.dim() != 2 or out.size(0) != T or out.size(1) < 1 or out.dtype != out_dtype or out.device != x.device:
+        raise ValueError(f"{who}: out must be a {out_dtype} tensor of shape [{T}, R], R >= 1, on x's device")
+    rows = out.size(1)
+    if rows * row_words >= 1 << 32:
+        raise ValueError(f"{who}: R * row_words must be below 2^32")
+    out_stride = out.stride(0) if T > 1 else rows
+    if (rows != 1 and out.stride(1) != 1) or out_stride < rows:
+        raise ValueError(f"{who}: out's last dimension must be contiguous and its rows at least R apart")
+    ok = out_status if out_status is not None else torch.empty([E], dtype=torch.uint8, device=x.device)
+    if not (ok.dtype == torch.uint8 and ok.is_contiguous() and list(ok.shape) == [E] and ok.device == x.device):
+        raise ValueError(f"{who}: out_status must be a contiguous uint8 tensor of {E} entries")
+    N.check(N.lib().dietgpu_float_matmul_grouped(
+        ws.h, FLOAT_TYPE[dtype], prob_bits, p.data_ptr(), E, row_words, rows, x.data_ptr(), T, x_stride,
+        offsets.data_ptr(), int(offsets.dtype == torch.int64), out.data_ptr(), int(out_dtype == torch.float32),
+        out_stride, ok.data_ptr(), _s()))
+    if check and not bool(ok.all()):
+        bad = (ok == 0).nonzero().flatten().tolist()
+        why = (f"archive(s) {bad[:8]} do not match dtype / prob_bits or hold fewer than {rows} rows of {row_words} "
+               "words")
+        if len(bad) == E:  # the one case in which bad offsets can be the cause
+            why = f"the offsets are not ascending inside 0 .. {T}, or all " + why
+        raise N.DietGpuError(f"{who}: {why}")
+    return out, ok
+
+
 def sparse_compress(ts, ft=None, prob_bits=10, checksum=False, ws=None):
     ft = ft or FLOAT_TYPE[ts[0].dtype]
     return _pointer_compress(N.lib().dietgpu_float_compress_sparse, (ft, prob_bits, int(checksum)), ts,

@@ -456,6 +456,31 @@ int dietgpu_float_matmul_tile(dietgpu_stack* res, int ft, int pb, const void* ar
   });
 }
 
+int dietgpu_float_matmul_grouped(dietgpu_stack* res, int ft, int pb, const void* archives_dev, uint32_t num_experts,
+                                 uint32_t row_words, uint32_t num_rows, const void* x_dev, uint32_t t,
+                                 uint64_t x_row_stride, const void* offsets_dev, int offsets_are_64, void* out_dev,
+                                 int out_is_fp32, uint64_t out_row_stride, uint8_t* succ, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at, as dietgpu_float_matmul_rows)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkProbBits(pb);
+    checkMatmulGroupedShape(ft, out_is_fp32 != 0, row_words, num_rows, num_experts, t, x_row_stride, out_row_stride);
+    floatMatmulGrouped(R(res), cfg, archives_dev, num_experts, row_words, num_rows, x_dev, t, x_row_stride,
+                       offsets_dev, offsets_are_64 != 0, out_dev, out_is_fp32 != 0, out_row_stride, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
+uint64_t dietgpu_float_matmul_grouped_scratch_bytes(uint32_t num_experts, uint32_t row_words, uint32_t num_rows,
+                                                    uint32_t t) {
+  uint64_t v = 0;
+  guarded([&] {
+    v = floatMatmulGroupedScratchBytes(num_experts, row_words, num_rows, t);
+    return DIETGPU_OK;
+  });
+  return v;
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {
@@ -479,6 +504,7 @@ void dietgpu_set_barrier_budget(uint32_t ticks) { setBarrierBudget(ticks); }
 void dietgpu_set_dispatch_skew(uint32_t ticks) { setDispatchSkew(ticks); }
 void dietgpu_set_compress_path(int mode) { setCompressPath(mode < 0 || mode > 2 ? 0 : mode); }
 void dietgpu_set_reduce_max_sources(uint32_t sources) { setReduceMaxSources(sources); }
+void dietgpu_set_matmul_grouped_grid(uint32_t workgroups) { setMatmulGroupedGrid(workgroups); }
 
 void dietgpu_profile_enable(int on) { prof::setEnabled(on != 0); }
 void dietgpu_profile_filter(const char* kernel) { prof::setFilter(kernel); }

@@ -216,6 +216,48 @@ inline MatmulTilePlan planMatmulTile(uint32_t numRows, uint32_t rowWords, uint32
   return p;
 }
 
+// The scratch and grid rule of the grouped matmul (matmul_grouped.h; DESIGN.md
+// 5.2l): E tables of numRows x rowWords words, T activation rows dealt to them
+// by offsets that only the device knows.  An entry is an expert's next <= 64
+// rows, so there are at most E + T / 64 of them; the task line is entries x
+// groups, groups and period planMatmulTile's for one table, and the grid is
+// sized by the bound.  The scratch holds, each 16 B-aligned: the head words,
+// one status byte per expert, the entry list (16 B each) and 4 * T * pieces
+// bytes of partials.
+constexpr uint32_t kMatmulGroupMaxExperts = 1024;  // four thread rounds of k_matmulGroupPlan's one workgroup
+
+struct MatmulGroupedPlan {
+  bool valid;  // planMatmulTile's rule for one table, 1 <= E <= 1024, T >= 1, T * pieces and the task bound < 2^32
+  uint32_t period, groups, pieces;  // planMatmulTile's
+  uint32_t entryBound;              // E + T / 64
+  uint64_t statusOffset, entriesOffset, partOffset;  // bytes into the scratch; the head is at 0
+  uint64_t partialBytes;            // the whole scratch
+  uint32_t gridX;                   // persistent workgroups of k_matmulTileGrouped
+};
+
+// slots: as planGather's.  gridCap: dietgpu_set_matmul_grouped_grid (0: none).
+inline MatmulGroupedPlan planMatmulGrouped(uint32_t E, uint32_t numRows, uint32_t rowWords, uint32_t T, uint32_t slots,
+                                           uint32_t gridCap) {
+  MatmulGroupedPlan p{};
+  const MatmulTilePlan one = planMatmulTile(numRows, rowWords, 1, 1);
+  if (!one.valid || E < 1 || E > kMatmulGroupMaxExperts || T < 1) return p;
+  p.period = one.period;
+  p.groups = one.groups;
+  p.pieces = one.pieces;
+  p.entryBound = E + T / kMatmulMaxRows;
+  const uint64_t tasks = uint64_t(p.entryBound) * p.groups;
+  if (uint64_t(T) * p.pieces >= (1ull << 32) || tasks >= (1ull << 32)) return p;
+  p.valid = true;
+  auto up16 = [](uint64_t v) { return (v + 15) / 16 * 16; };
+  p.statusOffset = 16;
+  p.entriesOffset = p.statusOffset + up16(E);
+  p.partOffset = p.entriesOffset + 16ull * p.entryBound;
+  p.partialBytes = p.partOffset + 4ull * T * p.pieces;
+  p.gridX = uint32_t(std::min<uint64_t>(std::max(1u, slots), tasks));
+  if (gridCap) p.gridX = std::min(p.gridX, gridCap);
+  return p;
+}
+
 // The pass rule of the fused reduce (k_reduce, reduce.h; DESIGN.md 5.2g;
 // tests/test_reduce_plan.py): K sources, at most nsMax per launch.  The
 // sources go to the passes in order, evenly (the larger passes first: fewer

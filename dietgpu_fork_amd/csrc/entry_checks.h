@@ -145,4 +145,19 @@ inline void checkMatmulTileShape(int floatType, bool outIsFp32, uint32_t rowWord
   checkMatmulShape(floatType, outIsFp32, rowWords, numRows, M, xRowStrideWords, outRowStrideWords);
 }
 
+// The grouped matmul (floatMatmulGrouped): checkMatmulTileShape's refusals for
+// one table first (any number of rows T: an expert's rows go 64 at a time),
+// then 1 .. 1024 experts, T >= 1 and partials that 32-bit indices reach.  The C
+// ABI makes the same checks before it looks at the stack or any pointer.
+inline void checkMatmulGroupedShape(int floatType, bool outIsFp32, uint32_t rowWords, uint32_t numRows,
+                                    uint32_t numExperts, uint32_t T, uint64_t xRowStrideWords,
+                                    uint64_t outRowStrideWords) {
+  checkMatmulTileShape(floatType, outIsFp32, rowWords, numRows, 1, xRowStrideWords, outRowStrideWords);
+  DG_CHECK(numExperts >= 1 && numExperts <= kMatmulGroupMaxExperts,
+           "numExperts (" << numExperts << ") must be in 1 .. " << kMatmulGroupMaxExperts);
+  DG_CHECK(T >= 1, "T must be at least 1 (x holds no row)");
+  DG_CHECK(planMatmulGrouped(numExperts, numRows, rowWords, T, 1, 0).valid,
+           "T (" << T << ") rows of numRows + blocks partial sums each must stay below 2^32 words");
+}
+
 }  // namespace dietgpu

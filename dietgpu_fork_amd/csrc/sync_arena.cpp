@@ -57,6 +57,9 @@ int compressPath() { return gCompressPath.load(); }
 std::atomic<uint32_t> gReduceMaxSources{0};
 void setReduceMaxSources(uint32_t ns) { gReduceMaxSources.store(ns); }
 uint32_t reduceMaxSources() { return gReduceMaxSources.load(); }
+std::atomic<uint32_t> gMatmulGroupedGrid{0};
+void setMatmulGroupedGrid(uint32_t workgroups) { gMatmulGroupedGrid.store(workgroups); }
+uint32_t matmulGroupedGrid() { return gMatmulGroupedGrid.load(); }
 
 SyncLease::SyncLease(StackDeviceMemory& res, hipStream_t stream, const size_t (&bytesIn)[kSyncRegions],
                      bool dequeue, size_t rowsBytes) {

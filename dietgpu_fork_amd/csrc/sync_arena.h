@@ -120,4 +120,11 @@ int compressPath();
 void setReduceMaxSources(uint32_t ns);
 uint32_t reduceMaxSources();
 
+// Test / tuning hook: the most workgroups k_matmulTileGrouped is launched with
+// (matmul_grouped.h); 0 (default) means the plan's (planMatmulGrouped,
+// decode_plan.h).  A small value makes one workgroup cross several entries.
+// Results are the same bits whatever the value.
+void setMatmulGroupedGrid(uint32_t workgroups);
+uint32_t matmulGroupedGrid();
+
 }  // namespace dietgpu

@@ -25,6 +25,7 @@
 //   gather_rows_sum                   ext   floatGatherRowsSum (*)
 //   matmul_rows                       ext   floatMatmulRows
 //   matmul_tile                       ext   floatMatmulTile
+//   matmul_grouped                    ext   floatMatmulGrouped
 //   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
@@ -838,6 +839,61 @@ int64_t matmul_tile(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& t
   return matmulOp(true, tIn, rowWords, tX, tOut, tempMem, status);
 }
 
+// Extension (no reference counterpart): matmul_tile over many expert tables in
+// one task line (floatMatmulGrouped).  t_archives [E] holds the int64 device
+// addresses of E archives W_e [R, row_words] of t_x's dtype (float16 or
+// bfloat16); t_x [T, row_words] holds the rows ordered by expert and t_offsets
+// [E + 1] (int32 or int64, on the device) their boundaries; t_out [T, R] takes
+// the products in t_x's dtype or float32.  out_status[e] = 1 iff archive e is
+// valid: a failing expert's rows of t_out are left untouched, as are rows at
+// or past t_offsets[E]; bad offsets set every status to 0.  The routing is
+// read on the device alone.  The checks that need no device come first.
+int64_t matmul_grouped(const at::Tensor& tArchives, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOffsets,
+                       const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
+                       const std::optional<at::Tensor>& status) {
+  TORCH_CHECK(rowWords >= 1 && rowWords % 256 == 0 && uint64_t(rowWords) <= kU32Max,
+              "row_words must be a positive multiple of 256 (pad the rows with zeros), not ", rowWords);
+  TORCH_CHECK(tX.scalar_type() == at::kHalf || tX.scalar_type() == at::kBFloat16,
+              "matmul_grouped multiplies float16 or bfloat16 words, not ", tX.scalar_type());
+  TORCH_CHECK(tOut.scalar_type() == tX.scalar_type() || tOut.scalar_type() == at::kFloat, "t_out must have t_x's dtype (",
+              tX.scalar_type(), ") or float32, not ", tOut.scalar_type());
+  TORCH_CHECK(tArchives.scalar_type() == at::kLong && tArchives.dim() == 1 && tArchives.is_contiguous(),
+              "t_archives must be a contiguous 1-d int64 tensor of device addresses");
+  const int64_t E = tArchives.numel();
+  TORCH_CHECK(E >= 1 && E <= int64_t(kMatmulGroupMaxExperts), "t_archives must hold 1 .. ", kMatmulGroupMaxExperts,
+              " addresses, not ", E);
+  TORCH_CHECK((tOffsets.scalar_type() == at::kInt || tOffsets.scalar_type() == at::kLong) && tOffsets.dim() == 1 &&
+                  tOffsets.is_contiguous() && tOffsets.numel() == E + 1,
+              "t_offsets must be a contiguous 1-d int32 or int64 tensor of t_archives.numel() + 1 = ", E + 1,
+              " entries");
+  TORCH_CHECK(tX.dim() == 2 && tX.size(1) == rowWords && tX.size(0) >= 1 && uint64_t(tX.size(0)) <= kU32Max,
+              "t_x must have the shape [T, row_words] = [T >= 1, ", rowWords, "], not ", tX.sizes());
+  const int64_t T = tX.size(0);
+  TORCH_CHECK(tOut.dim() == 2 && tOut.size(0) == T && tOut.size(1) >= 1, "t_out must have the shape [", T,
+              ", R], R >= 1, not ", tOut.sizes());
+  const int64_t rows = tOut.size(1);
+  TORCH_CHECK(uint64_t(rows) * uint64_t(rowWords) <= kU32Max, "R * row_words must be below 2^32");
+  TORCH_CHECK(tX.stride(1) == 1 && (rows == 1 || tOut.stride(1) == 1),
+              "t_x's and t_out's last dimension must be contiguous");
+  const int64_t xStride = T > 1 ? tX.stride(0) : rowWords, outStride = T > 1 ? tOut.stride(0) : rows;
+  TORCH_CHECK(xStride >= rowWords && outStride >= rows, "t_x's and t_out's rows must not overlap");
+  TORCH_CHECK(xStride * tX.element_size() % 16 == 0 && reinterpret_cast<uintptr_t>(tX.data_ptr()) % 16 == 0,
+              "t_x's rows must be 16-byte aligned (its data pointer and its row stride in bytes)");
+  TORCH_CHECK(tX.device().type() == at::kCUDA, "t_x must be a GPU tensor (on the archives' device)");
+  const int dev = tX.get_device();
+  for (const at::Tensor* t : {&tArchives, &tOffsets, &tOut})
+    TORCH_CHECK(t->device().type() == at::kCUDA && t->get_device() == dev,
+                "t_archives, t_offsets and t_out must be on t_x's device");
+  CallContext cx(dev);
+  const auto st = statusPointers(status, std::nullopt, E, dev).first;
+  cx.stack(tempMem);
+  floatMatmulGrouped(*cx.res, floatConfig(floatTypeOf(tX.scalar_type()), false), tArchives.data_ptr(), uint32_t(E),
+                     uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(T), uint64_t(xStride),
+                     tOffsets.data_ptr(), tOffsets.scalar_type() == at::kLong, tOut.data_ptr(),
+                     tOut.scalar_type() == at::kFloat, uint64_t(outStride), st, cx.stream);
+  return cx.used();
+}
+
 // DietGpu.cpp:685-832
 int64_t decompress_data_split_size(bool asFloat, const std::vector<at::Tensor>& tsIn, const at::Tensor& tOut,
                                    const at::Tensor& tSplit, bool checksum, const std::optional<at::Tensor>& tempMem,
@@ -957,6 +1013,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "matmul_tile(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, Tensor? temp_mem=None, Tensor? "
       "out_status=None) -> int");
+  m.def(
+      "matmul_grouped(Tensor t_archives, int row_words, Tensor t_x, Tensor t_offsets, Tensor t_out, Tensor? "
+      "temp_mem=None, Tensor? out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -977,4 +1036,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("gather_rows_sum", &dietgpu::gather_rows_sum);
   m.impl("matmul_rows", &dietgpu::matmul_rows);
   m.impl("matmul_tile", &dietgpu::matmul_tile);
+  m.impl("matmul_grouped", &dietgpu::matmul_grouped);
 }

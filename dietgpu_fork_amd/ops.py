@@ -26,6 +26,7 @@ validation and return values; "ext": not in the reference.
     gather_rows_sum                   ext   POOL_OPS    sums bags of rows of a table held by one archive
     matmul_rows                       ext   MATMUL_OPS  x W^T for a few rows of x, W a table held by one archive
     matmul_tile                       ext   TILE_OPS    the same through the matrix pipe: 1 .. 64 rows, one decode
+    matmul_grouped                    ext   GROUP_OPS   matmul_tile over many expert tables, routed on the device
 """
 import os
 
@@ -71,6 +72,10 @@ MATMUL_OPS = ("matmul_rows",)
 # every row of x in one pass over the archive
 TILE_OPS = ("matmul_tile",)
 
+# matmul_grouped is matmul_tile over many expert tables in one task line, the
+# routing read on the device: a compressed mixture-of-experts layer
+GROUP_OPS = ("matmul_grouped",)
+
 _LOADED = False
 
 
@@ -89,7 +94,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS:
+    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

@@ -386,4 +386,42 @@ void floatMatmulTile(StackDeviceMemory& res,
                      uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
                      hipStream_t stream);
 
+// floatMatmulTile over numExperts weight tables in one task line (a mixture of
+// experts): archives_dev holds numExperts device addresses (8 B each, in
+// device memory) of dense fp16 / bf16 archives, each W_e [numRows, rowWords],
+// all of config's type and precision.  x_dev holds T rows ordered by expert,
+// and offsets_dev numExperts + 1 boundaries (int32, or int64 when
+// offsetsAre64) in device memory: expert e owns rows offsets[e] ..
+// offsets[e + 1] - 1.  For each of them
+//   out[t * outRowStrideWords + r] = round_out(sum_k x[t, k] * W_e[r, k])
+// An expert's rows are served 64 at a time (each such chunk decodes the
+// archive again), and rows offsets[e] + 64 c .. of chunk c carry the bits of
+// floatMatmulTile(archive e, those rows): a row sits at the same place of its
+// tile in both calls and meets the same segments and pieces in the same order.
+// outSuccess_dev[e] (optional, numExperts bytes) = 1 iff archive e is 4 B-
+// aligned and valid for this config and numRows * rowWords words fit its
+// element; the rows of a failing expert are left untouched and every other
+// expert is served.  An expert with no rows costs no decode.  Rows of out below
+// offsets[0] or at or past offsets[numExperts] are untouched.  Offsets that decrease, start
+// below 0 or end above T set every status to 0 and nothing else is written.
+// Three launches; the routing is read on the device alone: no host table, no
+// upload, no read-back, no atomics, no wait between workgroups, scratch
+// (floatMatmulGroupedScratchBytes) from res.  The call can be captured in a
+// graph and replayed on new x, new offsets and new archive bytes.
+// Refused before any launch: floatMatmulTile's refusals for one table (its M
+// apart), numExperts outside 1 .. 1024, T == 0, T * (numRows + blocks) >= 2^32.
+void floatMatmulGrouped(StackDeviceMemory& res,
+                        const FloatDecompressConfig& config,
+                        const void* archives_dev, uint32_t numExperts,
+                        uint32_t rowWords, uint32_t numRows, const void* x_dev,
+                        uint32_t T, uint64_t xRowStrideWords,
+                        const void* offsets_dev, bool offsetsAre64,
+                        void* out_dev, bool outIsFp32,
+                        uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                        hipStream_t stream);
+
+// The scratch bytes floatMatmulGrouped takes from res for such a call.
+uint64_t floatMatmulGroupedScratchBytes(uint32_t numExperts, uint32_t rowWords,
+                                        uint32_t numRows, uint32_t T);
+
 } // namespace dietgpu

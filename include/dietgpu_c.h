@@ -39,6 +39,8 @@
  *   into one output row: embedding_bag(mode="sum"); one launch)
  *   dietgpu_float_matmul_rows (y = x W^T for up to 64 rows of x against a
  *   weight table held by one archive; the decoded matrix is never stored)
+ *   dietgpu_float_matmul_grouped (that product over many expert tables in one
+ *   task line, the routing read on the device)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -323,9 +325,33 @@ int dietgpu_float_matmul_tile(dietgpu_stack* res, int float_type, int prob_bits,
                               void* out_dev, int out_is_fp32, uint64_t out_row_stride_words,
                               uint8_t* out_success_dev, void* stream);
 
+/* dietgpu_float_matmul_tile over num_experts tables in one task line
+ * (floatMatmulGrouped, GpuFloatCodec.h): archives_dev holds num_experts device
+ * addresses (8 B each) of archives W_e [num_rows, row_words], x_dev t rows
+ * ordered by expert, offsets_dev num_experts + 1 boundaries (int32, int64 when
+ * offsets_are_64), all in device memory; expert e owns rows offsets[e] ..
+ * offsets[e + 1] - 1, served 64 at a time with the bits of
+ * dietgpu_float_matmul_tile on that archive and those rows.
+ * out_success_dev[e] (optional, num_experts bytes) = 1 iff archive e is valid;
+ * a failing expert's rows of out_dev are untouched, as are rows below
+ * offsets[0] or at or past offsets[num_experts]; bad offsets set every status to 0 and write nothing
+ * else.  float_type 1 or 2, 1 <= num_experts <= 1024, t >= 1.  Scratch
+ * (dietgpu_float_matmul_grouped_scratch_bytes) comes from res; no host
+ * synchronisation, no upload.  No checksum flag. */
+int dietgpu_float_matmul_grouped(dietgpu_stack* res, int float_type, int prob_bits,
+                                 const void* archives_dev, uint32_t num_experts, uint32_t row_words,
+                                 uint32_t num_rows, const void* x_dev, uint32_t t,
+                                 uint64_t x_row_stride_words, const void* offsets_dev,
+                                 int offsets_are_64, void* out_dev, int out_is_fp32,
+                                 uint64_t out_row_stride_words, uint8_t* out_success_dev,
+                                 void* stream);
+/* ... and its scratch bytes; 0 for a shape the call refuses (dietgpu_last_error) */
+uint64_t dietgpu_float_matmul_grouped_scratch_bytes(uint32_t num_experts, uint32_t row_words,
+                                                    uint32_t num_rows, uint32_t t);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
- * "decode_gather", "decode_gather_sum", "matmul_rows", "matmul_tile", "hist", "coalesce", "sparse",
+ * "decode_gather", "decode_gather_sum", "matmul_rows", "matmul_tile", "matmul_grouped", "hist", "coalesce", "sparse",
  * "sparse_accumulate", "sparse_reduce") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
@@ -385,6 +411,11 @@ void dietgpu_set_compress_path(int mode);
  * The fused sparse reduce's kernel obeys the same cap.  Results are the same
  * bits whatever the value. */
 void dietgpu_set_reduce_max_sources(uint32_t sources);
+/* Test / tuning hook: the most workgroups the grouped matmul's main kernel is
+ * launched with; 0 (default) means the plan's own grid.  A small value makes
+ * one workgroup cross from expert to expert on small tables.  Results are the
+ * same bits whatever the value. */
+void dietgpu_set_matmul_grouped_grid(uint32_t workgroups);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,14 @@ int dietgpu_test_matmul_tile_config(dietgpu_stack* res, int float_type, int use_
                                     uint32_t row_words, uint32_t num_rows, const void* x, uint32_t m, void* out,
                                     int out_is_fp32, uint8_t* out_success_dev, void* stream);
 
+/* ... and for the grouped matmul's (floatMatmulGrouped): num_experts archive
+ * addresses at archives, t rows at x (stride row_words), num_experts + 1 int64
+ * offsets, out [t, num_rows]. */
+int dietgpu_test_matmul_grouped_config(dietgpu_stack* res, int float_type, int use_checksum, const void* archives,
+                                       uint32_t num_experts, uint32_t row_words, uint32_t num_rows, const void* x,
+                                       uint32_t t, const void* offsets, void* out, int out_is_fp32,
+                                       uint8_t* out_success_dev, void* stream);
+
 /* The compress plan (csrc/compress_plan.h) of a dense compress call with no
  * caller-counted rows: which compressor takes the batch and what it launches.
  * Enumerations as in that header. */
