@@ -99,6 +99,7 @@ def _declare(L):
                                                  P, c_int, c_u64, P, P]),
         "dietgpu_float_matmul_grouped_scratch_bytes": (c_u64, [c_u32, c_u32, c_u32, c_u32]),
         "dietgpu_set_matmul_grouped_grid": (None, [c_u32]),
+        "dietgpu_set_matmul_grid": (None, [c_u32]),
         "dietgpu_profile_enable": (None, [c_int]),
         "dietgpu_profile_filter": (None, [ctypes.c_char_p]),
         "dietgpu_profile_reset": (None, []),
@@ -107,7 +108,7 @@ def _declare(L):
     }
     # test hooks absent from older builds (same-box A/B of earlier libraries)
     optional = {"dietgpu_set_barrier_budget", "dietgpu_set_dispatch_skew",
-                "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path"}
+                "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path", "dietgpu_set_matmul_grid"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue

@@ -684,10 +684,20 @@ def matmul_tile(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     exact, the sums fp32 in an order that depends on (row_words, r) alone --
     the same bits on every run, for row r whatever other rows the table holds,
     for row m whatever M is -- rounded once to out's dtype.  The bits are not
-    those of matmul_rows.  Two launches, scratch (4 * M * (R + blocks) bytes)
+    those of matmul_rows.  Denormal words of x and W multiply as their values
+    and a denormal fp32 sum stays one (the matrix pipe flushes nothing); an Inf
+    or NaN in x stays in its row of out, one in W in its column.  Two launches, scratch (4 * M * (R + blocks) bytes)
     from `ws`; the call can be captured in a graph."""
     return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
                        prob_bits=prob_bits, check=check, _tile=True)
+
+
+def set_matmul_grid(workgroups):
+    """Test / tuning hook: the most workgroups the main kernels of matmul_rows
+    and matmul_tile are launched with (0: the plan's own grid, the default).  A
+    small value makes one workgroup take several task groups.  The results are
+    the same bits."""
+    N.lib().dietgpu_set_matmul_grid(int(workgroups))
 
 
 MATMUL_GROUP_MAX_EXPERTS = 1024
@@ -725,7 +735,8 @@ def matmul_grouped(archive_ptrs, row_words, x, offsets, dtype, out=None, out_dty
     archive again, and rows offsets[e] + 64 c .. of chunk c carry exactly the
     bits of matmul_tile(archive_e, x[those rows]): a row sits at the same place
     16 * wave + i of its tile in both calls and meets the same segments and
-    pieces in the same order.
+    pieces in the same order.  Denormals are kept as in matmul_tile, and an Inf
+    or NaN in one expert's table reaches that expert's rows alone.
     ok[e] is 1 iff archive e matches dtype / prob_bits and holds R * row_words
     words; a failing expert's rows of `out` are untouched and every other
     expert is served.  An expert with no rows costs no decode.  Rows of `out`

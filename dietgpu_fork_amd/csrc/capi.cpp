@@ -505,6 +505,7 @@ void dietgpu_set_dispatch_skew(uint32_t ticks) { setDispatchSkew(ticks); }
 void dietgpu_set_compress_path(int mode) { setCompressPath(mode < 0 || mode > 2 ? 0 : mode); }
 void dietgpu_set_reduce_max_sources(uint32_t sources) { setReduceMaxSources(sources); }
 void dietgpu_set_matmul_grouped_grid(uint32_t workgroups) { setMatmulGroupedGrid(workgroups); }
+void dietgpu_set_matmul_grid(uint32_t workgroups) { setMatmulGrid(workgroups); }
 
 void dietgpu_profile_enable(int on) { prof::setEnabled(on != 0); }
 void dietgpu_profile_filter(const char* kernel) { prof::setFilter(kernel); }

@@ -12,6 +12,7 @@
 #include "matmul.h"
 #include "matmul_tile.h"
 #include "profile.h"
+#include "sync_arena.h"
 
 namespace dietgpu {
 
@@ -26,6 +27,12 @@ uint32_t matmulSlots(const void* kernel, uint32_t lds) {
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, dec::kThreads, lds));
     return uint32_t(std::max(1, cus) * std::max(1, perCU));
   });
+}
+
+// the plan's grid under dietgpu_set_matmul_grid (0: none)
+uint32_t cappedGrid(uint32_t gridX) {
+  const uint32_t cap = matmulGrid();
+  return cap ? std::min(gridX, cap) : gridX;
 }
 
 struct MatmulCall {
@@ -49,7 +56,7 @@ void launchMatmulPass(const MatmulCall& c) {
   const uint32_t lds = DecCfg<FT>::ldsBytes(c.pb);
   const uint32_t slots = matmulSlots(reinterpret_cast<const void*>(&k_matmulRows<FT, MT>), lds);
   const MatmulPlan plan = planMatmul(c.numRows, c.rowWords, c.mRows, MT, slots);
-  k_matmulRows<FT, MT><<<plan.gridX, dec::kThreads, lds, c.s>>>(c.archive, c.numRows, c.rowWords, c.x,
+  k_matmulRows<FT, MT><<<cappedGrid(plan.gridX), dec::kThreads, lds, c.s>>>(c.archive, c.numRows, c.rowWords, c.x,
                                                                  c.xRowStrideBytes, c.mRows, c.part, c.pieces, c.pb);
   HIP_LAUNCH_CHECK();
   k_matmulFinish<FT, OUT32><<<divUp(c.mRows * c.numRows, uint32_t(dec::kThreads)), dec::kThreads, 0, c.s>>>(
@@ -149,7 +156,7 @@ void floatMatmulTile(StackDeviceMemory& res, const FloatDecompressConfig& config
     const auto* x = static_cast<const uint8_t*>(x_dev);
     const uint32_t finishGrid = divUp(M * numRows, uint32_t(dec::kThreads));
     prof::Scope p("matmul_tile", stream);
-    k_matmulTile<FT><<<plan.gridX, dec::kThreads, lds, stream>>>(archive, numRows, rowWords, x, xRowStrideWords * 2, M,
+    k_matmulTile<FT><<<cappedGrid(plan.gridX), dec::kThreads, lds, stream>>>(archive, numRows, rowWords, x, xRowStrideWords * 2, M,
                                                                   partial, plan.pieces, plan.period, pb);
     HIP_LAUNCH_CHECK();
     k_matmulFinish<FT, decltype(out32)::value><<<finishGrid, dec::kThreads, 0, stream>>>(

@@ -60,6 +60,9 @@ uint32_t reduceMaxSources() { return gReduceMaxSources.load(); }
 std::atomic<uint32_t> gMatmulGroupedGrid{0};
 void setMatmulGroupedGrid(uint32_t workgroups) { gMatmulGroupedGrid.store(workgroups); }
 uint32_t matmulGroupedGrid() { return gMatmulGroupedGrid.load(); }
+std::atomic<uint32_t> gMatmulGrid{0};
+void setMatmulGrid(uint32_t workgroups) { gMatmulGrid.store(workgroups); }
+uint32_t matmulGrid() { return gMatmulGrid.load(); }
 
 SyncLease::SyncLease(StackDeviceMemory& res, hipStream_t stream, const size_t (&bytesIn)[kSyncRegions],
                      bool dequeue, size_t rowsBytes) {

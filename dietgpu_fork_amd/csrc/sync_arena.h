@@ -127,4 +127,12 @@ uint32_t reduceMaxSources();
 void setMatmulGroupedGrid(uint32_t workgroups);
 uint32_t matmulGroupedGrid();
 
+// Test / tuning hook: the most workgroups k_matmulRows and k_matmulTile are
+// launched with (matmul.hip); 0 (default) means the plan's (planMatmul,
+// planMatmulTile, decode_plan.h).  A small value makes one workgroup take
+// several task groups on small tables.  Results are the same bits whatever
+// the value.
+void setMatmulGrid(uint32_t workgroups);
+uint32_t matmulGrid();
+
 }  // namespace dietgpu

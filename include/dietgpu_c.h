@@ -416,6 +416,12 @@ void dietgpu_set_reduce_max_sources(uint32_t sources);
  * one workgroup cross from expert to expert on small tables.  Results are the
  * same bits whatever the value. */
 void dietgpu_set_matmul_grouped_grid(uint32_t workgroups);
+/* Test / tuning hook: the most workgroups the main kernels of
+ * dietgpu_float_matmul_rows and dietgpu_float_matmul_tile are launched with;
+ * 0 (default) means the plan's own grid.  A small value makes one workgroup
+ * take several task groups on small tables.  Results are the same bits
+ * whatever the value. */
+void dietgpu_set_matmul_grid(uint32_t workgroups);
 
 #ifdef __cplusplus
 }

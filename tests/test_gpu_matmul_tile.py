@@ -17,6 +17,8 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(256, 150), (768, 50), (4096, 9), (8192, 9), (4352, 9)]
 CASES = [(rw, R, ft, M) for rw, R in SHAPES for ft in (1, 2) for M in (5, 17, 64)]
 CASES += [(8192, 9, 2, M) for M in (1, 16, 33)]  # a tile exactly full, and one row into the next
+# periods 5 (40.6 blocks: a second run starts), 7 and 43 (one live half per group)
+CASES += [(rw, R, 2, 17) for rw, R in ((1280, 130), (1792, 94), (11008, 3))]
 
 ws = workspace_fixture(16 << 20)
 

@@ -25,6 +25,7 @@ def test_the_operator_its_list_and_the_export():
     assert len(ops.OPS) == 12 and ops.POOL_OPS == ("gather_rows_sum",)
     N.lib()
     assert "dietgpu_float_matmul_rows" in N.EXPORTED and hasattr(N.lib(), "dietgpu_float_matmul_rows")
+    assert "dietgpu_set_matmul_grid" in N.EXPORTED and hasattr(N.lib(), "dietgpu_set_matmul_grid")
     N.testlib()
     assert "dietgpu_test_matmul_config" in N.TEST_EXPORTED
 

@@ -21,6 +21,7 @@ def test_the_operator_its_list_and_the_export():
     assert len(ops.OPS) == 12 and ops.MATMUL_OPS == ("matmul_rows",)
     N.lib()
     assert "dietgpu_float_matmul_tile" in N.EXPORTED and hasattr(N.lib(), "dietgpu_float_matmul_tile")
+    assert "dietgpu_set_matmul_grid" in N.EXPORTED and hasattr(N.lib(), "dietgpu_set_matmul_grid")
     N.testlib()
     assert "dietgpu_test_matmul_tile_config" in N.TEST_EXPORTED
 
