@@ -98,6 +98,9 @@ def _declare(L):
         "dietgpu_float_matmul_grouped": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, c_u32, P, c_u32, c_u64, P, c_int,
                                                  P, c_int, c_u64, P, P]),
         "dietgpu_float_matmul_grouped_scratch_bytes": (c_u64, [c_u32, c_u32, c_u32, c_u32]),
+        "dietgpu_float_matmul_sparse_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int,
+                                                     c_u64, c_u32, P, P]),
+        "dietgpu_float_matmul_sparse_scratch_bytes": (c_u64, [c_int, c_u32, c_u32, c_u32, c_u32]),
         "dietgpu_set_matmul_grouped_grid": (None, [c_u32]),
         "dietgpu_set_matmul_grid": (None, [c_u32]),
         "dietgpu_profile_enable": (None, [c_int]),
@@ -106,9 +109,11 @@ def _declare(L):
         "dietgpu_profile_query": (c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_uint64)]),
     }
-    # test hooks absent from older builds (same-box A/B of earlier libraries)
+    # test hooks and entry points absent from older builds (same-box A/B of
+    # earlier libraries: tools/ab.py runs bench.py over the parent's set)
     optional = {"dietgpu_set_barrier_budget", "dietgpu_set_dispatch_skew",
-                "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path", "dietgpu_set_matmul_grid"}
+                "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path", "dietgpu_set_matmul_grid",
+                "dietgpu_float_matmul_sparse_rows", "dietgpu_float_matmul_sparse_scratch_bytes"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -151,6 +156,8 @@ def testlib():
                                                            P]),
                "dietgpu_test_matmul_grouped_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, c_u32, P, c_u32, P, P,
                                                               c_int, P, P]),
+               "dietgpu_test_matmul_sparse_config": (c_int, [P, c_int, c_int, P, c_u32, c_u32, P, c_u32, P, c_int,
+                                                             c_u32, P, P]),
                "dietgpu_test_sparse_accumulate_config": (c_int, [P, c_int, c_int, c_int, P, P, c_u32, P, P, P]),
                "dietgpu_test_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_u32, P, P, P]),
                "dietgpu_test_sparse_reduce_config": (c_int, [P, c_int, c_int, c_u32, P, P, c_int, P, c_u32, c_int, P,

@@ -603,7 +603,7 @@ def gather_rows_sum(archive, row_words, idx, offsets, dtype, out=None, out_dtype
 
 
 def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
-                check=False, _tile=False):
+                check=False, _tile=False, _sparse=False, _nnz_bound=None):
     """y = x @ W.T for a weight table W [R, row_words] stored as one dense
     float16 / bfloat16 / float32 archive of `dtype` -> (out [M, R], ok).  x is
     a CUDA tensor [M, row_words] of `dtype`, 1 <= M <= 64, its rows contiguous,
@@ -620,7 +620,7 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     Nothing is uploaded or read back, so the call (two launches per 4 rows of
     x, scratch from `ws`) can be captured in a graph and replayed on new x and
     new archive bytes.  check=True reads ok back and raises DietGpuError."""
-    who = "matmul_tile" if _tile else "matmul_rows"
+    who = "matmul_tile" if _tile else "matmul_sparse" if _sparse else "matmul_rows"
     if dtype == torch.uint8:
         raise ValueError(f"{who}: byte archives hold no floats to multiply")
     if _tile and dtype == torch.float32:
@@ -642,6 +642,15 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     if out_dtype not in (dtype, torch.float32):
         raise ValueError(f"{who}: out dtype {out_dtype} does not go with {dtype} archives (their own dtype, or "
                          "torch.float32)")
+    if _sparse and _nnz_bound is not None and int(_nnz_bound) < 1:
+        raise ValueError(f"{who}: nnz_bound must be at least 1 (the words of the nonzero list, or a bound on them)")
+    if _sparse and (out is None or _nnz_bound is None):
+        if not x.is_cuda:
+            raise ValueError(f"{who}: x and out must be CUDA tensors on one device")
+        n, nnz = _sparse_sizes(archive)  # one read-back for both
+        _nnz_bound = nnz if _nnz_bound is None else _nnz_bound
+        if out is None:
+            out = torch.empty([M, max(1, n // row_words)], dtype=out_dtype, device=x.device)
     if out is None:
         if not x.is_cuda:
             raise ValueError(f"{who}: x and out must be CUDA tensors on one device")
@@ -663,6 +672,17 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     ok = out_status if out_status is not None else torch.empty([1], dtype=torch.uint8, device=x.device)
     if not (ok.dtype == torch.uint8 and ok.is_contiguous() and ok.numel() == 1 and ok.device == x.device):
         raise ValueError(f"{who}: out_status must be a uint8 tensor of one entry")
+    if _sparse:
+        nnz_bound = int(_nnz_bound)
+        if ws is None:
+            ws = Workspace(matmul_sparse_scratch_bytes(FLOAT_TYPE[dtype], row_words, rows, M, nnz_bound), x.device)
+        N.check(N.lib().dietgpu_float_matmul_sparse_rows(
+            ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, rows, x.data_ptr(), M, x_stride,
+            out.data_ptr(), int(out_dtype == torch.float32), out_stride, nnz_bound, ok.data_ptr(), _s()))
+        if check and not bool(ok.all()):
+            raise N.DietGpuError(f"{who}: the archive does not match dtype / prob_bits, holds fewer than {rows} "
+                                 f"rows of {row_words} words, or its nonzero list exceeds nnz_bound = {nnz_bound}")
+        return out, ok
     if ws is None:  # the partial sums of one pass: min(M, 4) rows (tiled: all M) of R + blocks fp32 words
         ws = Workspace(4 * (M if _tile else min(M, 4)) * (rows + (rows * row_words + 4095) // 4096) + 256, x.device)
     N.check((N.lib().dietgpu_float_matmul_tile if _tile else N.lib().dietgpu_float_matmul_rows)(
@@ -690,6 +710,56 @@ def matmul_tile(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     from `ws`; the call can be captured in a graph."""
     return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
                        prob_bits=prob_bits, check=check, _tile=True)
+
+
+def _sparse_sizes(archive):
+    """(N, the words of the nonzero list) of a sparse float archive on the
+    device, in one read-back: sparse header word 0, and word 1 of the dense
+    archive's float header, which lies 16 + roundUp(ceil(N / 8), 16) bytes in
+    (held inside the tensor, whatever the header says)."""
+    n = archive[0:4].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    at = (16 + ((n + 7) // 8 + 15) // 16 * 16 + 4).clamp(max=archive.numel() - 4)
+    word = archive[at + torch.arange(4, device=archive.device)].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    n, nnz = torch.cat([n, word]).tolist()
+    return n, max(1, nnz)
+
+
+def matmul_sparse_scratch_bytes(ft, row_words, rows, M, nnz_bound):
+    """The workspace bytes a matmul_sparse call of M activation rows against
+    `rows` rows of row_words words of float type ft takes, its nonzero list
+    decoded into nnz_bound words; raises DietGpuError for a shape the call
+    refuses.  Host only: no device is touched."""
+    return N.size_or_raise(N.lib().dietgpu_float_matmul_sparse_scratch_bytes(int(ft), int(row_words), int(rows),
+                                                                           int(M), int(nnz_bound)))
+
+
+def matmul_sparse(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
+                  nnz_bound=None, check=False):
+    """matmul_rows on a SPARSE float archive (sparse_compress) of a pruned
+    weight table: y = x @ W.T for W [R, row_words], the first R * row_words
+    words of the archive's element, -> (out [M, R], ok).  x, out, row_words,
+    the dtypes, alignment and refusals are matmul_rows'; the archive is 16-byte
+    aligned.  Only the words whose bitmap bit is set are multiplied, each one
+    fp32 fmaf, in an order that depends on (row_words, r) alone -- the same
+    bits on every run, for row r whatever else the table holds, for row m
+    whatever M is; not matmul_rows' bits -- with one rounding to out's dtype.
+    A clear bit (a weight of +0.0 bitwise) is SKIPPED, not multiplied, as
+    everywhere in the sparse codec: for finite x the value is the dense
+    product's, but an Inf or NaN of x under a clear bit does not reach `out`
+    (the dense product would be NaN there).
+    The nonzero list is decoded once into `ws`, whatever M is, and the expanded
+    matrix is never stored.  nnz_bound sizes that scratch: the words of the
+    list, or any bound on them (the element's words + 1 always suffices).
+    None reads the count (and, without `out`, the element's size) from the
+    archive, which synchronises the stream once, like matmul_rows without
+    `out`.  With nnz_bound and `out` given nothing is uploaded or read back,
+    and the call (four launches) can be captured in a graph and replayed on
+    new x and new archive bytes.  ok is one uint8: 1 iff the archive matches
+    dtype / prob_bits, holds R * row_words words, and its list fits nnz_bound;
+    else `out` is untouched.  check=True reads ok back and raises
+    DietGpuError."""
+    return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
+                       prob_bits=prob_bits, check=check, _sparse=True, _nnz_bound=nnz_bound)
 
 
 def set_matmul_grid(workgroups):

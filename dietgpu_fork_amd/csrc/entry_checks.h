@@ -131,6 +131,15 @@ inline void checkMatmulShape(int floatType, bool outIsFp32, uint32_t rowWords, u
            "outRowStrideWords (" << outRowStrideWords << ") must be at least numRows (" << numRows << ")");
 }
 
+// The matmul on a sparse archive (floatMatmulSparseRows) takes checkMatmulShape
+// and a capacity for the decoded nonzero list, which sizes its scratch.  The C
+// ABI makes the same checks before it looks at the stack or any pointer.
+inline void checkSparseListCapacity(uint32_t listCapacityWords) {
+  DG_CHECK(listCapacityWords >= 1 && listCapacityWords < UINT32_MAX - 32,
+           "listCapacityWords (" << listCapacityWords << ") must be in 1 .. 2^32 - 34 (the words of the archive's "
+                                 "nonzero list, or a bound on them)");
+}
+
 // The matmul through the matrix pipe (floatMatmulTile): fp16 and bf16 archives
 // alone, each other type with its own message; everything else is
 // checkMatmulShape's.  The C ABI makes the same checks before it looks at the

@@ -1,8 +1,10 @@
-// The host arithmetic of the four sparse drivers (sparse.hip sparseCompressT,
-// sparseDecompressT, sparseReduceT, sparseRangeT): tiles, chunks, rows, strides,
+// The host arithmetic of the five sparse drivers (sparse.hip sparseCompressT,
+// sparseDecompressT, sparseReduceT, sparseRangeT; sparse_matmul.hip
+// floatMatmulSparseRows): tiles, chunks, rows, strides,
 // grids and the element counts of every allocation, for a reduce call its
-// passes and total scratch, and for a range call the member sort and the
-// packed host columns.  Host only and free of HIP headers, as
+// passes and total scratch, for a range call the member sort and the
+// packed host columns, and for a matmul its pieces, passes and total
+// scratch.  Host only and free of HIP headers, as
 // compress_plan.h and decode_plan.h are, so that it is stated once and swept
 // without a GPU (tests/test_sparse_plan.py, tests/test_sparse_reduce_plan.py).
 // The drivers allocate what a plan names and launch; they compute nothing else.
@@ -229,6 +231,60 @@ inline SparseRangePlan planSparseRange(const uint64_t* in, const uint32_t* first
   p.maxRangeBlocks = uint32_t((slice + cplan::kBlockWords - 1) / cplan::kBlockWords) + 1;
   p.chunkWaves = uint32_t((uint64_t(p.maxCount) + splan::kChunkWords - 1) / splan::kChunkWords) + 1;
   p.expandGridX = splan::div32(p.chunkWaves, splan::kWaves);
+  return p;
+}
+
+// ---------------------------------------------------------------------------
+// matmul on a sparse archive: the table W [numRows, rowWords]
+// is the first numRows * rowWords words of the element, x holds M activation
+// rows, and the element's nonzero list has at most listCapacity words
+// ---------------------------------------------------------------------------
+// The largest k_sparseMatmul instance (sparse_matmul.hip static_asserts it).
+constexpr uint32_t kSparseMatmulMaxMT = 8;
+
+struct SparseMatmulPlan {
+  bool valid = false;  // checkMatmulShape's rule, 1 <= listCapacity < 2^32 - 32, M * pieces < 2^32
+  uint32_t chunks = 0;   // 1024-word chunks that hold words of the table: one k_sparseMatmul wave each
+  uint32_t cblocks = 0;  // k_sparseChunks workgroups: only the table's chunks are counted
+  uint32_t gridX = 0;    // k_sparseMatmul workgroups per pass: a chunk per wave
+  uint32_t rowsPerPass = 0;  // MT: activation rows one pass over the scratch list serves
+  uint32_t passes = 0;       // grid.y of the one k_sparseMatmul launch
+  uint32_t pieces = 0;   // numRows + chunks: partial sums per activation row, id = chunk + row
+  uint32_t finishGrid = 0;  // k_sparseMatmulFinish workgroups: a thread per (m, r)
+  // element counts of the allocations, in the order they are taken
+  uint64_t densePtrs = 1, sizes = 1, denseOk = 1;  // u64, u32, u8: k_sparseChunks' and the dense decode's
+  uint64_t listBytes = 0;                          // the decoded nonzero list
+  uint64_t chunkPre = 0, blockTot = 0;             // u32
+  uint64_t partWords = 0;                          // fp32 [M][pieces]
+  // the arena bytes of the whole call (granules as planSparseReduce's)
+  uint64_t scratchBytes = 0;
+};
+
+// The smallest instance that holds M rows, or the largest: rows beyond it go
+// to further passes over the decoded list, never to a second decode.
+inline SparseMatmulPlan planSparseMatmul(uint32_t wordBytes, uint32_t numRows, uint32_t rowWords, uint32_t M,
+                                         uint32_t listCapacity) {
+  SparseMatmulPlan p;
+  const uint64_t total = uint64_t(numRows) * rowWords;
+  if (rowWords < 1 || rowWords % kMatmulSegWords != 0 || M < 1 || M > kMatmulMaxRows || numRows < 1 ||
+      total >= (1ull << 32) || listCapacity < 1 || listCapacity >= UINT32_MAX - 32)
+    return p;
+  p.chunks = uint32_t((total + splan::kChunkWords - 1) / splan::kChunkWords);
+  p.cblocks = splan::div32(p.chunks, splan::kThreads);
+  p.gridX = splan::div32(p.chunks, splan::kWaves);
+  p.rowsPerPass = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : kSparseMatmulMaxMT;
+  p.passes = splan::div32(M, p.rowsPerPass);
+  p.pieces = numRows + p.chunks;
+  p.partWords = uint64_t(M) * p.pieces;
+  if (p.partWords >= (1ull << 32)) return p;
+  p.finishGrid = splan::div32(M * numRows, splan::kThreads);
+  p.listBytes = splan::listStride(listCapacity, wordBytes);
+  p.chunkPre = p.chunks;
+  p.blockTot = p.cblocks;
+  auto granules = [](uint64_t bytes) { return std::max<uint64_t>((bytes + 255) / 256, 1) * 256; };
+  p.scratchBytes = granules(8 * p.densePtrs) + granules(4 * p.sizes) + granules(p.denseOk) + granules(p.listBytes) +
+                   granules(4 * p.chunkPre) + granules(4 * p.blockTot) + granules(4 * p.partWords);
+  p.valid = true;
   return p;
 }
 

@@ -26,6 +26,7 @@
 //   matmul_rows                       ext   floatMatmulRows
 //   matmul_tile                       ext   floatMatmulTile
 //   matmul_grouped                    ext   floatMatmulGrouped
+//   matmul_sparse                     ext   floatMatmulSparseRows
 //   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
@@ -774,10 +775,19 @@ int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tenso
 // out_status[0] = 1 iff the archive is valid and holds R * row_words words;
 // else t_out is left untouched.  Scratch comes from temp_mem.  The checks that
 // need no device come first.
-// tile: matmul_tile (floatMatmulTile: float16 and bfloat16 alone, all the rows
+// kTile: matmul_tile (floatMatmulTile: float16 and bfloat16 alone, all the rows
 // in one pass through the matrix pipe), with the same arguments and checks.
-int64_t matmulOp(bool tile, const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
-                 const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+// kSparse: matmul_sparse (floatMatmulSparseRows): t_in is a sparse float
+// archive whose element starts with W, a word under a clear bitmap bit is
+// skipped (an Inf or NaN of t_x there does not reach t_out), and nnz_bound >= 1
+// is the word count of the archive's nonzero list or a bound on it, which
+// sizes the scratch; out_status[0] is also 0 when the list does not fit it.
+enum class MatmulKind { kRows, kTile, kSparse };
+
+int64_t matmulOp(MatmulKind kind, const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX,
+                 const at::Tensor& tOut, int64_t nnzBound, const std::optional<at::Tensor>& tempMem,
+                 const std::optional<at::Tensor>& status) {
+  const bool tile = kind == MatmulKind::kTile;
   TORCH_CHECK(rowWords >= 1 && rowWords % 256 == 0 && uint64_t(rowWords) <= kU32Max,
               "row_words must be a positive multiple of 256 (pad the rows with zeros), not ", rowWords);
   checkDtype(tX, tX.scalar_type(), {false, "t_x", "t_x"});
@@ -796,6 +806,8 @@ int64_t matmulOp(bool tile, const at::Tensor& tIn, int64_t rowWords, const at::T
   TORCH_CHECK(M >= 1 && M <= int64_t(kMatmulMaxRows), "t_x must hold 1 .. ", kMatmulMaxRows,
               " rows (for more, decompress and call a GEMM), not ", M);
   TORCH_CHECK(uint64_t(rows) * uint64_t(rowWords) <= kU32Max, "R * row_words must be below 2^32");
+  TORCH_CHECK(kind != MatmulKind::kSparse || (nnzBound >= 1 && uint64_t(nnzBound) < kU32Max - 32),
+              "nnz_bound must be at least 1 (and below 2^32 - 33), not ", nnzBound);
   // rows at one stride: leading dimension d strides over the rows inside it
   auto rowStride = [&](const at::Tensor& t, int64_t width, const char* name) {
     TORCH_CHECK(width == 1 || t.stride(k) == 1, name, "'s last dimension must be contiguous");
@@ -822,21 +834,34 @@ int64_t matmulOp(bool tile, const at::Tensor& tIn, int64_t rowWords, const at::T
   TORCH_CHECK(tOut.device().type() == at::kCUDA && tOut.get_device() == dev, "t_out must be on the archive's device");
   const auto st = statusPointers(status, std::nullopt, 1, dev).first;
   cx.stack(tempMem);
-  (tile ? floatMatmulTile : floatMatmulRows)(*cx.res, floatConfig(floatTypeOf(tX.scalar_type()), false), tIn.data_ptr(),
-                                             uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(M),
-                                             uint64_t(xStride), tOut.data_ptr(), tOut.scalar_type() == at::kFloat,
-                                             uint64_t(outStride), st, cx.stream);
+  const auto cfg = floatConfig(floatTypeOf(tX.scalar_type()), false);
+  const bool out32 = tOut.scalar_type() == at::kFloat;
+  if (kind == MatmulKind::kSparse) {
+    floatMatmulSparseRows(*cx.res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(M),
+                          uint64_t(xStride), tOut.data_ptr(), out32, uint64_t(outStride), uint32_t(nnzBound), st,
+                          cx.stream);
+  } else {
+    (tile ? floatMatmulTile : floatMatmulRows)(*cx.res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(rows),
+                                               tX.data_ptr(), uint32_t(M), uint64_t(xStride), tOut.data_ptr(), out32,
+                                               uint64_t(outStride), st, cx.stream);
+  }
   return cx.used();
 }
 
 int64_t matmul_rows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
                     const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
-  return matmulOp(false, tIn, rowWords, tX, tOut, tempMem, status);
+  return matmulOp(MatmulKind::kRows, tIn, rowWords, tX, tOut, 0, tempMem, status);
 }
 
 int64_t matmul_tile(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
                     const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
-  return matmulOp(true, tIn, rowWords, tX, tOut, tempMem, status);
+  return matmulOp(MatmulKind::kTile, tIn, rowWords, tX, tOut, 0, tempMem, status);
+}
+
+int64_t matmul_sparse(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                      int64_t nnzBound, const std::optional<at::Tensor>& tempMem,
+                      const std::optional<at::Tensor>& status) {
+  return matmulOp(MatmulKind::kSparse, tIn, rowWords, tX, tOut, nnzBound, tempMem, status);
 }
 
 // Extension (no reference counterpart): matmul_tile over many expert tables in
@@ -1016,6 +1041,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "matmul_grouped(Tensor t_archives, int row_words, Tensor t_x, Tensor t_offsets, Tensor t_out, Tensor? "
       "temp_mem=None, Tensor? out_status=None) -> int");
+  m.def(
+      "matmul_sparse(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, int nnz_bound, Tensor? temp_mem=None, "
+      "Tensor? out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -1037,4 +1065,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("matmul_rows", &dietgpu::matmul_rows);
   m.impl("matmul_tile", &dietgpu::matmul_tile);
   m.impl("matmul_grouped", &dietgpu::matmul_grouped);
+  m.impl("matmul_sparse", &dietgpu::matmul_sparse);
 }

@@ -27,6 +27,7 @@ validation and return values; "ext": not in the reference.
     matmul_rows                       ext   MATMUL_OPS  x W^T for a few rows of x, W a table held by one archive
     matmul_tile                       ext   TILE_OPS    the same through the matrix pipe: 1 .. 64 rows, one decode
     matmul_grouped                    ext   GROUP_OPS   matmul_tile over many expert tables, routed on the device
+    matmul_sparse                     ext   SPARSE_MATMUL_OPS  x W^T on a sparse archive of a pruned table: zeros skipped
 """
 import os
 
@@ -76,6 +77,10 @@ TILE_OPS = ("matmul_tile",)
 # routing read on the device: a compressed mixture-of-experts layer
 GROUP_OPS = ("matmul_grouped",)
 
+# matmul_sparse is matmul_rows on a sparse float archive (bitmap + nonzero
+# list) of a pruned table: the list is decoded once, the zeros are skipped
+SPARSE_MATMUL_OPS = ("matmul_sparse",)
+
 _LOADED = False
 
 
@@ -94,7 +99,7 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS:
+    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS + SPARSE_MATMUL_OPS:
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

@@ -424,4 +424,48 @@ void floatMatmulGrouped(StackDeviceMemory& res,
 uint64_t floatMatmulGroupedScratchBytes(uint32_t numExperts, uint32_t rowWords,
                                         uint32_t numRows, uint32_t T);
 
+// Matmul on a sparse weight archive (a pruned W): archive_dev is a sparse
+// float archive (floatCompressSparse: a nonzero bitmap and a dense archive of
+// the compacted nonzeros), 16-byte aligned, whose element starts with the
+// table W [numRows, rowWords] row-major; words past the table are ignored.
+// x_dev, out_dev, the strides and outIsFp32 as floatMatmulRows'.
+//   out[m * outRowStrideWords + r] =
+//       round_out(sum over k with bit(r * rowWords + k) set of f(x[m, k]) * f(W[r, k]))
+// with f the exact conversion to fp32, every term one fp32 fmaf and one
+// rounding.  A clear bitmap bit (a word of +0.0 bitwise) is SKIPPED, not
+// multiplied, as everywhere in the sparse codec: for finite x the value is the
+// dense product's, and an Inf or NaN of x under a clear bit does not reach out
+// (the dense product would be NaN there).  The order of the adds depends on
+// (rowWords, r) alone: the same bits on every run, for row r whatever else the
+// table holds, for row m whatever M is; nothing is promised against
+// floatMatmulRows' bits.  The nonzero list is decoded once into scratch,
+// whatever M is, and the expanded matrix is never stored.
+// listCapacityWords: the words of scratch the decoded list may take, i.e. the
+// word count of the archive's dense part or any bound on it (the element's
+// words + 1 always suffices); the host cannot know it without a read-back.
+// outSuccess_dev[0] (optional) = 1 iff the sparse header holds at least
+// numRows * rowWords words, the dense part is valid for this config and its
+// words fit listCapacityWords; on failure nothing else is written.  Scratch
+// (floatMatmulSparseScratchBytes) comes from res; four launches, no host
+// synchronisation, no upload, no atomics, no wait between workgroups: the call
+// can be captured in a graph and replayed on new x and new archive bytes.
+// Refused before any launch: floatMatmulRows' refusals, listCapacityWords == 0
+// or within 33 of 2^32, and an archive_dev off 16 bytes.  archive_dev must be a
+// sparse archive, as for floatDecompressSparse: its header is trusted to
+// locate the dense part.
+void floatMatmulSparseRows(StackDeviceMemory& res,
+                           const FloatDecompressConfig& config,
+                           const void* archive_dev, uint32_t rowWords,
+                           uint32_t numRows, const void* x_dev, uint32_t M,
+                           uint64_t xRowStrideWords, void* out_dev,
+                           bool outIsFp32, uint64_t outRowStrideWords,
+                           uint32_t listCapacityWords, uint8_t* outSuccess_dev,
+                           hipStream_t stream);
+
+// The scratch bytes floatMatmulSparseRows takes from res for such a call.
+// Host only: no device is touched.
+uint64_t floatMatmulSparseScratchBytes(FloatType floatType, uint32_t rowWords,
+                                       uint32_t numRows, uint32_t M,
+                                       uint32_t listCapacityWords);
+
 } // namespace dietgpu

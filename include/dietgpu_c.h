@@ -41,6 +41,8 @@
  *   weight table held by one archive; the decoded matrix is never stored)
  *   dietgpu_float_matmul_grouped (that product over many expert tables in one
  *   task line, the routing read on the device)
+ *   dietgpu_float_matmul_sparse_rows (that product on a sparse archive of a
+ *   pruned table: bitmap and nonzero list, the expanded matrix never stored)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -349,10 +351,34 @@ int dietgpu_float_matmul_grouped(dietgpu_stack* res, int float_type, int prob_bi
 uint64_t dietgpu_float_matmul_grouped_scratch_bytes(uint32_t num_experts, uint32_t row_words,
                                                     uint32_t num_rows, uint32_t t);
 
+/* The product of dietgpu_float_matmul_rows on a SPARSE float archive
+ * (floatMatmulSparseRows, GpuFloatCodec.h; dietgpu_float_compress_sparse
+ * writes one): archive_dev, 16-byte aligned, holds W [num_rows, row_words] as
+ * the first words of its element; every other argument as
+ * dietgpu_float_matmul_rows.  A word whose bitmap bit is clear (+0.0 bitwise)
+ * is skipped, not multiplied: an Inf or NaN of x there does not reach out_dev.
+ * list_capacity_words: the word count of the archive's dense part (the
+ * nonzero list) or a bound on it; it sizes the scratch the list is decoded
+ * into, once, whatever m is.  out_success_dev[0] (optional) = 1 iff the sparse
+ * header holds num_rows * row_words words, the dense part is valid and its
+ * words fit list_capacity_words; else 0 and out_dev is untouched.  Scratch
+ * (dietgpu_float_matmul_sparse_scratch_bytes) comes from res; no host
+ * synchronisation, no upload.  No checksum flag. */
+int dietgpu_float_matmul_sparse_rows(dietgpu_stack* res, int float_type, int prob_bits,
+                                     const void* archive_dev, uint32_t row_words,
+                                     uint32_t num_rows, const void* x_dev, uint32_t m,
+                                     uint64_t x_row_stride_words, void* out_dev, int out_is_fp32,
+                                     uint64_t out_row_stride_words, uint32_t list_capacity_words,
+                                     uint8_t* out_success_dev, void* stream);
+/* ... and its scratch bytes; 0 for a shape the call refuses (dietgpu_last_error) */
+uint64_t dietgpu_float_matmul_sparse_scratch_bytes(int float_type, uint32_t row_words,
+                                                   uint32_t num_rows, uint32_t m,
+                                                   uint32_t list_capacity_words);
+
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
  * "decode_gather", "decode_gather_sum", "matmul_rows", "matmul_tile", "matmul_grouped", "hist", "coalesce", "sparse",
- * "sparse_accumulate", "sparse_reduce") is bracketed
+ * "sparse_accumulate", "sparse_reduce", "sparse_matmul") is bracketed
  * by hipEvents on its own stream; query returns the summed milliseconds and
  * the launch count since the last reset (synchronises the recorded events). */
 void dietgpu_profile_enable(int on);

@@ -132,6 +132,13 @@ int dietgpu_test_matmul_grouped_config(dietgpu_stack* res, int float_type, int u
                                        uint32_t t, const void* offsets, void* out, int out_is_fp32,
                                        uint8_t* out_success_dev, void* stream);
 
+/* ... and for the matmul on a sparse archive (floatMatmulSparseRows), with
+ * dietgpu_test_matmul_config's arguments and the list capacity. */
+int dietgpu_test_matmul_sparse_config(dietgpu_stack* res, int float_type, int use_checksum, const void* in,
+                                      uint32_t row_words, uint32_t num_rows, const void* x, uint32_t m, void* out,
+                                      int out_is_fp32, uint32_t list_capacity_words, uint8_t* out_success_dev,
+                                      void* stream);
+
 /* The compress plan (csrc/compress_plan.h) of a dense compress call with no
  * caller-counted rows: which compressor takes the batch and what it launches.
  * Enumerations as in that header. */
