@@ -91,6 +91,8 @@ def _declare(L):
         "dietgpu_float_gather_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_int, P, c_u64, P, P]),
         "dietgpu_float_gather_rows_sum": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, c_u32, P, P, c_int, P, c_int,
                                                   c_u64, P, P]),
+        "dietgpu_float_gather_rows_pool": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, c_u32, P, P, c_int, c_int, P,
+                                                   c_int, ctypes.c_int64, P, c_int, c_u64, P, P]),
         "dietgpu_float_matmul_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int, c_u64,
                                               P, P]),
         "dietgpu_float_matmul_tile": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int, c_u64,
@@ -113,7 +115,8 @@ def _declare(L):
     # earlier libraries: tools/ab.py runs bench.py over the parent's set)
     optional = {"dietgpu_set_barrier_budget", "dietgpu_set_dispatch_skew",
                 "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path", "dietgpu_set_matmul_grid",
-                "dietgpu_float_matmul_sparse_rows", "dietgpu_float_matmul_sparse_scratch_bytes"}
+                "dietgpu_float_matmul_sparse_rows", "dietgpu_float_matmul_sparse_scratch_bytes",
+                "dietgpu_float_gather_rows_pool"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue

@@ -602,6 +602,109 @@ def gather_rows_sum(archive, row_words, idx, offsets, dtype, out=None, out_dtype
     return out, ok
 
 
+POOL_MODE = {"sum": 0, "mean": 1, "max": 2}
+
+
+def gather_rows_pool(archive, row_words, idx, offsets, dtype, mode="sum", per_sample_weights=None, padding_idx=None,
+                     num_rows=None, out=None, out_dtype=None, out_status=None, prob_bits=10, ws=None, check=False):
+    """torch.nn.functional.embedding_bag on a [R, row_words] table stored as
+    one dense float16 / bfloat16 / float32 archive of `dtype` -> (out, ok).
+    archive, idx, offsets (B + 1 boundaries: the last offset is always
+    included), out, out_dtype, out_status, ok and check are gather_rows_sum's.
+    With x_t the rows of bag b that are not padding_idx, in list order, widened
+    exactly to fp32, and n_b their count, out[b] is per column
+      mode="sum"   the fp32 sum in list order, started from the first row: the
+                   bits of gather_rows_sum.  With per_sample_weights (a
+                   contiguous 1-d CUDA tensor of idx's length, float32 or
+                   `dtype`; weight i belongs to idx[i]): acc = w_1 * x_1, then
+                   acc = fmaf(w_t, x_t, acc); weights of 1.0 give the
+                   unweighted bits
+      mode="mean"  that sum, one correctly rounded fp32 division by float(n_b)
+      mode="max"   m = x_1, then m = x_t where x_t > m or x_t is NaN: a NaN in
+                   any row makes the column NaN, of equal values (and of +0.0
+                   against -0.0) the first stays; an out of `dtype` carries
+                   the table's words bit for bit
+    rounded once to out_dtype.  A bag that is empty or all padding gives +0.0
+    and ok 1.  padding_idx: None, or a row index; an entry equal to it is
+    skipped before the range check (not decoded, not counted, unable to fail
+    the bag).  A negative padding_idx means padding_idx + num_rows, as in
+    torch, and needs num_rows (the table's R).  Weights with mean or max are
+    refused, as torch refuses them.  One kernel launch on the current stream,
+    nothing uploaded or read back: the call can be captured in a graph and
+    replayed on new indices, offsets and weights; the same bits on every run,
+    and for a bag whatever the other bags are."""
+    who = "gather_rows_pool"
+    if mode not in POOL_MODE:
+        raise ValueError(f"{who}: unknown mode {mode!r} (sum, mean or max)")
+    for name, t in (("idx", idx), ("offsets", offsets)):
+        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64) and t.dim() == 1
+                and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous 1-d int32 or int64 tensor")
+    if idx.dtype != offsets.dtype:
+        raise ValueError(f"{who}: idx and offsets must share a dtype, not {idx.dtype} and {offsets.dtype}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{who}: offsets must hold B + 1 >= 1 entries")
+    if dtype == torch.uint8:
+        raise ValueError(f"{who}: byte archives hold no floats to pool")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16, bfloat16 or float32 archives)")
+    out_dtype = out_dtype if out_dtype is not None else (out.dtype if out is not None else dtype)
+    if out_dtype not in (dtype, torch.float32):
+        raise ValueError(f"{who}: out dtype {out_dtype} does not go with {dtype} archives (their own dtype, or "
+                         "torch.float32)")
+    row_words = int(row_words)
+    if row_words < 1:
+        raise ValueError(f"{who}: row_words must be at least 1")
+    w = per_sample_weights
+    if w is not None:
+        if mode != "sum":
+            raise ValueError(f"{who}: per_sample_weights go with mode 'sum' alone, not {mode!r}")
+        if not (isinstance(w, torch.Tensor) and w.dim() == 1 and w.is_contiguous() and w.numel() == idx.numel()):
+            raise ValueError(f"{who}: per_sample_weights must be a contiguous 1-d tensor of idx's {idx.numel()} "
+                             "entries")
+        if w.dtype not in (dtype, torch.float32):
+            raise ValueError(f"{who}: per_sample_weights must be float32 or of the archive's dtype {dtype}, not "
+                             f"{w.dtype}")
+    pad = -1
+    if padding_idx is not None:
+        pad = int(padding_idx)
+        if pad < 0:
+            if num_rows is None:
+                raise ValueError(f"{who}: a negative padding_idx counts from the table's end and needs num_rows")
+            if pad < -int(num_rows):
+                raise ValueError(f"{who}: padding_idx {pad} lies outside a table of {int(num_rows)} rows")
+            pad += int(num_rows)
+    if not (idx.is_cuda and offsets.is_cuda and idx.device == offsets.device):
+        raise ValueError(f"{who}: idx and offsets must be CUDA tensors on one device")
+    if w is not None and w.device != idx.device:
+        raise ValueError(f"{who}: per_sample_weights must be on idx's device")
+    bags = offsets.numel() - 1
+    shape = [bags, row_words]
+    out = out if out is not None else torch.empty(shape, dtype=out_dtype, device=idx.device)
+    if list(out.shape) != shape or out.dtype != out_dtype or out.device != idx.device:
+        raise ValueError(f"{who}: out must be a {out_dtype} tensor of shape {shape} on idx's device")
+    stride = _row_stride(out, row_words)
+    if stride is None or stride < row_words:
+        raise ValueError(f"{who}: out's last dimension must be contiguous and its rows must lie at a constant "
+                         "stride of at least row_words")
+    ok = out_status if out_status is not None else torch.empty([bags], dtype=torch.uint8, device=idx.device)
+    if not (ok.dtype == torch.uint8 and ok.is_contiguous() and list(ok.shape) == [bags] and ok.device == idx.device):
+        raise ValueError(f"{who}: out_status must be a contiguous uint8 tensor of {bags} entries")
+    fn = getattr(N.lib(), "dietgpu_float_gather_rows_pool", None)
+    if fn is None:  # (an older library swapped in for an A/B run: _native.py loads it without this entry)
+        raise N.DietGpuError(f"{who}: the loaded libdietgpu_amd.so has no dietgpu_float_gather_rows_pool; rebuild it")
+    ws = _ws(ws, idx.device)
+    N.check(fn(
+        ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, bags, idx.numel(), idx.data_ptr(),
+        offsets.data_ptr(), int(idx.dtype == torch.int64), POOL_MODE[mode], w.data_ptr() if w is not None else None,
+        FLOAT_TYPE[w.dtype] if w is not None else 0, pad, out.data_ptr(), int(out_dtype == torch.float32), stride,
+        ok.data_ptr(), _s()))
+    if check and not bool(ok.all()):
+        raise N.DietGpuError(f"{who}: a bag's offsets or rows lie outside idx or the table, or the archive does "
+                             "not match dtype / prob_bits")
+    return out, ok
+
+
 def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
                 check=False, _tile=False, _sparse=False, _nnz_bound=None):
     """y = x @ W.T for a weight table W [R, row_words] stored as one dense

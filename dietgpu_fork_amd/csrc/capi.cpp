@@ -427,6 +427,27 @@ int dietgpu_float_gather_rows_sum(dietgpu_stack* res, int ft, int pb, const void
   });
 }
 
+int dietgpu_float_gather_rows_pool(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
+                                   uint32_t num_bags, uint32_t num_idx, const void* idx_dev, const void* offsets_dev,
+                                   int idx_is_64, int mode, const void* weights_dev, int weight_type,
+                                   int64_t padding_idx, void* out_dev, int out_is_fp32, uint64_t out_row_stride,
+                                   uint8_t* succ, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at, as dietgpu_float_gather_rows_sum)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkProbBits(pb);
+    checkGatherSumShape(ft, out_is_fp32 != 0, row_words, out_row_stride);
+    checkGatherPoolMode(ft, mode, weight_type);
+    StackDeviceMemory& mem = R(res);
+    DG_CHECK(weight_type == 0 || weights_dev || num_bags == 0,
+             "weights_dev must not be null for weight_type " << weight_type);
+    floatGatherRowsPool(mem, cfg, archive_dev, row_words, num_bags, num_idx, idx_dev, offsets_dev, idx_is_64 != 0,
+                        PoolMode(mode), weight_type ? weights_dev : nullptr, FloatType(weight_type ? weight_type : ft),
+                        padding_idx, out_dev, out_is_fp32 != 0, out_row_stride, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
 int dietgpu_float_matmul_rows(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
                               uint32_t num_rows, const void* x_dev, uint32_t m, uint64_t x_row_stride, void* out_dev,
                               int out_is_fp32, uint64_t out_row_stride, uint8_t* succ, void* stream) {

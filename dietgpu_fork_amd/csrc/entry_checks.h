@@ -105,6 +105,19 @@ inline void checkGatherSumShape(int floatType, bool outIsFp32, uint32_t rowWords
   checkGatherRows(rowWords, outRowStrideWords);
 }
 
+// The pooling mode and the per-sample weights of floatGatherRowsPool (mode as
+// PoolMode's values; weightType 0 for none, else as FloatType's values); its
+// archive and row shape are checkGatherSumShape's.  The C ABI makes the same
+// checks before it looks at the stack or any pointer.
+inline void checkGatherPoolMode(int floatType, int mode, int weightType) {
+  DG_CHECK(mode >= 0 && mode <= 2, "unknown pooling mode " << mode << " (0 sum, 1 mean, 2 max)");
+  DG_CHECK(weightType == 0 || mode == 0,
+           "per-sample weights go with mode sum alone, not with " << (mode == 1 ? "mean" : "max"));
+  DG_CHECK(weightType == 0 || weightType == 3 || (weightType == floatType && floatType <= 2),
+           "weight type " << weightType << " does not go with float type " << floatType
+                          << " (fp32, or the archive's type)");
+}
+
 // The matmul on a compressed table (floatMatmulRows; float types as
 // FloatType's values): fp16, bf16 and fp32 archives, an out of the archive's
 // type or fp32, rows of a multiple of 256 words, 1 .. 64 activation rows at a

@@ -23,6 +23,7 @@
 //   gather_rows                       ext   floatGatherRows / ansGatherRows
 //   reduce_data                       ext   floatReduceArchives (*)
 //   gather_rows_sum                   ext   floatGatherRowsSum (*)
+//   gather_rows_pool                  ext   floatGatherRowsPool (*)
 //   matmul_rows                       ext   floatMatmulRows
 //   matmul_tile                       ext   floatMatmulTile
 //   matmul_grouped                    ext   floatMatmulGrouped
@@ -713,21 +714,22 @@ int64_t gather_rows(bool asFloat, const at::Tensor& tIn, int64_t rowWords, const
   return cx.used();
 }
 
-// Extension (no reference counterpart): embedding_bag(mode="sum") on a
-// compressed table (floatGatherRowsSum).  Bag b is t_idx[t_offsets[b] ..
-// t_offsets[b + 1]) (t_offsets holds B + 1 boundaries; both tensors int32 or
-// both int64, on the archive's device) and t_out [B, row_words] row b the fp32
-// sum of the bag's rows in list order, started from the first row and rounded
-// once to t_out's dtype; an empty bag gives +0.0.  float16 / bfloat16 outputs
-// name the archive's type themselves; for float32 outputs peekArchiveType
-// reads it (fp32, or fp16 / bf16 summed into fp32), which synchronises the
-// stream once.  out_status[b] = 1 iff the archive is valid, the bag's offsets
-// are ordered and inside t_idx and all its rows lie inside the element; a
-// failing bag's row is left untouched.  t_out's rows may lie at a stride.  The
-// checks that need no device come first.
-int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx, const at::Tensor& tOffsets,
-                        const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
-                        const std::optional<at::Tensor>& status) {
+// What gather_rows_pool (below) adds to gather_rows_sum's arguments: the mode,
+// the weights and the padding index of floatGatherRowsPool.
+struct PoolArgs {
+  const char* who;
+  PoolMode mode;
+  const std::optional<at::Tensor>& weights;
+  int64_t paddingIdx;  // negative: none
+};
+
+// The body of gather_rows_sum (pool == nullptr: floatGatherRowsSum) and of
+// gather_rows_pool (floatGatherRowsPool): the same arguments, checks and
+// messages, and for a pool its weights' checks.  The checks that need no
+// device come first.
+int64_t pooledRows(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx, const at::Tensor& tOffsets,
+                   const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
+                   const std::optional<at::Tensor>& status, const PoolArgs* pool) {
   TORCH_CHECK(rowWords >= 1 && uint64_t(rowWords) <= kU32Max, "row_words must be at least 1 (and below 2^32), not ",
               rowWords);
   TORCH_CHECK(tIdx.scalar_type() == at::kInt || tIdx.scalar_type() == at::kLong, "t_idx must be int32 or int64, not ",
@@ -745,6 +747,18 @@ int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tenso
   const int64_t rowStride = bags > 1 ? tOut.stride(0) : rowWords;
   TORCH_CHECK(rowStride >= rowWords, "t_out's rows must not overlap (row stride ", rowStride, " < row_words)");
   TORCH_CHECK(uint64_t(tIdx.numel()) <= kU32Max && uint64_t(bags) <= kU32Max, "too many indices or bags");
+  const bool weighted = pool && pool->weights.has_value();
+  if (weighted) {
+    const at::Tensor& tw = *pool->weights;
+    TORCH_CHECK(pool->mode == PoolMode::kSum, "per_sample_weights go with mode 'sum' alone, not '",
+                pool->mode == PoolMode::kMean ? "mean" : "max", "'");
+    // (a 16-bit t_out names the archive's type; under a float32 t_out it is known after the peek, below)
+    const auto wdt = tw.scalar_type(), named = tOut.scalar_type();
+    TORCH_CHECK(wdt == at::kFloat || (named == at::kFloat ? wdt == at::kHalf || wdt == at::kBFloat16 : wdt == named),
+                "per_sample_weights must be float32 or of the archive's dtype, not ", wdt);
+    TORCH_CHECK(tw.dim() == 1 && tw.numel() == tIdx.numel(), "per_sample_weights must be 1-d with t_idx's ",
+                tIdx.numel(), " entries");
+  }
   TORCH_CHECK(tOffsets.device().type() == at::kCUDA && tOffsets.is_contiguous() &&
                   tIdx.device().type() == at::kCUDA && tIdx.is_contiguous() &&
                   tIdx.get_device() == tOffsets.get_device(),
@@ -758,11 +772,75 @@ int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tenso
   cx.stack(tempMem);
   const FloatType outType = floatTypeOf(tOut.scalar_type());
   FloatType ft = outType;
-  if (ft == FloatType::kFloat32) ft = peekArchiveType(cx, m, tIn, "gather_rows_sum takes");
-  floatGatherRowsSum(*cx.res, floatConfig(ft, false), tIn.data_ptr(), uint32_t(rowWords), uint32_t(bags),
-                     uint32_t(tIdx.numel()), tIdx.data_ptr(), tOffsets.data_ptr(), tIdx.scalar_type() == at::kLong,
-                     tOut.data_ptr(), outType == FloatType::kFloat32, uint64_t(rowStride), st, cx.stream);
+  if (ft == FloatType::kFloat32) ft = peekArchiveType(cx, m, tIn, pool ? pool->who : "gather_rows_sum takes");
+  if (!pool) {
+    floatGatherRowsSum(*cx.res, floatConfig(ft, false), tIn.data_ptr(), uint32_t(rowWords), uint32_t(bags),
+                       uint32_t(tIdx.numel()), tIdx.data_ptr(), tOffsets.data_ptr(), tIdx.scalar_type() == at::kLong,
+                       tOut.data_ptr(), outType == FloatType::kFloat32, uint64_t(rowStride), st, cx.stream);
+    return cx.used();
+  }
+  FloatType wt = ft;
+  if (weighted) {
+    const at::Tensor& tw = *pool->weights;
+    TORCH_CHECK(tw.device().type() == at::kCUDA && tw.get_device() == dev && tw.is_contiguous(),
+                "per_sample_weights must be a contiguous GPU tensor on the archive's device");
+    wt = floatTypeOf(tw.scalar_type());
+    TORCH_CHECK(wt == FloatType::kFloat32 || wt == ft,
+                "per_sample_weights must be float32 or of the archive's dtype, not ", tw.scalar_type());
+  }
+  floatGatherRowsPool(*cx.res, floatConfig(ft, false), tIn.data_ptr(), uint32_t(rowWords), uint32_t(bags),
+                      uint32_t(tIdx.numel()), tIdx.data_ptr(), tOffsets.data_ptr(), tIdx.scalar_type() == at::kLong,
+                      pool->mode, weighted ? pool->weights->data_ptr() : nullptr, wt, pool->paddingIdx,
+                      tOut.data_ptr(), outType == FloatType::kFloat32, uint64_t(rowStride), st, cx.stream);
   return cx.used();
+}
+
+// Extension (no reference counterpart): embedding_bag(mode="sum") on a
+// compressed table (floatGatherRowsSum).  Bag b is t_idx[t_offsets[b] ..
+// t_offsets[b + 1]) (t_offsets holds B + 1 boundaries; both tensors int32 or
+// both int64, on the archive's device) and t_out [B, row_words] row b the fp32
+// sum of the bag's rows in list order, started from the first row and rounded
+// once to t_out's dtype; an empty bag gives +0.0.  float16 / bfloat16 outputs
+// name the archive's type themselves; for float32 outputs peekArchiveType
+// reads it (fp32, or fp16 / bf16 summed into fp32), which synchronises the
+// stream once.  out_status[b] = 1 iff the archive is valid, the bag's offsets
+// are ordered and inside t_idx and all its rows lie inside the element; a
+// failing bag's row is left untouched.  t_out's rows may lie at a stride.  The
+// checks that need no device come first.
+int64_t gather_rows_sum(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx, const at::Tensor& tOffsets,
+                        const at::Tensor& tOut, const std::optional<at::Tensor>& tempMem,
+                        const std::optional<at::Tensor>& status) {
+  return pooledRows(tIn, rowWords, tIdx, tOffsets, tOut, tempMem, status, nullptr);
+}
+
+// Extension (no reference counterpart): torch's embedding_bag on a compressed
+// table (floatGatherRowsPool).  t_in, t_idx, t_offsets (B + 1 boundaries: the
+// last offset is always included), t_out, temp_mem and out_status are
+// gather_rows_sum's.  mode "sum", "mean" or "max"; per_sample_weights ("sum"
+// alone): t_idx's length, float32 or the archive's dtype, on its device;
+// padding_idx: None, or a row whose entries are skipped (not decoded, not
+// counted, unable to fail a bag), a negative one counting from num_rows as in
+// torch.  An empty or all-padding bag gives +0.0.  The refusals that need no
+// device come first: an unknown mode, weights with mean or max, a weight dtype
+// that cannot go with the archive, a negative padding_idx without num_rows.
+int64_t gather_rows_pool(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tIdx, const at::Tensor& tOffsets,
+                         const at::Tensor& tOut, std::string mode, const std::optional<at::Tensor>& weights,
+                         std::optional<int64_t> paddingIdx, std::optional<int64_t> numRows,
+                         const std::optional<at::Tensor>& tempMem, const std::optional<at::Tensor>& status) {
+  TORCH_CHECK(mode == "sum" || mode == "mean" || mode == "max", "unknown mode '", mode, "' (sum, mean or max)");
+  int64_t pad = -1;
+  if (paddingIdx.has_value()) {
+    pad = *paddingIdx;
+    if (pad < 0) {
+      TORCH_CHECK(numRows.has_value(), "a negative padding_idx counts from the table's end and needs num_rows");
+      TORCH_CHECK(pad >= -*numRows, "padding_idx ", pad, " lies outside a table of ", *numRows, " rows");
+      pad += *numRows;
+    }
+  }
+  const PoolArgs pool{"gather_rows_pool takes",
+                      mode == "sum" ? PoolMode::kSum : (mode == "mean" ? PoolMode::kMean : PoolMode::kMax), weights,
+                      pad};
+  return pooledRows(tIn, rowWords, tIdx, tOffsets, tOut, tempMem, status, &pool);
 }
 
 // Extension (no reference counterpart): y = x W^T on a compressed weight table
@@ -1033,6 +1111,10 @@ TORCH_LIBRARY(dietgpu, m) {
       "gather_rows_sum(Tensor t_in, int row_words, Tensor t_idx, Tensor t_offsets, Tensor t_out, Tensor? "
       "temp_mem=None, Tensor? out_status=None) -> int");
   m.def(
+      "gather_rows_pool(Tensor t_in, int row_words, Tensor t_idx, Tensor t_offsets, Tensor t_out, str mode=\"sum\", "
+      "Tensor? per_sample_weights=None, int? padding_idx=None, int? num_rows=None, Tensor? temp_mem=None, Tensor? "
+      "out_status=None) -> int");
+  m.def(
       "matmul_rows(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, Tensor? temp_mem=None, Tensor? "
       "out_status=None) -> int");
   m.def(
@@ -1062,6 +1144,7 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("gather_rows", &dietgpu::gather_rows);
   m.impl("reduce_data", &dietgpu::reduce_data);
   m.impl("gather_rows_sum", &dietgpu::gather_rows_sum);
+  m.impl("gather_rows_pool", &dietgpu::gather_rows_pool);
   m.impl("matmul_rows", &dietgpu::matmul_rows);
   m.impl("matmul_tile", &dietgpu::matmul_tile);
   m.impl("matmul_grouped", &dietgpu::matmul_grouped);

@@ -24,6 +24,7 @@ validation and return values; "ext": not in the reference.
     gather_rows                       ext   MORE_OPS    rows of a table held by one archive, by device indices
     reduce_data                       ext   REDUCE_OPS  sums several archives per member in one kernel
     gather_rows_sum                   ext   POOL_OPS    sums bags of rows of a table held by one archive
+    gather_rows_pool                  ext   POOL_MODE_OPS  the same with a mode (sum, mean, max), weights, a padding index
     matmul_rows                       ext   MATMUL_OPS  x W^T for a few rows of x, W a table held by one archive
     matmul_tile                       ext   TILE_OPS    the same through the matrix pipe: 1 .. 64 rows, one decode
     matmul_grouped                    ext   GROUP_OPS   matmul_tile over many expert tables, routed on the device
@@ -65,6 +66,10 @@ REDUCE_OPS = ("reduce_data",)
 # kernel: embedding_bag(mode="sum") on a compressed table
 POOL_OPS = ("gather_rows_sum",)
 
+# gather_rows_pool is the rest of embedding_bag on a compressed table: mean and
+# max pooling, per-sample weights, a padding index
+POOL_MODE_OPS = ("gather_rows_pool",)
+
 # matmul_rows multiplies up to 64 activation rows into a weight table held by
 # one archive, out of the decoder's registers: a compressed nn.Linear forward
 MATMUL_OPS = ("matmul_rows",)
@@ -99,7 +104,8 @@ def register():
 
 
 def __getattr__(name):
-    if name in OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS + SPARSE_MATMUL_OPS:
+    if name in (OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + POOL_MODE_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS
+                + SPARSE_MATMUL_OPS):
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

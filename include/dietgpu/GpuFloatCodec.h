@@ -336,6 +336,43 @@ void floatGatherRowsSum(StackDeviceMemory& res,
                         bool outIsFp32, uint64_t outRowStrideWords,
                         uint8_t* outSuccess_dev, hipStream_t stream);
 
+// Pooled row gather with a pooling mode, per-sample weights and a padding
+// index: torch's embedding_bag on a compressed table.  Archive, idx_dev,
+// offsets_dev, out, outSuccess_dev, failure rules and refusals are
+// floatGatherRowsSum's.  With x_t the rows of bag b that are not paddingIdx, in
+// list order, f the exact conversion to fp32 and n_b their count, per column:
+//   kSum            floatGatherRowsSum's sum, and its bits
+//   kSum, weights   acc = w_1 * f(x_1) (one fp32 multiply), then
+//                   acc = fmaf(w_t, f(x_t), acc) in list order; with every
+//                   weight 1.0 the bits of the unweighted sum
+//   kMean           the unweighted sum, one correctly rounded fp32 division by
+//                   float(n_b)
+//   kMax            m = f(x_1); m = (f(x_t) > m || isnan(f(x_t))) ? f(x_t) : m:
+//                   a NaN in any row makes the column NaN, of equal values and
+//                   of +0 against -0 the first in list order stays; an out of
+//                   the archive's type carries the table's word bit for bit
+// and one rounding to the output type.  A bag that is empty or all padding
+// gives +0.0 in every mode, status 1.  weights_dev (kSum alone; nullptr for
+// none) holds numIdx words of weightType, fp32 or the archive's 16-bit type,
+// weights[i] the weight of idx[i]; the weight of a padding entry never enters
+// the sum.  paddingIdx < 0: none; an entry equal to it is skipped before the
+// range check: it is not decoded, not counted in n_b and cannot fail the bag
+// (so it may lie outside the table).  One launch, no host synchronisation, no
+// allocation, no atomics: capturable in a graph, the same bits on every run,
+// and for a bag whatever the other bags are.  Refused before any launch, beyond
+// floatGatherRowsSum's refusals: weights with kMean or kMax, and a weightType
+// that is neither fp32 nor the archive's type.
+enum class PoolMode : int { kSum = 0, kMean = 1, kMax = 2 };
+void floatGatherRowsPool(StackDeviceMemory& res,
+                         const FloatDecompressConfig& config,
+                         const void* archive_dev, uint32_t rowWords,
+                         uint32_t numBags, uint32_t numIdx, const void* idx_dev,
+                         const void* offsets_dev, bool idxIs64, PoolMode mode,
+                         const void* weights_dev, FloatType weightType,
+                         int64_t paddingIdx, void* out_dev, bool outIsFp32,
+                         uint64_t outRowStrideWords, uint8_t* outSuccess_dev,
+                         hipStream_t stream);
+
 // Matmul on a compressed weight table (y = x W^T straight from the archive):
 // the dense fp16 / bf16 / fp32 archive holds W [numRows, rowWords] row-major;
 // x_dev holds M rows of rowWords words of the archive's type, xRowStrideWords

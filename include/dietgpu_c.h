@@ -299,6 +299,29 @@ int dietgpu_float_gather_rows_sum(dietgpu_stack* res, int float_type, int prob_b
                                   uint64_t out_row_stride_words, uint8_t* out_success_dev,
                                   void* stream);
 
+/* Pooled row gather with a mode, per-sample weights and a padding index
+ * (floatGatherRowsPool, GpuFloatCodec.h): embedding_bag on a compressed table.
+ * Every argument of dietgpu_float_gather_rows_sum as there, and
+ *   mode          0 sum, 1 mean (the sum, one fp32 division by the count of
+ *                 the bag's non-padding rows), 2 max (a NaN wins, of equal
+ *                 values the first stays; a 16-bit out carries table words)
+ *   weight_type   0: none (weights_dev is not looked at); 3: fp32 weights;
+ *                 float_type (1 or 2): weights of the archive's type.  mode 0
+ *                 alone.  weights_dev[i] is the weight of idx_dev[i]:
+ *                 acc = w_1 * x_1, then acc = fmaf(w_t, x_t, acc) in fp32
+ *   padding_idx   negative: none; an entry equal to it is skipped before the
+ *                 range check, not counted and unable to fail the bag
+ * A bag that is empty or all padding gives +0.0, status 1.  mode 0 without
+ * weights gives the bits of dietgpu_float_gather_rows_sum.  One launch, no
+ * host synchronisation, no allocation.  No checksum flag. */
+int dietgpu_float_gather_rows_pool(dietgpu_stack* res, int float_type, int prob_bits,
+                                   const void* archive_dev, uint32_t row_words, uint32_t num_bags,
+                                   uint32_t num_idx, const void* idx_dev, const void* offsets_dev,
+                                   int idx_is_64, int mode, const void* weights_dev, int weight_type,
+                                   int64_t padding_idx, void* out_dev, int out_is_fp32,
+                                   uint64_t out_row_stride_words, uint8_t* out_success_dev,
+                                   void* stream);
+
 /* Matmul on a compressed weight table (floatMatmulRows, GpuFloatCodec.h): the
  * archive holds W [num_rows, row_words]; x_dev holds m rows of row_words words
  * of the archive's type, x_row_stride_words apart (base and stride whole
