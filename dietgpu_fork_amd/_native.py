@@ -103,6 +103,9 @@ def _declare(L):
         "dietgpu_float_matmul_sparse_rows": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int,
                                                      c_u64, c_u32, P, P]),
         "dietgpu_float_matmul_sparse_scratch_bytes": (c_u64, [c_int, c_u32, c_u32, c_u32, c_u32]),
+        "dietgpu_float_matmul_sparse_tile": (c_int, [vp, c_int, c_int, P, c_u32, c_u32, P, c_u32, c_u64, P, c_int,
+                                                     c_u64, c_u32, P, P]),
+        "dietgpu_float_matmul_sparse_tile_scratch_bytes": (c_u64, [c_int, c_u32, c_u32, c_u32, c_u32]),
         "dietgpu_set_matmul_grouped_grid": (None, [c_u32]),
         "dietgpu_set_matmul_grid": (None, [c_u32]),
         "dietgpu_profile_enable": (None, [c_int]),
@@ -116,7 +119,8 @@ def _declare(L):
     optional = {"dietgpu_set_barrier_budget", "dietgpu_set_dispatch_skew",
                 "dietgpu_barrier_fallback_count", "dietgpu_set_compress_path", "dietgpu_set_matmul_grid",
                 "dietgpu_float_matmul_sparse_rows", "dietgpu_float_matmul_sparse_scratch_bytes",
-                "dietgpu_float_gather_rows_pool"}
+                "dietgpu_float_gather_rows_pool", "dietgpu_float_matmul_sparse_tile",
+                "dietgpu_float_matmul_sparse_tile_scratch_bytes"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue

@@ -706,7 +706,7 @@ def gather_rows_pool(archive, row_words, idx, offsets, dtype, mode="sum", per_sa
 
 
 def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None, prob_bits=10,
-                check=False, _tile=False, _sparse=False, _nnz_bound=None):
+                check=False, _tile=False, _sparse=False, _nnz_bound=None, _sparse_tile=False):
     """y = x @ W.T for a weight table W [R, row_words] stored as one dense
     float16 / bfloat16 / float32 archive of `dtype` -> (out [M, R], ok).  x is
     a CUDA tensor [M, row_words] of `dtype`, 1 <= M <= 64, its rows contiguous,
@@ -723,9 +723,14 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
     Nothing is uploaded or read back, so the call (two launches per 4 rows of
     x, scratch from `ws`) can be captured in a graph and replayed on new x and
     new archive bytes.  check=True reads ok back and raises DietGpuError."""
-    who = "matmul_tile" if _tile else "matmul_sparse" if _sparse else "matmul_rows"
+    who = ("matmul_tile" if _tile else "matmul_sparse_tile" if _sparse_tile else "matmul_sparse" if _sparse
+           else "matmul_rows")
     if dtype == torch.uint8:
         raise ValueError(f"{who}: byte archives hold no floats to multiply")
+    if _sparse_tile and dtype == torch.float32:
+        raise ValueError(f"{who}: float32 archives go through matmul_sparse (the matrix pipe multiplies 16-bit words)")
+    if _sparse_tile and dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}: unsupported dtype {dtype} (float16 or bfloat16 archives)")
     if _tile and dtype == torch.float32:
         raise ValueError(f"{who}: float32 archives go through matmul_rows (the matrix pipe multiplies 16-bit words)")
     if dtype not in (torch.float16, torch.bfloat16) + (() if _tile else (torch.float32,)):
@@ -777,9 +782,16 @@ def matmul_rows(archive, row_words, x, dtype, out=None, out_dtype=None, out_stat
         raise ValueError(f"{who}: out_status must be a uint8 tensor of one entry")
     if _sparse:
         nnz_bound = int(_nnz_bound)
+        fn = N.lib().dietgpu_float_matmul_sparse_rows
+        if _sparse_tile:
+            fn = getattr(N.lib(), "dietgpu_float_matmul_sparse_tile", None)
+            if fn is None:  # (an older library swapped in for an A/B run: _native.py loads it without this entry)
+                raise N.DietGpuError(f"{who}: the loaded libdietgpu_amd.so has no dietgpu_float_matmul_sparse_tile; "
+                                     "rebuild it")
         if ws is None:
-            ws = Workspace(matmul_sparse_scratch_bytes(FLOAT_TYPE[dtype], row_words, rows, M, nnz_bound), x.device)
-        N.check(N.lib().dietgpu_float_matmul_sparse_rows(
+            size = matmul_sparse_tile_scratch_bytes if _sparse_tile else matmul_sparse_scratch_bytes
+            ws = Workspace(size(FLOAT_TYPE[dtype], row_words, rows, M, nnz_bound), x.device)
+        N.check(fn(
             ws.h, FLOAT_TYPE[dtype], prob_bits, archive.data_ptr(), row_words, rows, x.data_ptr(), M, x_stride,
             out.data_ptr(), int(out_dtype == torch.float32), out_stride, nnz_bound, ok.data_ptr(), _s()))
         if check and not bool(ok.all()):
@@ -863,6 +875,37 @@ def matmul_sparse(archive, row_words, x, dtype, out=None, out_dtype=None, out_st
     DietGpuError."""
     return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
                        prob_bits=prob_bits, check=check, _sparse=True, _nnz_bound=nnz_bound)
+
+
+def matmul_sparse_tile_scratch_bytes(ft, row_words, rows, M, nnz_bound):
+    """The workspace bytes a matmul_sparse_tile call of that shape takes
+    (matmul_sparse_scratch_bytes' arguments); raises DietGpuError for a shape
+    the call refuses.  Host only: no device is touched."""
+    return N.size_or_raise(N.lib().dietgpu_float_matmul_sparse_tile_scratch_bytes(int(ft), int(row_words), int(rows),
+                                                                                int(M), int(nnz_bound)))
+
+
+def matmul_sparse_tile(archive, row_words, x, dtype, out=None, out_dtype=None, out_status=None, ws=None,
+                       prob_bits=10, nnz_bound=None, check=False):
+    """matmul_sparse through the matrix pipe, for float16 / bfloat16 sparse
+    archives: all 1 <= M <= 64 rows of x in ONE pass over the decoded nonzero
+    list and the bitmap (matmul_sparse goes over the list once per eight rows),
+    so this is the path of a small batch or a short prefill on a pruned table.
+    Arguments, nnz_bound, status, alignment and refusals are matmul_sparse's; a
+    float32 `dtype` is refused.  The products are exact, the sums fp32 in an
+    order that depends on row_words alone -- the same bits on every run, for
+    row r whatever else the table holds and whatever R the call names, for row
+    m whatever M is; not the bits of matmul_sparse or matmul_tile -- rounded
+    once to out's dtype.
+    A CLEAR BIT IS MULTIPLIED HERE, as a weight of +0.0: the one difference
+    from matmul_sparse, which skips it.  For finite x the value is
+    matmul_sparse's up to the order of the sums; an Inf or NaN in x[m, k] over
+    a zero of W[r, k] gives NaN in out[m, r], as a dense product does.
+    The expanded matrix is never stored.  With nnz_bound and `out` given
+    nothing is uploaded or read back, and the call (five launches) can be
+    captured in a graph and replayed on new x and new archive bytes."""
+    return matmul_rows(archive, row_words, x, dtype, out=out, out_dtype=out_dtype, out_status=out_status, ws=ws,
+                       prob_bits=prob_bits, check=check, _sparse=True, _nnz_bound=nnz_bound, _sparse_tile=True)
 
 
 def set_matmul_grid(workgroups):

@@ -529,6 +529,33 @@ uint64_t dietgpu_float_matmul_sparse_scratch_bytes(int ft, uint32_t row_words, u
   return v;
 }
 
+int dietgpu_float_matmul_sparse_tile(dietgpu_stack* res, int ft, int pb, const void* archive_dev, uint32_t row_words,
+                                     uint32_t num_rows, const void* x_dev, uint32_t m, uint64_t x_row_stride,
+                                     void* out_dev, int out_is_fp32, uint64_t out_row_stride,
+                                     uint32_t list_capacity_words, uint8_t* succ, void* stream) {
+  return guarded([&] {
+    // (before the stack or any pointer is looked at, as dietgpu_float_matmul_rows)
+    const FloatCodecConfig cfg = floatCfg(ft, pb, 0);
+    checkProbBits(pb);
+    checkMatmulSparseTileShape(ft, out_is_fp32 != 0, row_words, num_rows, m, x_row_stride, out_row_stride,
+                               list_capacity_words);
+    floatMatmulSparseTile(R(res), cfg, archive_dev, row_words, num_rows, x_dev, m, x_row_stride, out_dev,
+                          out_is_fp32 != 0, out_row_stride, list_capacity_words, succ, S(stream));
+    return DIETGPU_OK;
+  });
+}
+
+uint64_t dietgpu_float_matmul_sparse_tile_scratch_bytes(int ft, uint32_t row_words, uint32_t num_rows, uint32_t m,
+                                                        uint32_t list_capacity_words) {
+  uint64_t v = 0;
+  guarded([&] {
+    DG_CHECK(ft >= 1 && ft <= 4, "float_type must be 1..4");
+    v = floatMatmulSparseTileScratchBytes(FloatType(ft), row_words, num_rows, m, list_capacity_words);
+    return DIETGPU_OK;
+  });
+  return v;
+}
+
 uint32_t dietgpu_device_error_count(int reset) {
   uint32_t v = 0;
   guarded([&] {

@@ -167,6 +167,22 @@ inline void checkMatmulTileShape(int floatType, bool outIsFp32, uint32_t rowWord
   checkMatmulShape(floatType, outIsFp32, rowWords, numRows, M, xRowStrideWords, outRowStrideWords);
 }
 
+// The matmul on a sparse archive through the matrix pipe
+// (floatMatmulSparseTile): fp16 and bf16 archives alone, each other type with
+// its own message; then checkMatmulShape and checkSparseListCapacity.  The C
+// ABI makes the same checks before it looks at the stack or any pointer.
+inline void checkMatmulSparseTileShape(int floatType, bool outIsFp32, uint32_t rowWords, uint32_t numRows, uint32_t M,
+                                       uint64_t xRowStrideWords, uint64_t outRowStrideWords,
+                                       uint32_t listCapacityWords) {
+  DG_CHECK(floatType != 3, "a tiled sparse matmul multiplies 16-bit words (float type 1 or 2); matmul_sparse is the "
+                           "path of an fp32 archive");
+  DG_CHECK(floatType != 4, "a tiled sparse matmul takes fp16 or bf16 archives (float type 1 or 2), not fp64");
+  DG_CHECK(floatType == 1 || floatType == 2,
+           "a tiled sparse matmul takes fp16 or bf16 archives (float type 1 or 2), not " << floatType);
+  checkMatmulShape(floatType, outIsFp32, rowWords, numRows, M, xRowStrideWords, outRowStrideWords);
+  checkSparseListCapacity(listCapacityWords);
+}
+
 // The grouped matmul (floatMatmulGrouped): checkMatmulTileShape's refusals for
 // one table first (any number of rows T: an expert's rows go 64 at a time),
 // then 1 .. 1024 experts, T >= 1 and partials that 32-bit indices reach.  The C

@@ -288,4 +288,54 @@ inline SparseMatmulPlan planSparseMatmul(uint32_t wordBytes, uint32_t numRows, u
   return p;
 }
 
+// ---------------------------------------------------------------------------
+// the same product through the matrix pipe: one pass over the
+// list for all M <= 64 rows of x, a task per 16 weight rows and 1024 columns
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSparseTileRows = 16;      // weight rows of a task (sparse_matmul_tile.hip static_asserts both)
+constexpr uint32_t kSparseTileWords = 1024;   // columns of a task: a slice of a row
+
+struct SparseMatmulTilePlan {
+  bool valid = false;  // planSparseMatmul's rule with M * numRows * slices < 2^32
+  uint32_t chunks = 0;     // 1024-word chunks that hold words of the table
+  uint32_t cblocks = 0;    // k_sparseChunks and k_sparseChunkOffsets workgroups
+  uint32_t rowBlocks = 0;  // ceil(numRows / 16)
+  uint32_t slices = 0;     // ceil(rowWords / 1024): partial sums per (m, r)
+  uint32_t tasks = 0;      // rowBlocks * slices: k_sparseMatmulTile workgroups
+  uint32_t finishGrid = 0;  // k_sparseMatmulTileFinish workgroups: a thread per (m, r)
+  // element counts of the allocations, in the order they are taken
+  uint64_t densePtrs = 1, sizes = 1, denseOk = 1;  // u64, u32, u8: k_sparseChunks' and the dense decode's
+  uint64_t listBytes = 0;                          // the decoded nonzero list
+  uint64_t chunkPre = 0, blockTot = 0, chunkOff = 0;  // u32
+  uint64_t partWords = 0;                          // fp32 [M][numRows][slices]
+  // the arena bytes of the whole call (granules as planSparseReduce's)
+  uint64_t scratchBytes = 0;
+};
+
+inline SparseMatmulTilePlan planSparseMatmulTile(uint32_t wordBytes, uint32_t numRows, uint32_t rowWords, uint32_t M,
+                                                 uint32_t listCapacity) {
+  SparseMatmulTilePlan p;
+  const uint64_t total = uint64_t(numRows) * rowWords;
+  if (rowWords < 1 || rowWords % kMatmulSegWords != 0 || M < 1 || M > kMatmulMaxRows || numRows < 1 ||
+      total >= (1ull << 32) || listCapacity < 1 || listCapacity >= UINT32_MAX - 32)
+    return p;
+  p.chunks = uint32_t((total + splan::kChunkWords - 1) / splan::kChunkWords);
+  p.cblocks = splan::div32(p.chunks, splan::kThreads);
+  p.rowBlocks = splan::div32(numRows, kSparseTileRows);
+  p.slices = splan::div32(rowWords, kSparseTileWords);
+  p.partWords = uint64_t(M) * numRows * p.slices;
+  if (p.partWords >= (1ull << 32)) return p;
+  p.tasks = p.rowBlocks * p.slices;  // a grid x far below 2^31: total < 2^32
+  p.finishGrid = splan::div32(M * numRows, splan::kThreads);
+  p.listBytes = splan::listStride(listCapacity, wordBytes);
+  p.chunkPre = p.chunkOff = p.chunks;
+  p.blockTot = p.cblocks;
+  auto granules = [](uint64_t bytes) { return std::max<uint64_t>((bytes + 255) / 256, 1) * 256; };
+  p.scratchBytes = granules(8 * p.densePtrs) + granules(4 * p.sizes) + granules(p.denseOk) + granules(p.listBytes) +
+                   granules(4 * p.chunkPre) + granules(4 * p.blockTot) + granules(4 * p.chunkOff) +
+                   granules(4 * p.partWords);
+  p.valid = true;
+  return p;
+}
+
 }  // namespace dietgpu

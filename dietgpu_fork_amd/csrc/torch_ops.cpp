@@ -28,6 +28,7 @@
 //   matmul_tile                       ext   floatMatmulTile
 //   matmul_grouped                    ext   floatMatmulGrouped
 //   matmul_sparse                     ext   floatMatmulSparseRows
+//   matmul_sparse_tile                ext   floatMatmulSparseTile
 //   (*) after floatGetCompressedInfo on ts_in[0] / t_in where only float32 tensors
 //       would name the archives' type (peekArchiveType)
 //
@@ -860,17 +861,24 @@ int64_t gather_rows_pool(const at::Tensor& tIn, int64_t rowWords, const at::Tens
 // skipped (an Inf or NaN of t_x there does not reach t_out), and nnz_bound >= 1
 // is the word count of the archive's nonzero list or a bound on it, which
 // sizes the scratch; out_status[0] is also 0 when the list does not fit it.
-enum class MatmulKind { kRows, kTile, kSparse };
+// kSparseTile: matmul_sparse_tile (floatMatmulSparseTile): matmul_sparse's
+// arguments, float16 and bfloat16 alone, all the rows in one pass over the
+// list through the matrix pipe; a word under a clear bit is a +0.0 weight that
+// IS multiplied (an Inf or NaN of t_x there gives NaN in t_out).
+enum class MatmulKind { kRows, kTile, kSparse, kSparseTile };
 
 int64_t matmulOp(MatmulKind kind, const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX,
                  const at::Tensor& tOut, int64_t nnzBound, const std::optional<at::Tensor>& tempMem,
                  const std::optional<at::Tensor>& status) {
   const bool tile = kind == MatmulKind::kTile;
+  const bool sparse = kind == MatmulKind::kSparse || kind == MatmulKind::kSparseTile;
   TORCH_CHECK(rowWords >= 1 && rowWords % 256 == 0 && uint64_t(rowWords) <= kU32Max,
               "row_words must be a positive multiple of 256 (pad the rows with zeros), not ", rowWords);
   checkDtype(tX, tX.scalar_type(), {false, "t_x", "t_x"});
   TORCH_CHECK(!tile || tX.scalar_type() != at::kFloat,
               "matmul_tile multiplies float16 or bfloat16 words; matmul_rows is the path of a float32 archive");
+  TORCH_CHECK(kind != MatmulKind::kSparseTile || tX.scalar_type() != at::kFloat,
+              "matmul_sparse_tile multiplies float16 or bfloat16 words; matmul_sparse is the path of a float32 archive");
   TORCH_CHECK(tOut.scalar_type() == tX.scalar_type() || tOut.scalar_type() == at::kFloat, "t_out must have t_x's dtype (",
               tX.scalar_type(), ") or float32, not ", tOut.scalar_type());
   const int64_t k = tX.dim() - 1;
@@ -884,7 +892,7 @@ int64_t matmulOp(MatmulKind kind, const at::Tensor& tIn, int64_t rowWords, const
   TORCH_CHECK(M >= 1 && M <= int64_t(kMatmulMaxRows), "t_x must hold 1 .. ", kMatmulMaxRows,
               " rows (for more, decompress and call a GEMM), not ", M);
   TORCH_CHECK(uint64_t(rows) * uint64_t(rowWords) <= kU32Max, "R * row_words must be below 2^32");
-  TORCH_CHECK(kind != MatmulKind::kSparse || (nnzBound >= 1 && uint64_t(nnzBound) < kU32Max - 32),
+  TORCH_CHECK(!sparse || (nnzBound >= 1 && uint64_t(nnzBound) < kU32Max - 32),
               "nnz_bound must be at least 1 (and below 2^32 - 33), not ", nnzBound);
   // rows at one stride: leading dimension d strides over the rows inside it
   auto rowStride = [&](const at::Tensor& t, int64_t width, const char* name) {
@@ -914,8 +922,8 @@ int64_t matmulOp(MatmulKind kind, const at::Tensor& tIn, int64_t rowWords, const
   cx.stack(tempMem);
   const auto cfg = floatConfig(floatTypeOf(tX.scalar_type()), false);
   const bool out32 = tOut.scalar_type() == at::kFloat;
-  if (kind == MatmulKind::kSparse) {
-    floatMatmulSparseRows(*cx.res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(M),
+  if (sparse) {
+    (kind == MatmulKind::kSparseTile ? floatMatmulSparseTile : floatMatmulSparseRows)(*cx.res, cfg, tIn.data_ptr(), uint32_t(rowWords), uint32_t(rows), tX.data_ptr(), uint32_t(M),
                           uint64_t(xStride), tOut.data_ptr(), out32, uint64_t(outStride), uint32_t(nnzBound), st,
                           cx.stream);
   } else {
@@ -940,6 +948,12 @@ int64_t matmul_sparse(const at::Tensor& tIn, int64_t rowWords, const at::Tensor&
                       int64_t nnzBound, const std::optional<at::Tensor>& tempMem,
                       const std::optional<at::Tensor>& status) {
   return matmulOp(MatmulKind::kSparse, tIn, rowWords, tX, tOut, nnzBound, tempMem, status);
+}
+
+int64_t matmul_sparse_tile(const at::Tensor& tIn, int64_t rowWords, const at::Tensor& tX, const at::Tensor& tOut,
+                           int64_t nnzBound, const std::optional<at::Tensor>& tempMem,
+                           const std::optional<at::Tensor>& status) {
+  return matmulOp(MatmulKind::kSparseTile, tIn, rowWords, tX, tOut, nnzBound, tempMem, status);
 }
 
 // Extension (no reference counterpart): matmul_tile over many expert tables in
@@ -1126,6 +1140,9 @@ TORCH_LIBRARY(dietgpu, m) {
   m.def(
       "matmul_sparse(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, int nnz_bound, Tensor? temp_mem=None, "
       "Tensor? out_status=None) -> int");
+  m.def(
+      "matmul_sparse_tile(Tensor t_in, int row_words, Tensor t_x, Tensor t_out, int nnz_bound, Tensor? temp_mem=None, "
+      "Tensor? out_status=None) -> int");
 }
 
 TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
@@ -1149,4 +1166,5 @@ TORCH_LIBRARY_IMPL(dietgpu, CompositeExplicitAutograd, m) {
   m.impl("matmul_tile", &dietgpu::matmul_tile);
   m.impl("matmul_grouped", &dietgpu::matmul_grouped);
   m.impl("matmul_sparse", &dietgpu::matmul_sparse);
+  m.impl("matmul_sparse_tile", &dietgpu::matmul_sparse_tile);
 }

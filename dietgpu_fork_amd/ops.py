@@ -29,6 +29,7 @@ validation and return values; "ext": not in the reference.
     matmul_tile                       ext   TILE_OPS    the same through the matrix pipe: 1 .. 64 rows, one decode
     matmul_grouped                    ext   GROUP_OPS   matmul_tile over many expert tables, routed on the device
     matmul_sparse                     ext   SPARSE_MATMUL_OPS  x W^T on a sparse archive of a pruned table: zeros skipped
+    matmul_sparse_tile                ext   SPARSE_TILE_OPS  the same through the matrix pipe: 1 .. 64 rows, one list pass, zeros multiplied
 """
 import os
 
@@ -86,6 +87,11 @@ GROUP_OPS = ("matmul_grouped",)
 # list) of a pruned table: the list is decoded once, the zeros are skipped
 SPARSE_MATMUL_OPS = ("matmul_sparse",)
 
+# matmul_sparse_tile is that product for float16 / bfloat16 through the matrix
+# pipe: every row of x in one pass over the nonzero list; a clear bit is a
+# +0.0 weight that is multiplied (Inf or NaN of x there gives NaN)
+SPARSE_TILE_OPS = ("matmul_sparse_tile",)
+
 _LOADED = False
 
 
@@ -105,7 +111,7 @@ def register():
 
 def __getattr__(name):
     if name in (OPS + MORE_OPS + REDUCE_OPS + POOL_OPS + POOL_MODE_OPS + MATMUL_OPS + TILE_OPS + GROUP_OPS
-                + SPARSE_MATMUL_OPS):
+                + SPARSE_MATMUL_OPS + SPARSE_TILE_OPS):
         register()
         return getattr(torch.ops.dietgpu, name)
     raise AttributeError(name)

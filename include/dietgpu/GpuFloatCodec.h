@@ -505,4 +505,44 @@ uint64_t floatMatmulSparseScratchBytes(FloatType floatType, uint32_t rowWords,
                                        uint32_t numRows, uint32_t M,
                                        uint32_t listCapacityWords);
 
+// floatMatmulSparseRows through the matrix pipe, for fp16 and bf16 sparse
+// archives: all 1 <= M <= 64 rows of x in ONE pass over the decoded nonzero
+// list and the bitmap (floatMatmulSparseRows makes one per eight rows), the
+// path of a small batch or a short prefill on a pruned table.  Every argument
+// is floatMatmulSparseRows'.
+//   out[m * outRowStrideWords + r] = round_out(sum_k x[m, k] * W[r, k])
+// the products exact, the sums fp32, one rounding to out's type.  A CLEAR
+// BITMAP BIT IS A +0.0 WEIGHT WORD HERE AND IS MULTIPLIED -- the one
+// difference from floatMatmulSparseRows, which skips it: the matrix
+// instruction shares its activation operand among 16 weight rows, so x cannot
+// be masked per row.  For finite x the value is floatMatmulSparseRows' up to
+// the order of the sums; an Inf or NaN in x[m, k] over a zero of W[r, k] gives
+// NaN in out[m, r], as a dense product does.  The order of the adds is a
+// function of rowWords alone: the same bits on every run, for row r whatever
+// else the table holds and whatever numRows the call names, for row m whatever
+// M is; nothing is promised against the bits of floatMatmulSparseRows or
+// floatMatmulTile.  outSuccess_dev, failure (only the status is written),
+// listCapacityWords and the memory safety under a corrupt bitmap are
+// floatMatmulSparseRows'.  Scratch (floatMatmulSparseTileScratchBytes) comes
+// from res; five launches, no host synchronisation, no upload, no atomics, no
+// wait between workgroups: the call can be captured in a graph and replayed on
+// new x and new archive bytes.  Refused before any launch: fp32 and fp64
+// archives, each with its own message, a config with useChecksum, and
+// floatMatmulSparseRows' other refusals.
+void floatMatmulSparseTile(StackDeviceMemory& res,
+                           const FloatDecompressConfig& config,
+                           const void* archive_dev, uint32_t rowWords,
+                           uint32_t numRows, const void* x_dev, uint32_t M,
+                           uint64_t xRowStrideWords, void* out_dev,
+                           bool outIsFp32, uint64_t outRowStrideWords,
+                           uint32_t listCapacityWords, uint8_t* outSuccess_dev,
+                           hipStream_t stream);
+
+// The scratch bytes floatMatmulSparseTile takes from res for such a call.
+// Host only: no device is touched.
+uint64_t floatMatmulSparseTileScratchBytes(FloatType floatType,
+                                           uint32_t rowWords, uint32_t numRows,
+                                           uint32_t M,
+                                           uint32_t listCapacityWords);
+
 } // namespace dietgpu

@@ -43,6 +43,8 @@
  *   task line, the routing read on the device)
  *   dietgpu_float_matmul_sparse_rows (that product on a sparse archive of a
  *   pruned table: bitmap and nonzero list, the expanded matrix never stored)
+ *   dietgpu_float_matmul_sparse_tile (the same through the matrix pipe: up to
+ *   64 rows of x in one pass over the list; a clear bit is a multiplied zero)
  *
  * Conventions: `stream` is a hipStream_t (NULL = default stream); the
  * `res` arena is the reference's StackDeviceMemory& first argument; float
@@ -397,6 +399,25 @@ int dietgpu_float_matmul_sparse_rows(dietgpu_stack* res, int float_type, int pro
 uint64_t dietgpu_float_matmul_sparse_scratch_bytes(int float_type, uint32_t row_words,
                                                    uint32_t num_rows, uint32_t m,
                                                    uint32_t list_capacity_words);
+
+/* dietgpu_float_matmul_sparse_rows through the matrix pipe
+ * (floatMatmulSparseTile, GpuFloatCodec.h), for float_type 1 and 2: all 1 ..
+ * 64 rows of x in one pass over the nonzero list.  Every argument, the status
+ * and what a failure leaves are dietgpu_float_matmul_sparse_rows'.  The one
+ * difference: a word whose bitmap bit is clear is a +0.0 weight and IS
+ * multiplied, so an Inf or NaN of x over it gives NaN in out_dev, as a dense
+ * product does.  float_type 3 and 4 are refused, each with its own message.
+ * Scratch (dietgpu_float_matmul_sparse_tile_scratch_bytes) comes from res. */
+int dietgpu_float_matmul_sparse_tile(dietgpu_stack* res, int float_type, int prob_bits,
+                                     const void* archive_dev, uint32_t row_words,
+                                     uint32_t num_rows, const void* x_dev, uint32_t m,
+                                     uint64_t x_row_stride_words, void* out_dev, int out_is_fp32,
+                                     uint64_t out_row_stride_words, uint32_t list_capacity_words,
+                                     uint8_t* out_success_dev, void* stream);
+/* ... and its scratch bytes; 0 for a shape the call refuses (dietgpu_last_error) */
+uint64_t dietgpu_float_matmul_sparse_tile_scratch_bytes(int float_type, uint32_t row_words,
+                                                        uint32_t num_rows, uint32_t m,
+                                                        uint32_t list_capacity_words);
 
 /* Kernel timing hook used by bench.py: when enabled, every launch of the
  * named kernel family ("encode", "decode", "decode_range", "decode_accumulate",
